@@ -354,6 +354,41 @@ def roofline_entries(by_shape, KT, lib):
     return main
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 18     # arrays above this are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(directory, last, prefix="", world=1):
+    """What the timed path returned from its last step, one DIR/<prefix>stage<s>_<key>.npy per tensor (float32; python
+    scalars float64).  An array larger than DUMP_MAX_ELEMS is flattened and sampled at sorted indices drawn from a
+    generator seeded by its name, so two builds given the same arguments write the same elements.  N > 1: each rank writes
+    its own files, with the sample size and byte budget split over the ranks.  Returns the names."""
+    import zlib
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = []
+    for s in sorted(last):
+        for k, v in sorted((last[s] or {}).items()):
+            if v is None:
+                continue
+            name = "%sstage%d_%s" % (prefix, s, k)
+            if torch.is_tensor(v):
+                a = v.detach().float().cpu().numpy().reshape(v.shape)
+            else:
+                a = np.asarray(float(v), dtype=np.float64)
+            if a.size > DUMP_MAX_ELEMS // world:
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                a = a.reshape(-1)[np.sort(rng.choice(a.size, DUMP_MAX_ELEMS // world, replace=False))]
+                name += "_sample"
+            arrays.append((name, a))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_BUDGET_BYTES // world:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET_BYTES // world))
+    for name, a in arrays:
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return [n for n, _ in arrays]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,6 +407,10 @@ def main():
                     help="video = BASELINE configs[2] (the metric's config, default); image = configs[1] (2-D path); video8 = "
                          "configs[3] (8 pyramid scales, --min-size 48; N > 1: level pipeline, one level per GPU at N = 8); "
                          "baseline = configs[4] (train_video_baselines GeneratorSG, 8 scales; N > 1: stage pipeline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what each stage's last timed step returned (losses, generated / fake "
+                         "volumes, mu, logvar, ...) as DIR/stage<s>_<name>.npy; large arrays as a fixed seeded sample; "
+                         "N > 1: every rank writes its own, prefixed rank<r>_")
     args = ap.parse_args()
     global CONFIG
     CONFIG = args.config
@@ -479,6 +518,8 @@ def main():
     # outside the timed region: the iterations just timed must have produced finite losses (a fast run that trained
     # NaNs - as hipGraph replays once did, DESIGN.md section 4 - is not a measurement)
     runner.check_finite()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner.last, prefix="rank%d_" % rank if world > 1 else "", world=world)
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -97,3 +97,28 @@ def test_roofline_entries_price_executed_flops(conv_kind, wgrad_kind):
     vox = 2 * 13 * 144 * 256
     assert abs(h["achieved"] - (4.0 * vox * 67 + 4 * 3 * 64 * 27) / 0.21e-3 / 1e9) < 1 and 0 < h["frac"] < 1 and 0 < t["frac"] < 1
     assert abs(t["flop_per_byte"] - 2.0 * vox * 64 * 3 * 27 / (4.0 * vox * 67 + 4 * 3 * 64 * 27)) < 0.01
+
+
+def test_dump_outputs_writes_the_last_step_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: one float .npy per returned tensor / scalar, None entries skipped, arrays over the cap written as
+    the same seeded sample on every call (two builds given the same arguments compare element for element)."""
+    import numpy as np
+    import bench
+    big = torch.randn(2, 3, 13, 144, 256)
+    last = {0: {"total_loss": torch.tensor(1.5), "mu": torch.randn(2, 8, 3, 4), "clip_info": torch.tensor([0.5, 2.0]),
+                "generated": None},
+            9: {"errG": -0.25, "fake": big}}
+    names = bench.dump_outputs(str(tmp_path / "a"), last)
+    bench.dump_outputs(str(tmp_path / "b"), last)
+    assert sorted(names) == ["stage0_clip_info", "stage0_mu", "stage0_total_loss", "stage9_errG", "stage9_fake_sample"]
+    mu = np.load(tmp_path / "a" / "stage0_mu.npy")
+    assert mu.dtype == np.float32 and np.array_equal(mu, last[0]["mu"].numpy())
+    errG = np.load(tmp_path / "a" / "stage9_errG.npy")
+    assert errG.dtype == np.float64 and float(errG) == -0.25
+    fa = np.load(tmp_path / "a" / "stage9_fake_sample.npy")
+    assert fa.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(fa, np.load(tmp_path / "b" / "stage9_fake_sample.npy"))
+    assert np.isin(fa, big.numpy().reshape(-1)).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET_BYTES
+    r1 = bench.dump_outputs(str(tmp_path / "r"), {9: {"fake": big}}, prefix="rank1_", world=4)
+    assert r1 == ["rank1_stage9_fake_sample"]
+    assert np.load(tmp_path / "r" / "rank1_stage9_fake_sample.npy").shape == (bench.DUMP_MAX_ELEMS // 4,)

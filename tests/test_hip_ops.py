@@ -186,7 +186,7 @@ def test_conv_winograd_kernel_against_direct_kernel_and_oracle(ops, wino_mode, B
     (1, 8, 40, (2, 1000, 256)),
 ])
 def test_conv_winograd_two_axis_kernel_against_direct_kernel_and_oracle(ops, wino_mode, B, Cin, Cout, sp):
-    """conv_wino2d_kernel (F(2x2, 3x3) over H and W, one workgroup per CU, software-pipelined with hand-counted waits;
+    """conv_wino2r_kernel (F(2x2, 3x3) over H and W, one workgroup per CU, software-pipelined with hand-counted waits;
     forced wherever it can run: 3x3x3, even W, H*W a multiple of 4) against the oracle and the direct kernel: forward,
     backward-data, LeakyReLU + 1-bit mask output, masked epilogues; odd H (half a quad row), W = 2, two tiles per quad
     row, ragged channel counts (sub-chunks past Cin, an odd number of output-channel tiles), several tiles and sub-chunks per
@@ -717,8 +717,11 @@ def test_full_size_conv_family_properties(ops):
     three conv kernels are tied together by size-independent properties instead -
       * locality: any crop of the output equals the oracle's conv of the matching input crop (+1 voxel of context);
       * adjointness: <conv(x, w), dy> = <x, bwd_data(dy, w)> = <w, bwd_weight(dy, x)>  (one number, three kernels);
-      * linearity of the forward kernel in its input."""
+      * linearity of the forward kernel in its input.
+    Both convs of this shape run the two-axis Winograd kernel (kind 2) under the default size rules."""
+    from hp_vae_gan_amd import lib as hplib
     B, C, T, H, W = 2, 64, 13, 144, 256
+    assert hplib.load().hpvg_conv_fwd_kernel_kind(B, C, C, T, H, W, 3) == 2   # forward and backward-data (C -> C)
     g = torch.Generator(device=DEV).manual_seed(5)
     x = torch.randn(B, C, T, H, W, device=DEV, generator=g)
     dy = torch.randn(B, C, T, H, W, device=DEV, generator=g)
@@ -831,7 +834,12 @@ def test_full_size_batchnorm_properties(ops):
 def test_full_size_head_and_tail_convs_by_crops(ops, Cin, Cout):
     """The other layer shapes of the path at the finest level's size (tails 64->3 / 64->1 on the narrow-output kernel,
     head 3->64, decoder head 128->64 at its own largest size): output crops against the oracle, forward and backward-data."""
+    from hp_vae_gan_amd import lib as hplib
     B, T, H, W = (2, 13, 144, 256) if Cin != 128 else (2, 4, 18, 33)
+    # (forward, backward-data) kernel kinds: 0 direct, 1 one-axis Winograd, 3 narrow output
+    kinds = {(64, 3): (3, 0), (3, 64): (0, 3), (64, 1): (3, 0), (128, 64): (1, 1)}[(Cin, Cout)]
+    lib = hplib.load()
+    assert (lib.hpvg_conv_fwd_kernel_kind(B, Cin, Cout, T, H, W, 3), lib.hpvg_conv_fwd_kernel_kind(B, Cout, Cin, T, H, W, 3)) == kinds
     g = torch.Generator(device=DEV).manual_seed(7)
     x = torch.randn(B, Cin, T, H, W, device=DEV, generator=g)
     dy = torch.randn(B, Cout, T, H, W, device=DEV, generator=g)

@@ -1105,6 +1105,20 @@ inline int bn_nsplit(int B, int C, long S) {
   if (want > 64) want = 64;
   return (int)want;
 }
+// the BatchNorm forward / backward launches fold the finalize into the apply kernel (two launches for all groups) up to
+// HPVG_BN_FUSE_MAX elements of the whole batch; above, three launches per group
+inline bool bn_fused(int B, int C, long S) { return (long)B * C * S <= HPVG_BN_FUSE_MAX; }
+// vector width of the per-channel reductions over `groups` groups of B / groups samples that start at x (the narrowest of
+// the groups' row starts)
+inline int bn_vec_width(const void* x, int B, int C, long S, int groups) {
+  const long gsz = (long)(B / groups) * C * S;
+  int vw = 4;
+  for (int g = 0; g < groups; ++g) {
+    const int v = hpvg_vec_width((const char*)x + g * gsz * (long)sizeof(float), S);
+    if (v < vw) vw = v;
+  }
+  return vw;
+}
 
 }  // namespace
 
@@ -1146,7 +1160,7 @@ int hpvg_bn_train_fwd_f32(const float* x, const float* gamma, const float* beta,
   const int gstride = 4 * C;
   const int ns = bn_nsplit(Bg, C, S);
   hipStream_t s = (hipStream_t)stream;
-  if ((long)B * C * S > HPVG_BN_FUSE_MAX) {
+  if (!bn_fused(B, C, S)) {
     // large tensors: tens of thousands of apply workgroups would each repeat the finalize prologue - three launches (per
     // group) win
     for (int g = 0; g < groups; ++g) {
@@ -1167,10 +1181,7 @@ int hpvg_bn_train_fwd_f32(const float* x, const float* gamma, const float* beta,
     }
     return hpvg_launch_status();
   }
-  const long gsz = (long)Bg * C * S;
-  int vw = 4;
-  for (int g = 0; g < groups; ++g) { const int v = hpvg_vec_width(x + g * gsz, S); if (v < vw) vw = v; }
-  switch (vw) {
+  switch (bn_vec_width(x, B, C, S, groups)) {
     case 4: hipLaunchKernelGGL(bn_stats_partial_kernel<4>, dim3(ns, C * groups), dim3(256), 0, s, x, Bg, C, S, ns, (double*)ws); break;
     case 2: hipLaunchKernelGGL(bn_stats_partial_kernel<2>, dim3(ns, C * groups), dim3(256), 0, s, x, Bg, C, S, ns, (double*)ws); break;
     default: hipLaunchKernelGGL(bn_stats_partial_kernel<1>, dim3(ns, C * groups), dim3(256), 0, s, x, Bg, C, S, ns, (double*)ws);
@@ -1258,7 +1269,7 @@ int hpvg_bn_act_bwd_f32(const float* dh, const float* r, const float* mean, cons
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)ws;
   const long gsz = (long)Bg * C * S;
-  if ((long)B * C * S > HPVG_BN_FUSE_MAX) {
+  if (!bn_fused(B, C, S)) {
     float* sums = (float*)((char*)ws + (size_t)C * groups * 64 * 2 * sizeof(double));
     for (int g = 0; g < groups; ++g) {
       const float* dhg = dh + g * gsz;
@@ -1277,11 +1288,8 @@ int hpvg_bn_act_bwd_f32(const float* dh, const float* r, const float* mean, cons
     }
     return hpvg_launch_status();
   }
-  int vw = 4;
-  for (int g = 0; g < groups; ++g) {
-    const int v = hpvg_vec_width(dh + g * gsz, S) < hpvg_vec_width(r + g * gsz, S) ? hpvg_vec_width(dh + g * gsz, S) : hpvg_vec_width(r + g * gsz, S);
-    if (v < vw) vw = v;
-  }
+  int vw = bn_vec_width(dh, B, C, S, groups);
+  if (bn_vec_width(r, B, C, S, groups) < vw) vw = bn_vec_width(r, B, C, S, groups);
   if (vw == 4) hipLaunchKernelGGL(bn_lrelu_bwd_reduce_kernel<4>, dim3(ns, C * groups), dim3(256), 0, s, dh, r, mean, invstd, scale, shift, Bg, C, S, ns, lrelu, part, gstride);
   else if (vw == 2) hipLaunchKernelGGL(bn_lrelu_bwd_reduce_kernel<2>, dim3(ns, C * groups), dim3(256), 0, s, dh, r, mean, invstd, scale, shift, Bg, C, S, ns, lrelu, part, gstride);
   else hipLaunchKernelGGL(bn_lrelu_bwd_reduce_kernel<1>, dim3(ns, C * groups), dim3(256), 0, s, dh, r, mean, invstd, scale, shift, Bg, C, S, ns, lrelu, part, gstride);
@@ -1290,6 +1298,18 @@ int hpvg_bn_act_bwd_f32(const float* dh, const float* r, const float* mean, cons
                      (const double*)part, ns, dgamma, dbeta, accumulate, dr, C, S, (float)(1.0 / ((double)Bg * (double)S)), lrelu, Bg,
                      groups, gstride);
   return hpvg_launch_status();
+}
+
+// host only: the launch plan of hpvg_bn_train_fwd_f32 / hpvg_bn_act_bwd_f32 for tensors whose start is 16-byte aligned:
+// out[0] = 1 when the finalize is folded into the apply kernel (else three launches per group), out[1] = nsplit (partial
+// blocks per channel and group), out[2] = vector width of the reduction kernels
+int hpvg_bn_plan(int B, int C, long S, int groups, int* out3) {
+  if (!out3 || B < 1 || C < 1 || S < 1 || groups < 1 || B % groups) return HPVG_ERR_ARG;
+  const void* aligned = (const void*)(uintptr_t)256;
+  out3[0] = bn_fused(B, C, S) ? 1 : 0;
+  out3[1] = bn_nsplit(B / groups, C, S);
+  out3[2] = bn_vec_width(aligned, B, C, S, groups);
+  return HPVG_OK;
 }
 
 // second-order backward of h = LeakyReLU_opt(BN_train(r)) (see bn_lrelu_bwd2_reduce_kernel): g = dL/d(dr) of the first-order

@@ -59,6 +59,7 @@ _SIGS = {
     "hpvg_affine_act_f32": [P, P, P, P, I, I, I, L, P],
     "hpvg_bn_train_fwd_f32": [P, P, P, P, P, F, F, P, P, P, P, P, I, I, P, Z, I, I, L, P],
     "hpvg_bn_act_bwd_f32": [P, P, P, P, P, P, I, I, P, P, P, I, P, Z, I, I, L, P],
+    "hpvg_bn_plan": [I, I, L, I, P],
     "hpvg_bn_bwd2_ws_bytes": [I],
     "hpvg_bn_act_bwd2_f32": [P, P, P, P, P, P, P, I, P, P, P, I, P, Z, I, I, L, P],
     "hpvg_bn_sums_f32": [P, P, P, Z, I, I, L, P],

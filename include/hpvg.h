@@ -148,6 +148,10 @@ int hpvg_affine_act_f32(const float* x, const float* scale, const float* shift, 
 int hpvg_bn_act_bwd_f32(const float* dh, const float* r, const float* mean, const float* invstd, const float* scale,
                         const float* shift, int lrelu, int groups, float* dr, float* dgamma, float* dbeta, int accumulate, void* ws,
                         size_t ws_bytes, int B, int C, long S, void* stream);
+/* host only: launch plan of the two calls above for 16-byte-aligned tensors: out[0] = 1 when the statistics finalize is
+ * folded into the apply kernel (two launches for all groups; else three per group), out[1] = partial blocks per channel
+ * and group, out[2] = vector width (floats per load) of the reduction kernels */
+int hpvg_bn_plan(int B, int C, long S, int groups, int* out3);
 /* SECOND-order backward of the same block: the WGAN-GP of a critic that contains BatchNorm (WDiscriminatorBaselines,
  * networks_3d.py:184-210; modules/utils.py:14-18) differentiates the first-order backward once more.  g = dL/d(dr);
  * outputs (each nullable): g_dh = dL/d(dh), g_r = dL/d(r), g_gamma = dL/d(gamma) (+= when accumulate).  torch:

@@ -119,8 +119,10 @@ WEIGHT_NAMES = {5: ("o", "i", "kt", "kh", "kw"), 4: ("o", "i", "kh", "kw")}
 
 
 def err_ratio(got, ref, A):
-    """(max_i |got_i - ref_i| / A_i, index of that element); A_i = 0 admits only an exact result, NaN counts as infinite."""
-    got = got.detach().cpu()
+    """(max_i |got_i - ref_i| / A_i, index of that element); A_i = 0 admits only an exact result, NaN counts as infinite.
+    Computed on the device of ref (float64 references may live on the GPU)."""
+    got = got.detach().to(ref.device)
+    A = A.to(ref.device)
     assert tuple(got.shape) == tuple(ref.shape) == tuple(A.shape), (tuple(got.shape), tuple(ref.shape), tuple(A.shape))
     rows = got.shape[0] if got.dim() > 1 else 1
     g2, r2, a2 = (t.reshape(rows, -1) for t in (got, ref, A))
@@ -147,7 +149,7 @@ def check(got, ref, A, what, tau=TAU, names=None):
     if not worst <= tau:
         names = names or _NAMES.get(got.dim(), tuple("d%d" % k for k in range(got.dim())))
         at = ", ".join("%s=%d" % (n, v) for n, v in zip(names, idx))
-        g = float(got.detach().cpu()[idx])
+        g = float(got.detach()[idx])
         raise AssertionError("%s: |got - ref| / A = %.3e > tau %.1e at (%s): got %.9g, ref %.9g, A %.6g" % (
             what, worst, tau, at, g, float(ref[idx]), float(A[idx])))
     assert_close(got, ref, RTOL, what)

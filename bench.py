@@ -7,6 +7,10 @@ weights are random-init (default torch init), as SURVEY.md 8(d) prescribes.
 
 One "step" = one train iteration (train_video.py:111-202) at EVERY pyramid stage 0..9, inputs resident in HBM.
 value = stage-iterations per second over the timed region (10*K / seconds); per-stage it/s are reported beside it.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; its roofline costs nothing
+extra (the HIP events that feed it are recorded inside the timed steps).  --full adds what the headline value does not
+need: the CPU oracle leg (cpu_baseline, about three minutes on the host).
 """
 import argparse
 import json
@@ -395,14 +399,18 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--stages", type=str, default="all", help="pyramid stages in a step, e.g. 0-9 or 9 (default: every stage of the config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline value does not need: the CPU oracle leg (cpu_baseline) of the "
+                         "video config on one GPU; a plain run reports cpu_baseline null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU leg")
     ap.add_argument("--cpu-stages", type=str, default="all",
-                    help="stages the CPU leg times (default: every stage of the step; 1 warm-up + 20 timed iterations at stages "
-                         "0-3, 3 at 4-7, 1 at 8-9; nothing is extrapolated - a stage left out here is reported as not run)")
+                    help="with --full: stages the CPU leg times (default: every stage of the step; 1 warm-up + 20 timed "
+                         "iterations at stages 0-3, 3 at 4-7, 1 at 8-9; nothing is extrapolated - a stage left out here is "
+                         "reported as not run)")
     ap.add_argument("--graph-stages", type=str, default="0-8",
                     help="stages whose iteration is captured once and replayed as a hipGraph (single-GPU path; the stage "
                          "holding the roofline kernel always stays eager so that its launches can be bracketed by events); "
-                         "'none' = every stage eager.  Measured r01: +52 % at stage 0, +8 % at stage 3, +2 % at stage 7")
+                         "'none' = every stage eager.  Measured r01: +52 %% at stage 0, +8 %% at stage 3, +2 %% at stage 7")
     ap.add_argument("--config", choices=["video", "image", "video8", "baseline"], default="video",
                     help="video = BASELINE configs[2] (the metric's config, default); image = configs[1] (2-D path); video8 = "
                          "configs[3] (8 pyramid scales, --min-size 48; N > 1: level pipeline, one level per GPU at N = 8); "
@@ -542,7 +550,7 @@ def main():
         per_stage = {str(s): 1000.0 * args.steps / ev[0].elapsed_time(ev[1]) for s, ev in stage_ev.items()}
         roof = roofline_entries(by_shape, KT, hplib.load())
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and CONFIG == "video":
+        if args.full and not args.no_cpu_baseline and world == 1 and CONFIG == "video":
             cs = stages if args.cpu_stages == "all" else [s for s in parse(args.cpu_stages) if s in stages]
             if cs:
                 threads = min(os.cpu_count() or 1, 16)

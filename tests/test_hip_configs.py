@@ -64,6 +64,15 @@ def test_ten_scale_configs_run_on_one_gpu(config):
         assert fams["conv_fwd"]["traffic"] is not None and fams["weight_gradient"]["traffic"] is not None
 
 
+def test_cpu_leg_only_with_full():
+    """a plain run measures the steps alone (cpu_baseline null); --full adds the CPU oracle leg over the stages asked for"""
+    plain = _bench(["--stages", "0-1", "--steps", "1", "--warmup", "1"])
+    assert plain["cpu_baseline"] is None and plain["value"] > 0
+    full = _bench(["--full", "--stages", "0-1", "--cpu-stages", "0", "--steps", "1", "--warmup", "1"])
+    cpu = full["cpu_baseline"]
+    assert cpu["kind"] == "port" and list(cpu["per_stage_it_s"]) == ["0"] and cpu["stages_not_run"] == [1] and cpu["value"] > 0
+
+
 @pytest.mark.parametrize("config", ["video8", "baseline"])
 def test_eight_scale_configs_run_on_one_gpu(config):
     line = _bench(["--config", config, "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/final_r03}
 mkdir -p $O
-python3 bench.py > $O/bench_video.log 2>&1; echo video >> $O/progress
+python3 bench.py --full > $O/bench_video.log 2>&1; echo video >> $O/progress
 python3 bench.py --config image --no-cpu-baseline > $O/bench_image.log 2>&1; echo image >> $O/progress
 python3 bench.py --config video8 --no-cpu-baseline > $O/bench_video8.log 2>&1; echo video8 >> $O/progress
 python3 bench.py --config baseline --no-cpu-baseline > $O/bench_baseline.log 2>&1; echo baseline >> $O/progress

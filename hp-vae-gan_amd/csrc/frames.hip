@@ -12,6 +12,10 @@
 // pass in 32-bit integers and the vertical pass ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2 - HIP output ==
 // oracle output bit for bit (tests/test_frames.py, torch.equal).  Without `quantize`: the exact bilinear value in fp32.
 // cv2 is not installed in the build image: PARITY UNPINNED against the reference's decoder/resizer.
+//
+// The inverse direction, for the programs' outputs: hpvg_video_to_u8_f32 turns a generated fp32 [B][C][T][H][W] volume into
+// uint8 [B][T][H][W][C] frames the way utils/saver.py:8-19 (write_video) does, and hpvg_scalar_log_append_f32 appends one
+// row of per-iteration loss scalars to a device table, so that a replayed hipGraph logs without a host synchronisation.
 #include "hpvg_common.h"
 #include "hpvg.h"
 
@@ -85,9 +89,84 @@ __global__ __launch_bounds__(256) void frames_resize_norm_kernel(const unsigned 
   }
 }
 
+// np.uint8((x + 1) * 127.5) of write_video, restated so that it does not depend on contraction or reassociation: the add and
+// the multiply are rounded separately in fp32, the conversion truncates (a value a fraction of a ulp under a level goes down
+// one level, as numpy's does).  Out-of-range values clamp to [0, 255] and NaN becomes 0 (numpy's cast leaves both undefined).
+#pragma clang fp contract(off)
+__device__ __forceinline__ unsigned char video_level(float x) {
+  float v = __fmul_rn(__fadd_rn(x, 1.0f), 127.5f);
+  if (!(v >= 0.0f)) v = 0.0f;  // negative and NaN
+  if (v > 255.0f) v = 255.0f;
+  return (unsigned char)(int)truncf(v);
+}
+
+// One workgroup per output row (b, t, h) at a time: the C input rows are read along W (coalesced fp32 loads), the row's
+// W*C interleaved bytes are assembled in LDS and stored contiguously.  VIDEO_CHUNK pixels per pass.
+constexpr int VIDEO_CHUNK = 256;
+
+template <int C>
+__global__ __launch_bounds__(256) void video_to_u8_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, int T, int H,
+                                                          int W, long rows) {
+  __shared__ unsigned char row[VIDEO_CHUNK * C];
+  const long plane = (long)H * W;
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int h = (int)(r % H);
+    const long bt = r / H;
+    const int t = (int)(bt % T);
+    const long b = bt / T;
+    const float* src = x + ((b * C) * T + t) * plane + (long)h * W;  // channel c at src + c * T * plane
+    unsigned char* dst = out + r * (long)W * C;
+    for (int w0 = 0; w0 < W; w0 += VIDEO_CHUNK) {
+      const int n = W - w0 < VIDEO_CHUNK ? W - w0 : VIDEO_CHUNK;
+      const int w = threadIdx.x;
+      if (w < n) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) row[w * C + c] = video_level(src[(long)c * T * plane + w0 + w]);
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < n * C; i += 256) dst[(long)w0 * C + i] = row[i];
+      __syncthreads();
+    }
+  }
+}
+
+// One wave: lane k < K copies *src.p[k] into row cursor % capacity; lane 0 then advances the cursor with an ordinary global
+// store.  The cursor is read and written in device memory, so a replayed graph appends a fresh row with unchanged arguments.
+__global__ __launch_bounds__(64) void scalar_log_append_kernel(hpvg_scalar_ptrs src, int K, float* __restrict__ table, int capacity,
+                                                               int* cursor) {
+  const int lane = threadIdx.x;
+  const int c = __builtin_nontemporal_load(cursor);
+  const long base = (long)((unsigned)c % (unsigned)capacity) * K;
+#pragma unroll
+  for (int k = 0; k < HPVG_LOG_MAX_K; ++k)
+    if (k < K && lane == k) table[base + k] = *src.p[k];
+  if (lane == 0) cursor[0] = c + 1;
+}
+
 }  // namespace
 
 extern "C" {
+
+// x: [B][C][T][H][W] fp32 (device), out: [B][T][H][W][C] uint8 (device).  C = 1 or 3.
+int hpvg_video_to_u8_f32(const float* x, unsigned char* out, int B, int C, int T, int H, int W, void* stream) {
+  if (!x || !out || B < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
+  if (C != 1 && C != 3) return HPVG_ERR_UNSUPPORTED;
+  const long rows = (long)B * T * H;
+  const unsigned nb = (unsigned)(rows < 8192 ? rows : 8192);
+  if (C == 3)
+    hipLaunchKernelGGL(video_to_u8_kernel<3>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, T, H, W, rows);
+  else
+    hipLaunchKernelGGL(video_to_u8_kernel<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, out, T, H, W, rows);
+  return hpvg_launch_status();
+}
+
+int hpvg_scalar_log_append_f32(hpvg_scalar_ptrs src, int K, float* table, int capacity, int* cursor, void* stream) {
+  if (!table || !cursor || K < 1 || K > HPVG_LOG_MAX_K || capacity < 1) return HPVG_ERR_ARG;
+  for (int k = 0; k < K; ++k)
+    if (!src.p[k]) return HPVG_ERR_ARG;
+  hipLaunchKernelGGL(scalar_log_append_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, src, K, table, capacity, cursor);
+  return hpvg_launch_status();
+}
 
 // src: N frames [N][H][W][3] uint8 RGB (device).  dst: [3][count][h][w] fp32 = normalize(resize(frame[first + k*step])).
 int hpvg_frames_resize_norm_u8_f32(const unsigned char* src, float* dst, int N, int H, int W, int first, int step, int count, int h,

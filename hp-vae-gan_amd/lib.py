@@ -25,6 +25,14 @@ F = ctypes.c_float
 D = ctypes.c_double
 Z = ctypes.c_size_t
 
+LOG_MAX_K = 16  # HPVG_LOG_MAX_K
+
+
+class ScalarPtrs(ctypes.Structure):
+    """hpvg_scalar_ptrs: the K <= LOG_MAX_K device scalar pointers of one loss-log row, passed by value."""
+    _fields_ = [("p", ctypes.c_void_p * LOG_MAX_K)]
+
+
 # name -> argtypes (restype int unless listed in _SIZE_FUNCS)
 _SIGS = {
     "hpvg_conv_wpack_floats": [I, I, I],
@@ -89,6 +97,8 @@ _SIGS = {
     "hpvg_uniform_f32": [P, L, ctypes.c_ulonglong, ctypes.c_uint, P, P],
     "hpvg_upsample_linear_ac_noise_f32": [P, P, P, F, L, I, I, I, I, I, I, I, I, ctypes.c_ulonglong, ctypes.c_uint, P, P],
     "hpvg_frames_resize_norm_u8_f32": [P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "hpvg_video_to_u8_f32": [P, P, I, I, I, I, I, P],
+    "hpvg_scalar_log_append_f32": [ScalarPtrs, I, P, I, P, P],
     "hpvg_upsample_linear_ac_bwd_f32": [P, P, P, L, I, I, I, I, I, I, P],
     "hpvg_sn_power_iter_f32": [P, P, P, P, P, P, I, I, I, F, P, Z, P],
     "hpvg_div_scalar_f32": [P, P, P, L, P],

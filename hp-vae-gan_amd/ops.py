@@ -1275,3 +1275,68 @@ def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
 
 def counter_inc_(counter):
     call("hpvg_counter_inc_i32", ptr(counter), stream())
+
+
+# ------------------------------------------------------------------------------------------ the programs' outputs
+def video_to_u8(x):
+    """fp32 [B][C][T][H][W] (or an image batch [B][C][H][W]) -> uint8 [B][T][H][W][C] (images: [B][H][W][C]) with write_video's
+    np.uint8((x + 1) * 127.5) (utils/saver.py:8-19): truncation, clamped to [0, 255], NaN -> 0 (hpvg_video_to_u8_f32)."""
+    x = _c(x)
+    if x.dtype != torch.float32:
+        raise RuntimeError("video_to_u8: fp32 input expected, got %s" % x.dtype)
+    if x.dim() == 4:
+        B, C, H, W = x.shape
+        T = 1
+        out = torch.empty(B, H, W, C, dtype=torch.uint8, device=x.device)
+    elif x.dim() == 5:
+        B, C, T, H, W = x.shape
+        out = torch.empty(B, T, H, W, C, dtype=torch.uint8, device=x.device)
+    else:
+        raise RuntimeError("video_to_u8: expected [B,C,T,H,W] or [B,C,H,W], got %s" % (tuple(x.shape),))
+    if out.numel():
+        call("hpvg_video_to_u8_f32", ptr(x), ptr(out), B, C, T, H, W, stream())
+    return out
+
+
+def scalar_log_append_(scalars, table, cursor):
+    """Append (*scalars[0], ..., *scalars[K-1]) to row cursor % capacity of `table` [capacity][K] and advance the device int
+    `cursor` (hpvg_scalar_log_append_f32: one single-wave kernel; captured into a graph it appends on every replay).
+    `scalars`: fp32 device tensors of one element each, or (tensor, element index) pairs."""
+    from .lib import LOG_MAX_K, ScalarPtrs
+    K = len(scalars)
+    capacity, k_tab = table.shape
+    if not 1 <= K <= LOG_MAX_K or k_tab != K:
+        raise RuntimeError("scalar_log_append_: %d scalars for a table of %d columns (at most %d)" % (K, k_tab, LOG_MAX_K))
+    src = ScalarPtrs()
+    for k, s in enumerate(scalars):
+        t, i = s if isinstance(s, tuple) else (s, 0)
+        if t.dtype != torch.float32 or not t.is_cuda or not 0 <= i < t.numel():
+            raise RuntimeError("scalar_log_append_: column %d is not an fp32 device scalar" % k)
+        src.p[k] = t.data_ptr() + 4 * i
+    call("hpvg_scalar_log_append_f32", src, K, ptr(table), int(capacity), ptr(cursor), stream())
+
+
+NOISE_STREAM_BASE = 1 << 31
+
+
+class noise_stream:
+    """Draws made inside `with ops.noise_stream(device):` use call indices from NOISE_STREAM_BASE (top bit set) up, so their
+    Philox keys (seed, device iteration, call index) never equal a train iteration's, whose call indices count from 0.  On
+    exit the host call index is put back.  torch's CPU / CUDA generators and python's `random` are not touched: previews
+    and samples drawn between train iterations leave the data order, the CPU alpha draws and the flips where they were."""
+
+    def __init__(self, device=None, base=NOISE_STREAM_BASE):
+        if not base & NOISE_STREAM_BASE:
+            raise ValueError("noise_stream: the base call index must have its top bit set")
+        self.device = torch.device(device if device is not None else "cuda")
+        self.base = base
+
+    def __enter__(self):
+        self._st = _rng(self.device)
+        self._saved = self._st.call
+        self._st.call = self.base
+        return self
+
+    def __exit__(self, *exc):
+        self._st.call = self._saved
+        return False

@@ -1,0 +1,469 @@
+"""Shared code of the three programs: `python -m hp_vae_gan_amd.train_video`, `.train_image` and `.generate`.
+
+The trainers follow the reference's programs (train_video.py:265-417, train_image.py:279-440): the same flags, the same
+setup (noise_amp_init / scale_factor_init, adjust_scales2image, manualSeed drawn when absent and logged, then random.seed
+and torch.manual_seed), DataLoader(shuffle=True, drop_last=True) over a dataset that serves device tensors (so
+num_workers=0), and per stage: dataset.generate_frames, the discriminator with its warm-start rule (train_video.py:44-52:
+the resume directory on a resumed scale, otherwise the experiment directory), train.train, checkpoint.save_stage.
+
+Run directory: <run-dir>/<clip>/<checkname>/experiment_<n>/ with eval/, numbered as utils/saver.py:23-37 does (one more than
+the highest existing number; the reference takes the last of a lexical sort, which only differs from ten experiments on).
+<clip> is the input's file name without its extension, or a frame directory's basename.  Beside the checkpoints it holds
+opt.json (the parsed flags plus the derived settings `generate` needs; settings only), logbook.txt (every console line),
+scalars.jsonl and, with --visualize, previews/.
+
+Scalars: the reference calls .item() on every loss of every iteration (train_video.py:210-222).  Here each iteration
+appends its scalars to a device loss log (telemetry.LossLog, captured into the replayed hipGraph) which is drained every
+--print-interval iterations and at the end of each stage into scalars.jsonl, one {"tag", "step", "value"} line per value,
+under the reference's tags (`Video/Scale {s}/...`, also for images, as train_image.py:227-237 has it) plus
+gradient_penalty, total_loss and grad_norm.
+
+Previews (--visualize) at iteration % print_interval == 0, as train_video.py:225-241: real, generated and generated_vae
+of that iteration, and 3 x batch_size random draws ("Fake var", "Fake VAE var") made under no_grad with the generator in
+train mode (BatchNorm uses batch statistics and updates its running buffers, as in the reference).  Their noise comes from
+ops.noise_stream, so it never shares a key with a training draw and no torch or python generator moves: the training
+trajectory (weights, optimizer state, losses) is the same with and without previews.  Frames go through
+hpvg_video_to_u8_f32 (write_video's conversion) into animated GIFs (video) or PNGs (images).
+
+Resume (--netG <experiment>/netG.pth) follows train_video.py:399-417: the generator grows to the saved scale and loads its
+weights and Noise_Amps, and the loop trains the saved scale AGAIN.  Its iteration 0 appends a fresh noise amplitude
+(train_video.py:131-145), so Noise_Amps ends one entry longer than the number of scales - the reference's quirk, kept like
+the others.  The optimizer state is not restored (neither does the reference).
+
+Not built: mp4 decoding / encoding (cv2), tensorboard event files and neptune (--tag is only recorded), a CPU path
+(--no-cuda is refused), multi-GPU launch."""
+import argparse
+import glob
+import json
+import math
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+from . import checkpoint, datasets, ops, telemetry
+from . import train as hp_train
+from . import utils as hp_utils
+from .modules import networks_2d, networks_3d
+
+# column of the loss log -> the reference's scalar tag (train_video.py:210-222) or a tag of its own
+TAGS = {"rec_vae_loss": "Rec VAE", "kl_loss": "KLD", "rec_loss": "rec loss", "errG": "errG", "errD_real": "errD_real",
+        "errD_fake": "errD_fake", "gradient_penalty": "gradient_penalty", "total_loss": "total_loss", "grad_norm": "grad_norm"}
+
+
+# ------------------------------------------------------------------------------------------------------------------- flags
+def build_parser(kind):
+    """The reference's parser of train_video.py (kind 'video') or train_image.py ('image'): same names, types, defaults and
+    `required`; plus --run-dir and --no-hip-graph."""
+    video = kind == "video"
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.train_" + kind,
+                                description="Train HP-VAE-GAN on one %s, stage by stage, on an MI355X." % kind)
+    a = p.add_argument
+    # load, input, save
+    a('--netG', default='', help='netG.pth of an experiment to resume from (its scale is trained again)')
+    a('--netD', default='', help='accepted, unused (as in the reference)')
+    a('--manualSeed', type=int, help='seed of python random and torch (random when absent)')
+    # networks
+    a('--nc-im', type=int, default=3, help='image channels')
+    a('--nfc', type=int, default=64, help='base channel count')
+    a('--latent-dim', type=int, default=128, help='VAE latent channels')
+    a('--vae-levels', type=int, default=3, help='number of VAE levels')
+    a('--enc-blocks', type=int, default=2, help='encoder blocks')
+    a('--ker-size', type=int, default=3, help='kernel size')
+    a('--num-layer', type=int, default=5, help='layers per block')
+    a('--stride', default=1, help='stride')
+    a('--padd-size', type=int, default=1, help='padding')
+    a('--generator', type=str, default='GeneratorHPVAEGAN', help='generator class')
+    a('--discriminator', type=str, default='WDiscriminator3D' if video else 'WDiscriminator2D', help='discriminator class')
+    # pyramid
+    a('--scale-factor', type=float, default=0.75, help='pyramid scale factor')
+    a('--noise_amp', type=float, default=0.1, help='additive noise weight')
+    a('--min-size', type=int, default=32, help='size of the coarsest scale')
+    a('--max-size', type=int, default=256, help='size of the finest scale')
+    # optimisation
+    a('--niter', type=int, default=50000, help='iterations per scale')
+    a('--lr-g', type=float, default=0.0005, help='generator learning rate')
+    a('--lr-d', type=float, default=0.0005, help='discriminator learning rate')
+    a('--beta1', type=float, default=0.5, help='Adam beta1')
+    a('--lambda-grad', type=float, default=0.1, help='gradient penalty weight')
+    a('--rec-weight', type=float, default=10., help='reconstruction loss weight')
+    a('--kl-weight', type=float, default=1., help='KL weight')
+    a('--disc-loss-weight', type=float, default=1.0, help='adversarial loss weight')
+    a('--lr-scale', type=float, default=0.2, help='learning-rate scaling of the lower trained levels')
+    a('--train-depth', type=int, default=1, help='levels trained at once')
+    a('--grad-clip', type=float, default=5, help='gradient clip norm')
+    a('--const-amp', action='store_true', default=False, help='constant noise amplitude')
+    a('--train-all', action='store_true', default=False, help='train all levels w.r.t. train-depth')
+    # data
+    if video:
+        a('--video-path', required=True, help='frame directory or .npy [N,H,W,3] uint8 (no mp4 decoder in this build)')
+        a('--start-frame', default=0, type=int, help='first frame')
+        a('--max-frames', default=1000, type=int, help='frames to keep')
+    else:
+        a('--image-path', required=True, help='image file, directory of images or .npy [N,H,W,3] uint8')
+    a('--hflip', action='store_true', default=False, help='random horizontal flips')
+    a('--img-size', type=int, default=256)
+    if video:
+        a('--sampling-rates', type=int, nargs='+', default=[4, 3, 2, 1], help='temporal sampling rates')
+    a('--stop-scale-time', type=int, default=-1)
+    a('--data-rep', type=int, default=1 if video else 1000, help='dataset repetitions')
+    # main
+    a('--checkname', type=str, default='DEBUG', help='run name')
+    a('--mode', default='train', help='task')
+    a('--batch-size', type=int, default=2, help='batch size')
+    a('--print-interval', type=int, default=100, help='iterations between log drains (and previews)')
+    a('--visualize', action='store_true', default=False, help='write previews (GIF / PNG) under previews/')
+    a('--no-cuda', action='store_true', default=False, help='refused: there is no CPU path')
+    if not video:
+        a('--tag', type=str, default='', help='recorded in opt.json only (the reference tags a neptune run)')
+    # this project's own
+    a('--run-dir', default='run', help='root of the run directories')
+    a('--no-hip-graph', action='store_true', default=False, help='stay eager (no hipGraph replay)')
+    p.set_defaults(hflip=False)
+    return p
+
+
+# ---------------------------------------------------------------------------------------------------------- run directory
+def clip_name(path):
+    """<clip> of the run directory: the file name without its extension (utils/saver.py:26), a directory's basename."""
+    path = os.path.normpath(path)
+    base = os.path.basename(path)
+    if os.path.isdir(path) or '.' not in base:
+        return base
+    return '.'.join(base.split('.')[:-1])
+
+
+def experiment_dir(run_dir, clip, checkname):
+    """Create and return <run_dir>/<clip>/<checkname>/experiment_<n> (and its eval/): n = 1 + the highest existing number."""
+    directory = os.path.join(run_dir, clip, checkname)
+    nums = []
+    for d in glob.glob(os.path.join(directory, 'experiment_*')):
+        tail = d.rsplit('_', 1)[-1]
+        if tail.isdigit():
+            nums.append(int(tail))
+    exp = os.path.join(directory, 'experiment_{}'.format(max(nums) + 1 if nums else 0))
+    os.makedirs(os.path.join(exp, 'eval'), exist_ok=True)
+    return exp
+
+
+def resume_info(netG_path):
+    """(scale, resume_dir) of a --netG checkpoint (train_video.py:399-403)."""
+    if not os.path.isfile(netG_path):
+        raise RuntimeError("=> no <G> checkpoint found at '{}'".format(netG_path))
+    ckpt = torch.load(netG_path, map_location='cpu', weights_only=True)
+    return int(ckpt['scale']), os.path.dirname(netG_path)
+
+
+def stage_plan(scale_idx, resumed_idx, stop_scale):
+    """[(scale, grow the generator first?)] of the stage loop (train_video.py:413-417): a fresh run grows at every scale
+    above 0; a resumed run starts at the saved scale without growing (the checkpoint already holds that level)."""
+    return [(s, s > 0 and s != resumed_idx) for s in range(scale_idx, stop_scale + 1)]
+
+
+def json_settings(opt):
+    """The JSON-representable settings of `opt` (no tensors, devices, datasets or code)."""
+    out = {}
+    for k, v in sorted(vars(opt).items()):
+        if isinstance(v, (bool, int, float, str)) or v is None:
+            out[k] = v
+        elif isinstance(v, (list, tuple)) and all(isinstance(e, (bool, int, float, str)) for e in v):
+            out[k] = list(v)
+    return out
+
+
+class Logbook:
+    """print() to the console and to <experiment>/logbook.txt."""
+
+    def __init__(self, path):
+        self.f = open(path, 'a')
+
+    def __call__(self, msg):
+        print(msg, flush=True)
+        self.f.write(msg + '\n')
+        self.f.flush()
+
+    def close(self):
+        self.f.close()
+
+
+# --------------------------------------------------------------------------------------------------------- frames on disk
+def write_frames(u8, path, fps):
+    """u8: [T][H][W][C] or [H][W][C] uint8 -> an animated GIF (video) or a PNG (image)."""
+    from PIL import Image
+    if u8.shape[-1] == 1:
+        u8 = u8[..., 0]
+    if path.endswith('.gif'):
+        frames = [Image.fromarray(f) for f in u8]
+        frames[0].save(path, save_all=True, append_images=frames[1:], duration=max(1, int(round(1000.0 / fps))), loop=0)
+    else:
+        Image.fromarray(u8).save(path)
+
+
+# ------------------------------------------------------------------------------------------------------------ training
+def _networks(opt):
+    return networks_3d if opt.dims == 3 else networks_2d
+
+
+def _stage_data(loader, holder):
+    """Iterate the DataLoader and remember the batch at hand (the previews show `real`)."""
+    for item in loader:
+        holder[0] = item
+        yield item
+
+
+class _Stage:
+    """Callback of train.train for one stage: drains the loss log into scalars.jsonl, prints progress, writes previews."""
+
+    def __init__(self, prog, trainer_log, holder):
+        self.prog, self.log, self.holder = prog, trainer_log, holder
+
+    def __call__(self, trainer, out):
+        opt = self.prog.opt
+        i = trainer.iteration - 1
+        if opt.visualize and i % opt.print_interval == 0:
+            self.prog.preview(trainer, out, self.holder[0], i)
+        if trainer.iteration % opt.print_interval == 0:
+            self.prog.drain(self.log)
+
+
+class Program:
+    """One training run of train_video / train_image (see the module docstring)."""
+
+    def __init__(self, kind, argv=None):
+        self.kind = kind
+        opt = build_parser(kind).parse_args(argv)
+        if opt.no_cuda:
+            raise SystemExit("--no-cuda: hp-vae-gan_amd has no CPU path; every op runs on an MI355X")
+        self.path = opt.video_path if kind == 'video' else opt.image_path
+        if self.path.lower().endswith('.mp4') or not os.path.exists(self.path):
+            datasets.load_frames(self.path)   # the data front-end's own error (no decoder / missing file)
+        if not torch.cuda.is_available():
+            raise SystemExit("hp-vae-gan_amd: no GPU visible; every op runs on an MI355X")
+        assert opt.vae_levels > 0
+        assert opt.disc_loss_weight > 0
+        if kind == 'image' and opt.data_rep < opt.batch_size:
+            opt.data_rep = opt.batch_size
+        opt.dims = 3 if kind == 'video' else 2
+        opt.hip_graph = not opt.no_hip_graph
+        self.exp_dir = experiment_dir(opt.run_dir, clip_name(self.path), opt.checkname)
+        opt.experiment_dir = self.exp_dir
+        self.log = Logbook(os.path.join(self.exp_dir, 'logbook.txt'))
+        self.scalars = open(os.path.join(self.exp_dir, 'scalars.jsonl'), 'a')
+        opt.device = torch.device('cuda', torch.cuda.current_device())
+        opt.noise_amp_init = opt.noise_amp
+        opt.scale_factor_init = opt.scale_factor
+        hp_utils.adjust_scales2image(opt.img_size, opt)
+        if opt.manualSeed is None:
+            opt.manualSeed = random.randint(1, 10000)
+        self.log("Random Seed: {}".format(opt.manualSeed))
+        random.seed(opt.manualSeed)
+        torch.manual_seed(opt.manualSeed)
+        opt.scale_idx = 0
+        opt.nfc_prev = 0
+        opt.Noise_Amps = []
+        if kind == 'video':
+            self.dataset = datasets.SingleVideoDataset(opt)
+        else:
+            self.dataset = datasets.SingleImageDataset(opt)
+        self.loader = torch.utils.data.DataLoader(self.dataset, shuffle=True, drop_last=True, batch_size=opt.batch_size,
+                                                  num_workers=0)
+        if opt.stop_scale_time == -1:
+            opt.stop_scale_time = opt.stop_scale
+        self.opt = opt
+        with open(os.path.join(self.exp_dir, 'opt.json'), 'w') as f:
+            json.dump(json_settings(opt), f, indent=1, sort_keys=True)
+        for k, v in json_settings(opt).items():
+            self.log('{}: {}'.format(k, v))
+        self.log("Experiment: {}".format(self.exp_dir))
+        self.netG = getattr(_networks(opt), opt.generator)(opt).to(opt.device)
+        if opt.netG != '':
+            opt.scale_idx, opt.resume_dir = resume_info(opt.netG)
+            opt.resumed_idx = opt.scale_idx
+            _, opt.Noise_Amps = checkpoint.resume_generator(self.netG, opt.resume_dir)
+            self.netG.to(opt.device)
+            self.log("Resumed scale {} from {} (Noise_Amps {})".format(opt.scale_idx, opt.resume_dir, opt.Noise_Amps))
+        else:
+            opt.resumed_idx = -1
+        self.trainers = []
+        self.logs = []
+
+    # ---- one stage
+    def make_discriminator(self):
+        opt = self.opt
+        if not opt.vae_levels < opt.scale_idx + 1:
+            return None
+        netD = getattr(_networks(opt), opt.discriminator)(opt).to(opt.device)
+        if opt.netG != '' and opt.resumed_idx == opt.scale_idx:
+            checkpoint.warm_start_discriminator(netD, opt.resume_dir, opt.scale_idx)
+        elif opt.vae_levels < opt.scale_idx:
+            checkpoint.warm_start_discriminator(netD, self.exp_dir, opt.scale_idx)
+        return netD
+
+    def train_stage(self):
+        opt = self.opt
+        if opt.dims == 3:
+            opt.fps, opt.td, opt.fps_index = hp_utils.get_fps_td_by_index(opt.scale_idx, opt)
+            self.log("Scale {}: FPS {}, time depth {}, sampling rate {}".format(
+                opt.scale_idx, opt.fps, opt.td, opt.sampling_rates[opt.fps_index]))
+            self.dataset.generate_frames(opt.scale_idx)
+        netD = self.make_discriminator()
+        is_gan = netD is not None
+        log = telemetry.LossLog(hp_train.loss_log_columns(is_gan), capacity=max(64, 2 * opt.print_interval),
+                                device=opt.device)
+        holder = [None]
+        trainer = hp_train.train(opt, self.netG, _Loop(self.loader, holder), netD=netD, loss_log=log,
+                                 callback=_Stage(self, log, holder))
+        if trainer.iteration % opt.print_interval != 0:
+            self.drain(log)
+        checkpoint.save_stage(self.exp_dir, opt, trainer)
+        self.trainers.append(trainer)
+        self.logs.append(log)
+        return trainer
+
+    def run(self):
+        opt = self.opt
+        for scale, grow in stage_plan(opt.scale_idx, opt.resumed_idx, opt.stop_scale):
+            opt.scale_idx = scale
+            if grow:
+                self.netG.init_next_stage()
+                self.netG.to(opt.device)
+            self.train_stage()
+        opt.scale_idx = opt.stop_scale + 1
+        torch.cuda.synchronize()
+        self.log("Done: {}".format(self.exp_dir))
+        self.scalars.close()
+        self.log.close()
+        return self
+
+    # ---- scalars
+    def drain(self, log):
+        opt = self.opt
+        idx, rows, lost = log.drain()
+        if lost:
+            self.log("Scale {}: the loss log lost {} rows before this drain".format(opt.scale_idx, lost))
+        prefix = 'Video/Scale {}/'.format(opt.scale_idx)
+        for step, row in zip(idx.tolist(), rows):
+            lines = [{"tag": prefix + "noise_amp", "step": step, "value": float(opt.noise_amp)}]
+            lines += [{"tag": prefix + TAGS[c], "step": step, "value": float(v)} for c, v in zip(log.columns, row)]
+            for ln in lines:
+                self.scalars.write(json.dumps(ln) + '\n')
+        self.scalars.flush()
+        if len(idx):
+            last = ', '.join('{} {:.5g}'.format(TAGS[c], float(v)) for c, v in zip(log.columns, rows[-1]))
+            self.log('Scale [{}/{}], Iteration [{}/{}]: noise_amp {:.5g}, {}'.format(
+                opt.scale_idx + 1, opt.stop_scale + 1, int(idx[-1]) + 1, opt.niter, float(opt.noise_amp), last))
+
+    # ---- previews
+    def sample(self, count=3):
+        """`count` rand draws of batch_size from the current generator (train mode, no_grad, ops.noise_stream):
+        (fake, fake_vae), each [count * batch_size, C, ...]."""
+        opt, netG = self.opt, self.netG
+        fakes, vaes = [], []
+        with torch.no_grad(), ops.noise_stream(opt.device):
+            for _ in range(count):
+                noise_init = hp_utils.generate_noise(size=opt.Z_init_size, device=opt.device)
+                fake, fake_vae = netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
+                fakes.append(fake)
+                vaes.append(fake_vae)
+        return torch.cat(fakes, 0), torch.cat(vaes, 0)
+
+    def preview(self, trainer, out, batch, iteration):
+        opt = self.opt
+        real = batch[0] if isinstance(batch, (list, tuple)) else batch
+        fake_var, fake_vae_var = self.sample()
+        d = os.path.join(self.exp_dir, 'previews')
+        os.makedirs(d, exist_ok=True)
+        ext = '.gif' if opt.dims == 3 else '.png'
+        fps = getattr(opt, 'fps', 1)
+        for name, x in (('real', real), ('generated', out['generated']), ('generated_vae', out['generated_vae']),
+                        ('fake_var', fake_var), ('fake_vae_var', fake_vae_var)):
+            u8 = ops.video_to_u8(x.float()).cpu().numpy()
+            for b in range(u8.shape[0]):
+                write_frames(u8[b], os.path.join(d, 'scale{}_iter{:06d}_{}_{}{}'.format(opt.scale_idx, iteration, name, b, ext)),
+                             fps)
+
+
+class _Loop:
+    """Re-iterable view of the DataLoader that remembers the batch at hand (train.train restarts an exhausted iterator)."""
+
+    def __init__(self, loader, holder):
+        self.loader, self.holder = loader, holder
+
+    def __iter__(self):
+        return _stage_data(self.loader, self.holder)
+
+
+def train_main(kind, argv=None):
+    Program(kind, argv).run()
+    return 0
+
+
+# ------------------------------------------------------------------------------------------------------------ generate
+def generate_parser():
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.generate",
+                                description="Sample videos / images from a trained experiment directory.")
+    p.add_argument('--exp-dir', required=True, help='experiment_<n> directory of train_video / train_image')
+    p.add_argument('--num-samples', type=int, default=8, help='number of samples')
+    p.add_argument('--batch-size', type=int, default=None, help='samples per generator pass (default: the run\'s)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the noise')
+    p.add_argument('--out', default=None, help='output directory (default: <exp-dir>/eval/samples)')
+    return p
+
+
+def load_generator(exp_dir, device):
+    """(opt, netG) rebuilt from opt.json, netG.pth and Noise_Amps.pth (weights_only loads; nothing is written back)."""
+    import types
+    with open(os.path.join(exp_dir, 'opt.json')) as f:
+        opt = types.SimpleNamespace(**json.load(f))
+    opt.device = device
+    netG = getattr(_networks(opt), opt.generator)(opt)
+    scale, amps = checkpoint.resume_generator(netG, exp_dir)
+    opt.scale_idx = scale
+    opt.Noise_Amps = amps
+    return opt, netG.to(device)
+
+
+def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None):
+    """Draw `num_samples` samples in groups of batch_size (train mode, no_grad: BatchNorm statistics per group, as the
+    reference's previews); write samples.npy (uint8 [N, T, H, W, 3], images [N, H, W, 3]) and one GIF / PNG per sample."""
+    if not torch.cuda.is_available():
+        raise SystemExit("hp-vae-gan_amd: no GPU visible; every op runs on an MI355X")
+    device = torch.device('cuda', torch.cuda.current_device())
+    opt, netG = load_generator(exp_dir, device)
+    bs = int(batch_size or opt.batch_size)
+    torch.manual_seed(seed)
+    netG.train()
+    if opt.dims == 3:
+        level0 = hp_utils.images.level_shape_3d(0, opt)
+        fps = hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[0]
+    else:
+        level0 = hp_utils.images.level_shape_2d(0, opt)
+        fps = 1
+    size = [bs, opt.latent_dim, *level0]
+    samples = []
+    with torch.no_grad(), ops.noise_stream(device):
+        for _ in range(math.ceil(num_samples / bs)):
+            noise_init = hp_utils.generate_noise(size=size, device=device)
+            fake, _ = netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
+            samples.append(ops.video_to_u8(fake).cpu().numpy())
+    arr = np.concatenate(samples, 0)[:num_samples]
+    out = out or os.path.join(exp_dir, 'eval', 'samples')
+    os.makedirs(out, exist_ok=True)
+    np.save(os.path.join(out, 'samples.npy'), arr)
+    ext = '.gif' if opt.dims == 3 else '.png'
+    for i, a in enumerate(arr):
+        write_frames(a, os.path.join(out, 'sample_{:04d}{}'.format(i, ext)), fps)
+    print("wrote {} samples {} to {}".format(len(arr), tuple(arr.shape[1:]), out))
+    return arr
+
+
+def generate_main(argv=None):
+    a = generate_parser().parse_args(argv)
+    generate(a.exp_dir, a.num_samples, a.batch_size, a.seed, a.out)
+    return 0
+
+
+def main_guard(fn):
+    sys.exit(fn())

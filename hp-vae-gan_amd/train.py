@@ -3,8 +3,9 @@ on the MI355X kernels.  Same `opt` blackboard fields, same step sequence and the
 netG stays in train mode for every forward, noise amplitude calibrated at iteration 0 and divided by batch_size,
 clip over ALL generator gradients, a fresh Adam per stage, D gradients of the G step discarded.
 
-Data loading, logging, tensorboard and checkpoint writing are out of scope: `data` is any iterable
-yielding `real` (stage 0) or `(real, real_zero)` device tensors."""
+`data` is any iterable yielding `real` (stage 0) or `(real, real_zero)` device tensors.  Data loading, logging and
+checkpoint writing live in the programs (programs.py); the trainer's two optional hooks serve them: `loss_log` (one device
+append of the iteration's scalars, replayed with the graph) and train()'s per-iteration `callback`."""
 
 import torch
 
@@ -61,13 +62,16 @@ def generator_param_groups(opt, netG):
 def _capture_iteration(trainer, run, nets):
     """Capture `run()` - one eager iteration of `trainer` on its static input buffers - into a hipGraph.  Sets
     trainer._graph / _g_out / _graph_bn / graph_nodes; leaves trainer.iteration where it was (capture records the launches,
-    it does not execute the iteration).  Shared by StageTrainer and BaselineStageTrainer."""
+    it does not execute the iteration).  Returns the output of the warm-up iteration that runs (and counts) before the
+    capture; it is also left in trainer.warmup_out, for a caller that catches GraphCaptureRefused.  Shared by StageTrainer
+    and BaselineStageTrainer."""
     ops.pin_workspaces()  # the graph bakes in scratch addresses: they must outlive later (larger) stages' buffers
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        run()  # warm-up on the capture stream's side (allocator, workspaces)
+        warm = run()  # warm-up on the capture stream's side (allocator, workspaces)
     torch.cuda.current_stream().wait_stream(side)
+    trainer.warmup_out = warm
     it = trainer.iteration
     graph = torch.cuda.CUDAGraph(keep_graph=True)   # keep the hipGraph_t: its nodes are inspected below
     # host-side state that python advances while it records the iteration: BatchNorm forward counts (replays must add
@@ -103,6 +107,7 @@ def _capture_iteration(trainer, run, nets):
             trainer._graph = None
             trainer._g_out = None
             _restore_host_state(trainer, host)
+    return warm
 
 
 class GraphCaptureRefused(RuntimeError):
@@ -164,6 +169,9 @@ class StageTrainer:
         # test hook: callable(trainer) run right after the discriminator's optimizer step (the parity tests put the reference's
         # post-step critic in place there, so that the generator step is judged from an identical state: see tests/helpers.py)
         self.after_d_step = None
+        # telemetry.LossLog with the columns of loss_log_columns(self.is_gan), or None: each iteration then ends with one
+        # append of its scalars, which a captured iteration replays (no host synchronisation per iteration)
+        self.loss_log = None
 
     def calibrate_noise_amp(self, real, real_zero):
         """Iteration-0 noise amplitude (train_video.py:131-145)."""
@@ -268,17 +276,29 @@ class StageTrainer:
         self.iteration += 1
         out.update(total_loss=total_loss.detach(), generated=generated.detach(), generated_vae=generated_vae.detach(),
                    mu=mu.detach(), logvar=logvar.detach(), clip_info=self.clip_info)
+        if self.loss_log is not None:
+            self.loss_log.append([out[k] for k in loss_log_columns(self.is_gan)[:-1]] + [(self.clip_info, 1)])
         self.last = out
         return out
 
 
-def train(opt, netG, data, netD=None, niter=None):
+def loss_log_columns(is_gan):
+    """Columns of a StageTrainer.loss_log row: the iteration's losses (train_video.py:153-202), then the clip norm (clip_info[1])."""
+    if is_gan:
+        return ["rec_loss", "errG", "errD_real", "errD_fake", "gradient_penalty", "total_loss", "grad_norm"]
+    return ["rec_vae_loss", "kl_loss", "total_loss", "grad_norm"]
+
+
+def train(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
     """Train stage opt.scale_idx for opt.niter iterations (reference: train(opt, netG)).  Returns the StageTrainer
-    (holding netD and the last losses) so that the caller can checkpoint exactly what the reference saves."""
+    (holding netD and the last losses) so that the caller can checkpoint exactly what the reference saves.
+    loss_log: a telemetry.LossLog with loss_log_columns(is GAN stage) columns, appended to on every iteration.
+    callback(trainer, out) runs once per iteration that advances trainer.iteration, the capture's warm-up included."""
     if getattr(opt, 'dims', 3) == 3:
         fps, td, fps_index = utils.get_fps_td_by_index(opt.scale_idx, opt)
         opt.fps, opt.td, opt.fps_index = fps, td, fps_index
     trainer = StageTrainer(opt, netG, netD)
+    trainer.loss_log = loss_log
     iterator = iter(data)
     n = opt.niter if niter is None else niter
     while trainer.iteration < n:
@@ -292,12 +312,15 @@ def train(opt, netG, data, netD=None, niter=None):
         else:
             real = item
             real_zero = real
-        trainer.step(real, real_zero)
+        out = trainer.step(real, real_zero)
+        if callback is not None:
+            callback(trainer, out)
         # after two eager iterations (noise-amplitude calibration done, every workspace at its final size) the iteration
         # is captured once and replayed as a hipGraph: the host leaves the critical path (opt.hip_graph = False: stay
         # eager).  Capturing runs one more real iteration on this batch first (side-stream warm-up), which counts.
         if (trainer.iteration == 2 and n - trainer.iteration >= 2 and getattr(opt, 'hip_graph', True)
                 and getattr(trainer, '_graph', None) is None and real.is_cuda):
+            before = trainer.iteration
             try:
                 trainer.enable_graph(real, real_zero)
             except GraphCaptureRefused as e:
@@ -306,6 +329,8 @@ def train(opt, netG, data, netD=None, niter=None):
                 print("hp-vae-gan_amd: hipGraph replay off for stage %d (%s; node census %s)"
                       % (opt.scale_idx, e, getattr(trainer, "graph_nodes", None)))
                 opt.hip_graph = False
+            if callback is not None and trainer.iteration > before:
+                callback(trainer, trainer.warmup_out)
     return trainer
 
 

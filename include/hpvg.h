@@ -228,6 +228,18 @@ int hpvg_upsample_linear_ac_bwd_f32(const float* dy, const float* dy2, float* dx
 int hpvg_frames_resize_norm_u8_f32(const unsigned char* src, float* dst, int N, int H, int W, int first, int step, int count, int h,
                                    int w, int hflip, int quantize, void* stream);
 
+/* ---- the programs' outputs (train_video / train_image / generate) */
+/* write_video's frame conversion (utils/saver.py:8-19): x [B][C][T][H][W] fp32 -> out [B][T][H][W][C] uint8 with
+ * out = (uint8) truncf(clamp((x + 1) * 127.5, 0, 255)), add and multiply rounded separately in fp32; NaN -> 0.  C = 1 or 3
+ * (images: T = 1). */
+int hpvg_video_to_u8_f32(const float* x, unsigned char* out, int B, int C, int T, int H, int W, void* stream);
+/* per-iteration loss log: row (*cursor % capacity) of table [capacity][K] <- (*p[0], ..., *p[K-1]), then *cursor += 1.  The
+ * cursor (a device int) is read and written by the kernel, so a replayed hipGraph appends a fresh row each time.  Values are
+ * copied bit for bit.  1 <= K <= HPVG_LOG_MAX_K; the pointer struct is passed by value. */
+#define HPVG_LOG_MAX_K 16
+typedef struct { const float* p[HPVG_LOG_MAX_K]; } hpvg_scalar_ptrs;
+int hpvg_scalar_log_append_f32(hpvg_scalar_ptrs src, int K, float* table, int capacity, int* cursor, void* stream);
+
 /* ---- spectral norm (nn.utils.spectral_norm, networks_3d.py:63): one power iteration, sigma, 1/sigma; backward through sigma */
 int hpvg_sn_power_iter_f32(const float* w, float* u, float* v, float* sigma, float* inv_sigma, float* uv_copy, int Co, int K,
                            int do_iter, float eps, void* ws, size_t ws_bytes, void* stream);

@@ -546,6 +546,42 @@ __global__ __launch_bounds__(256) void copy_kernel(const float* __restrict__ src
 __global__ __launch_bounds__(256) void zero_kernel(float* __restrict__ out, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = 0.f;
 }
+// dst[bc][t][h][w] = src[bc][t - oT][h - oH][w - oW] inside src, +0 outside (zero pad / crop and their backwards).  Indexed by
+// destination: each thread writes 4 consecutive flat elements (one 16-byte store when VEC), decoding the first and carrying
+// w -> h -> t -> bc for the rest; the shifted source is not 16-byte aligned, so it is read per element, each read bounds-checked.
+// n = elements of this launch's dst (< 2^30: the host splits BC), so flat indices fit an int.
+template <bool VEC>
+__global__ __launch_bounds__(256) void box_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int sT,
+                                                       int sH, int sW, int dT, int dH, int dW, int oT, int oH, int oW) {
+  const long svol = (long)sT * sH * sW;
+  for (int i = 4 * (blockIdx.x * 256 + threadIdx.x); i < n; i += 4 * gridDim.x * 256) {
+    int w = i % dW, r = i / dW;
+    int h = r % dH;
+    r /= dH;
+    int t = r % dT, bc = r / dT;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int st = t - oT, sh = h - oH, sw = w - oW;
+      const bool in = i + k < n && (unsigned)st < (unsigned)sT && (unsigned)sh < (unsigned)sH && (unsigned)sw < (unsigned)sW;
+      v[k] = in ? src[bc * svol + ((long)st * sH + sh) * sW + sw] : 0.f;
+      if (++w == dW) {
+        w = 0;
+        if (++h == dH) {
+          h = 0;
+          if (++t == dT) { t = 0; ++bc; }
+        }
+      }
+    }
+    if (VEC && i + 4 <= n) {
+      *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (i + k < n) dst[i + k] = v[k];
+    }
+  }
+}
 // out = a + b
 __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                    float* __restrict__ out, long n) {
@@ -1408,6 +1444,30 @@ int hpvg_copy_f32(const float* src, float* dst, long n, void* stream) {
   if (!dst || n < 1) return HPVG_ERR_ARG;
   if (src) hipLaunchKernelGGL(copy_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, src, dst, n);
   else hipLaunchKernelGGL(zero_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dst, n);
+  return hpvg_launch_status();
+}
+// dst[bc, t, h, w] = src[bc, t - oT, h - oH, w - oW] inside src, else +0 (2-D: sT = dT = 1, oT = 0)
+int hpvg_box_copy_f32(const float* src, float* dst, long BC, int sT, int sH, int sW, int dT, int dH, int dW, int oT, int oH,
+                      int oW, void* stream) {
+  if (!src || !dst || BC < 1 || sT < 1 || sH < 1 || sW < 1 || dT < 1 || dH < 1 || dW < 1) return HPVG_ERR_ARG;
+  const long dvol = (long)dT * dH * dW, svol = (long)sT * sH * sW;
+  const long max_n = 1L << 30;
+  if (dvol > max_n) return HPVG_ERR_UNSUPPORTED;
+  const long chunk = max_n / dvol;   // bc per launch: flat indices of a launch fit an int
+  for (long bc0 = 0; bc0 < BC; bc0 += chunk) {
+    const long nbc = BC - bc0 < chunk ? BC - bc0 : chunk;
+    const int n = (int)(nbc * dvol);
+    const float* s = src + bc0 * svol;
+    float* d = dst + bc0 * dvol;
+    long nb = (n + 4L * 256 - 1) / (4L * 256);
+    if (nb > 8192) nb = 8192;
+    if (((size_t)d & 15) == 0)
+      hipLaunchKernelGGL(box_copy_kernel<true>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, s, d, n, sT, sH, sW, dT, dH,
+                         dW, oT, oH, oW);
+    else
+      hipLaunchKernelGGL(box_copy_kernel<false>, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, s, d, n, sT, sH, sW, dT, dH,
+                         dW, oT, oH, oW);
+  }
   return hpvg_launch_status();
 }
 // out = a + b

@@ -77,6 +77,7 @@ _SIGS = {
     "hpvg_lrelu_mask_mul_f32": [P, P, P, L, P],
     "hpvg_add_f32": [P, P, P, L, P],
     "hpvg_copy_f32": [P, P, L, P],
+    "hpvg_box_copy_f32": [P, P, L, I, I, I, I, I, I, I, I, I, P],
     "hpvg_tanh_fwd_f32": [P, P, P, L, P],
     "hpvg_tanh_bwd_f32": [P, P, P, L, P],
     "hpvg_reparam_fwd_f32": [P, P, P, P, L, P],

@@ -60,10 +60,9 @@ def embed_center(w, dims):
 
 def crop_border(y):
     """padding=0 ("valid") convolution of the SinGAN baselines (networks_3d.py:285-290) = the zero-padded conv with
-    its outermost voxel shell removed (every kept output only ever saw real inputs).  Pure data movement (torch
-    slicing; autograd's backward of it is the zero pad that the backward-data pass needs)."""
-    idx = (slice(None), slice(None)) + (slice(1, -1),) * (y.dim() - 2)
-    return y[idx].contiguous()
+    its outermost voxel shell removed (every kept output only ever saw real inputs).  Pure data movement (ops.CropBorder:
+    its backward is the zero pad, ops.ZeroPad, that the backward-data pass needs)."""
+    return ops.CropBorder.apply(y, 1)
 
 
 class SNConv(nn.Module):
@@ -570,8 +569,7 @@ class GeneratorSG(nn.Module):
         self.body.append(copy.deepcopy(self.body[-1]))
 
     def _zero_pad(self, x):
-        p = self.pad
-        return torch.nn.functional.pad(x, (p, p, p, p, p, p))
+        return ops.ZeroPad.apply(x, self.pad)
 
     def forward(self, noise_init, noise_amp, mode='rand', start=0, stop=None):
         """start / stop (not in the reference; defaults = every stage): run body[start:stop] only.  For start > 0
@@ -627,7 +625,7 @@ class GeneratorCSG(nn.Module):
 
     @staticmethod
     def _zero_pad(x, p):
-        return torch.nn.functional.pad(x, (p,) * 6)
+        return ops.ZeroPad.apply(x, p)
 
     def forward(self, noise_init, noise_amp, mode='rand'):
         p = self.pad
@@ -669,5 +667,5 @@ class WDiscriminatorBaselines(nn.Module):
         self.apply(weights_init)
 
     def forward(self, x):
-        x = torch.nn.functional.pad(x, (self.pad,) * 6)
+        x = ops.ZeroPad.apply(x, self.pad)
         return self.tail(self.body(self.head(x)))

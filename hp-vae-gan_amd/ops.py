@@ -842,6 +842,49 @@ class Add(Function):
         return g, g
 
 
+def _box_copy(src, grow):
+    """[B, C, (T,) H, W] -> every spatial axis grown by 2 * grow (grow < 0 crops), src placed `grow` voxels in and the
+    border zero (hpvg_box_copy_f32)."""
+    src = _c(src)
+    B, C, T, H, W = geom(src)
+    oT = grow if src.dim() == 5 else 0
+    dT, dH, dW = T + 2 * oT, H + 2 * grow, W + 2 * grow
+    if min(dT, dH, dW) < 1:
+        raise RuntimeError("crop of %d from %s leaves nothing" % (-grow, tuple(src.shape)))
+    out = src.new_empty((B, C, dT, dH, dW) if src.dim() == 5 else (B, C, dH, dW))
+    call("hpvg_box_copy_f32", ptr(src), ptr(out), ctypes.c_long(B * C), T, H, W, dT, dH, dW, oT, grow, grow, stream())
+    return out
+
+
+class ZeroPad(Function):
+    """F.pad(x, (p,) * 2 * spatial dims): the zero padding of the SinGAN baselines' volumes (networks_3d.py:205,247-268,
+    300-318).  Its backward is CropBorder and CropBorder's is ZeroPad, so the pair is differentiable to any order (the
+    critic's input pad sits inside the gradient penalty's double backward)."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        ctx.p = p
+        return _box_copy(x, p)
+
+    @staticmethod
+    def backward(ctx, g):
+        return CropBorder.apply(g, ctx.p), None
+
+
+class CropBorder(Function):
+    """y[:, :, c:-c, c:-c(, c:-c)]: the outer `c`-voxel shell removed (a padding=0 convolution = the zero-padded one cropped
+    by 1, _nets.crop_border).  Its backward is ZeroPad."""
+
+    @staticmethod
+    def forward(ctx, y, c=1):
+        ctx.c = c
+        return _box_copy(y, -c)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ZeroPad.apply(g, ctx.c), None
+
+
 class UpsampleAC(Function):
     """Tri/bi-linear resize with align_corners=True to `size`; with `noise`, also returns up + amp*noise
     (utils/images.py:83-105 + networks_3d.py:395-400)."""

@@ -1,4 +1,5 @@
-"""Shared code of the three programs: `python -m hp_vae_gan_amd.train_video`, `.train_image` and `.generate`.
+"""Shared code of the programs: `python -m hp_vae_gan_amd.train_video`, `.train_image`, `.train_video_baselines` (its own
+notes are in train_video_baselines.py) and `.generate`.
 
 The trainers follow the reference's programs (train_video.py:265-417, train_image.py:279-440): the same flags, the same
 setup (noise_amp_init / scale_factor_init, adjust_scales2image, manualSeed drawn when absent and logged, then random.seed
@@ -231,6 +232,11 @@ class _Stage:
 class Program:
     """One training run of train_video / train_image (see the module docstring)."""
 
+    tags = TAGS   # loss-log column -> scalar tag
+
+    def logs_noise_amp(self):
+        return True
+
     def __init__(self, kind, argv=None):
         self.kind = kind
         opt = build_parser(kind).parse_args(argv)
@@ -344,14 +350,15 @@ class Program:
         if lost:
             self.log("Scale {}: the loss log lost {} rows before this drain".format(opt.scale_idx, lost))
         prefix = 'Video/Scale {}/'.format(opt.scale_idx)
+        tags = self.tags
         for step, row in zip(idx.tolist(), rows):
-            lines = [{"tag": prefix + "noise_amp", "step": step, "value": float(opt.noise_amp)}]
-            lines += [{"tag": prefix + TAGS[c], "step": step, "value": float(v)} for c, v in zip(log.columns, row)]
+            lines = [{"tag": prefix + "noise_amp", "step": step, "value": float(opt.noise_amp)}] if self.logs_noise_amp() else []
+            lines += [{"tag": prefix + tags[c], "step": step, "value": float(v)} for c, v in zip(log.columns, row)]
             for ln in lines:
                 self.scalars.write(json.dumps(ln) + '\n')
         self.scalars.flush()
         if len(idx):
-            last = ', '.join('{} {:.5g}'.format(TAGS[c], float(v)) for c, v in zip(log.columns, rows[-1]))
+            last = ', '.join('{} {:.5g}'.format(tags[c], float(v)) for c, v in zip(log.columns, rows[-1]))
             self.log('Scale [{}/{}], Iteration [{}/{}]: noise_amp {:.5g}, {}'.format(
                 opt.scale_idx + 1, opt.stop_scale + 1, int(idx[-1]) + 1, opt.niter, float(opt.noise_amp), last))
 
@@ -400,11 +407,213 @@ def train_main(kind, argv=None):
     return 0
 
 
+# ------------------------------------------------------------------------------------------------ train_video_baselines
+# column of the baselines' loss log -> the reference's tag (train_video_baselines.py:178-184: `rec_loss`, not train_video's
+# `rec loss`) or this project's own (gradient_penalty)
+BASELINE_TAGS = {"errD_real": "errD_real", "errD_fake": "errD_fake", "gradient_penalty": "gradient_penalty", "errG": "errG",
+                 "rec_loss": "rec_loss"}
+
+
+def build_baseline_parser():
+    """The reference's parser of train_video_baselines.py:217-272 (same names, types, defaults and `required`), plus --run-dir
+    and --no-hip-graph."""
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.train_video_baselines",
+                                description="Train a SinGAN-3D baseline on one video, stage by stage, on an MI355X.")
+    a = p.add_argument
+    # load, input, save
+    a('--netG', default='', help='netG.pth of an experiment to resume from (its scale is trained again)')
+    a('--netD', default='', help='accepted, unused (as in the reference)')
+    a('--manualSeed', type=int, help='seed of python random and torch (random when absent)')
+    # networks
+    a('--nc-z', type=int, default=3, help='noise channels')
+    a('--nc-im', type=int, help='image channels', default=3)
+    a('--nfc', type=int, default=64, help='base channel count')
+    a('--ker-size', type=int, default=3, help='kernel size')
+    a('--num-layer', type=int, default=5, help='layers per stage')
+    a('--stride', default=1, help='stride')
+    a('--padd-size', type=int, default=1, help='padding of the critic convolutions')
+    a('--generator', type=str, help='generator class (GeneratorCSG, GeneratorSG)', default='GeneratorCSG')
+    a('--discriminator', type=str, help='discriminator class (WDiscriminator3D, WDiscriminatorBaselines)',
+      default='WDiscriminator3D')
+    # pyramid
+    a('--scale-factor', type=float, default=0.75, help='pyramid scale factor')
+    a('--noise_amp', type=float, default=0.1, help='additive noise weight')
+    a('--min-size', type=int, default=32, help='size of the coarsest scale')
+    a('--max-size', type=int, default=256, help='size of the finest scale')
+    # optimisation
+    a('--niter', type=int, default=50000, help='iterations per scale')
+    a('--lr-g', type=float, default=0.0005, help='generator learning rate')
+    a('--lr-d', type=float, default=0.0005, help='discriminator learning rate')
+    a('--beta1', type=float, default=0.5, help='Adam beta1')
+    a('--disc-loss-weight', type=float, default=1.0, help='adversarial loss weight')
+    a('--Gsteps', type=int, default=1, help='generator optimizer steps per iteration')
+    a('--Dsteps', type=int, default=1, help='discriminator updates per iteration')
+    a('--lambda-grad', type=float, default=0.1, help='gradient penalty weight')
+    a('--alpha', type=float, help='reconstruction loss weight', default=10.)
+    a('--lr-scale', type=float, default=0.2, help='learning-rate scaling of the lower trained stages')
+    a('--train-depth', type=int, default=1, help='stages trained at once')
+    # data
+    a('--video-path', required=True, help='frame directory or .npy [N,H,W,3] uint8 (no mp4 decoder in this build)')
+    a('--start-frame', default=0, type=int, help='first frame')
+    a('--max-frames', default=1000, type=int, help='frames to keep')
+    a('--hflip', action='store_true', default=False, help='random horizontal flips')
+    a('--img-size', type=int, default=256)
+    a('--sampling-rates', type=int, nargs='+', default=[4, 3, 2, 1], help='temporal sampling rates')
+    a('--stop-scale-time', type=int, default=-1)
+    a('--data-rep', type=int, default=1, help='dataset repetitions')
+    # main
+    a('--checkname', type=str, default='DEBUG', help='run name')
+    a('--mode', default='train', help='accepted, unused (as in the reference)')
+    a('--batch-size', type=int, default=2, help='batch size')
+    a('--print-interval', type=int, default=100, help='iterations between log drains (and previews)')
+    a('--visualize', action='store_true', default=False, help='write GIF previews under previews/')
+    a('--no-cuda', action='store_true', default=False, help='refused: there is no CPU path')
+    # this project's own
+    a('--run-dir', default='run', help='root of the run directories')
+    a('--no-hip-graph', action='store_true', default=False, help='stay eager (no hipGraph replay)')
+    p.set_defaults(hflip=False)
+    return p
+
+
+def z_init_shape(opt):
+    """Shape of the baselines' fixed reconstruction noise (train_video_baselines.py:38-43): [B, 3, opt.td, H0, W0] with the
+    level-0 width and height and the time depth of the stage being trained when it is drawn (the first one of the process)."""
+    w = hp_utils.get_scales_by_index(0, opt.scale_factor, opt.stop_scale, opt.img_size)
+    return [opt.batch_size, 3, opt.td, int(w * opt.ar), w]
+
+
+def baseline_netD_dir(opt, exp_dir):
+    """Directory whose netD_{s-1}.pth warm-starts the critic of stage s = opt.scale_idx, or None at stage 0.  On the resumed
+    scale that is the resume directory; the reference reads its experiment directory there too (train_video_baselines.py:45-48),
+    which holds no such file after a resume."""
+    if opt.scale_idx == 0:
+        return None
+    if opt.netG != '' and opt.resumed_idx == opt.scale_idx:
+        return opt.resume_dir
+    return exp_dir
+
+
+class BaselineProgram(Program):
+    """One training run of train_video_baselines (see the module docstring of train_video_baselines.py)."""
+
+    tags = BASELINE_TAGS
+
+    def __init__(self, argv=None):
+        self.kind = 'video'
+        opt = build_baseline_parser().parse_args(argv)
+        if opt.no_cuda:
+            raise SystemExit("--no-cuda: hp-vae-gan_amd has no CPU path; every op runs on an MI355X")
+        self.path = opt.video_path
+        if self.path.lower().endswith('.mp4') or not os.path.exists(self.path):
+            datasets.load_frames(self.path)   # the data front-end's own error (no decoder / missing file)
+        if not torch.cuda.is_available():
+            raise SystemExit("hp-vae-gan_amd: no GPU visible; every op runs on an MI355X")
+        assert opt.disc_loss_weight > 0
+        opt.program = 'train_video_baselines'
+        opt.dims = 3
+        opt.hip_graph = not opt.no_hip_graph
+        self.exp_dir = experiment_dir(opt.run_dir, clip_name(self.path), opt.checkname)
+        opt.experiment_dir = self.exp_dir
+        self.log = Logbook(os.path.join(self.exp_dir, 'logbook.txt'))
+        self.scalars = open(os.path.join(self.exp_dir, 'scalars.jsonl'), 'a')
+        opt.device = torch.device('cuda', torch.cuda.current_device())
+        opt.noise_amp_init = opt.noise_amp
+        opt.scale_factor_init = opt.scale_factor
+        hp_utils.adjust_scales2image(opt.img_size, opt)
+        if opt.manualSeed is None:
+            opt.manualSeed = random.randint(1, 10000)
+        self.log("Random Seed: {}".format(opt.manualSeed))
+        random.seed(opt.manualSeed)
+        torch.manual_seed(opt.manualSeed)
+        opt.scale_idx = 0
+        opt.nfc_prev = 0
+        opt.Noise_Amps = []
+        self.dataset = datasets.SingleVideoDataset(opt)
+        self.loader = torch.utils.data.DataLoader(self.dataset, shuffle=True, drop_last=True, batch_size=opt.batch_size,
+                                                  num_workers=0)
+        if opt.stop_scale_time == -1:
+            opt.stop_scale_time = opt.stop_scale
+        self.opt = opt
+        with open(os.path.join(self.exp_dir, 'opt.json'), 'w') as f:
+            json.dump(json_settings(opt), f, indent=1, sort_keys=True)
+        for k, v in json_settings(opt).items():
+            self.log('{}: {}'.format(k, v))
+        opt.Z_init = None   # drawn at the first stage this process trains
+        self.log("Experiment: {}".format(self.exp_dir))
+        self.netG = getattr(networks_3d, opt.generator)(opt).to(opt.device)
+        if opt.netG != '':
+            opt.scale_idx, opt.resume_dir = resume_info(opt.netG)
+            opt.resumed_idx = opt.scale_idx
+            _, opt.Noise_Amps = checkpoint.resume_generator(self.netG, opt.resume_dir)
+            self.netG.to(opt.device)
+            self.log("Resumed scale {} from {} (Noise_Amps {})".format(opt.scale_idx, opt.resume_dir, opt.Noise_Amps))
+        else:
+            opt.resumed_idx = -1
+        self.trainers = []
+        self.logs = []
+
+    def logs_noise_amp(self):
+        return self.opt.alpha > 0   # (train_video_baselines.py:181-184)
+
+    def save_z_init(self):
+        torch.save({'data': self.opt.Z_init.detach().cpu()}, os.path.join(self.exp_dir, 'Z_init.pth'))
+
+    def train_stage(self):
+        opt = self.opt
+        opt.fps, opt.td, opt.fps_index = hp_utils.get_fps_td_by_index(opt.scale_idx, opt)
+        self.log("Scale {}: FPS {}, time depth {}, sampling rate {}".format(
+            opt.scale_idx, opt.fps, opt.td, opt.sampling_rates[opt.fps_index]))
+        self.dataset.generate_frames(opt.scale_idx)
+        if opt.Z_init is None:
+            opt.Z_init = hp_utils.generate_noise(size=z_init_shape(opt), device=opt.device)
+            self.save_z_init()
+        netD = getattr(networks_3d, opt.discriminator)(opt).to(opt.device)
+        src = baseline_netD_dir(opt, self.exp_dir)
+        if src is not None:
+            checkpoint.warm_start_discriminator(netD, src, opt.scale_idx)
+            self.log("Scale {}: critic warm-started from {}".format(opt.scale_idx,
+                                                                   os.path.join(src, 'netD_{}.pth'.format(opt.scale_idx - 1))))
+        log = telemetry.LossLog(hp_train.baseline_loss_log_columns(opt.alpha), capacity=max(64, 2 * opt.print_interval),
+                                device=opt.device)
+        holder = [None]
+        trainer = hp_train.train_baseline(opt, self.netG, _Loop(self.loader, holder), netD=netD, loss_log=log,
+                                          callback=_Stage(self, log, holder))
+        if trainer.iteration % opt.print_interval != 0:
+            self.drain(log)
+        self.log("Scale {}: {} iterations, hipGraph replay {}".format(
+            opt.scale_idx, trainer.iteration, 'on' if getattr(trainer, '_graph', None) is not None else 'off'))
+        self.save_z_init()
+        checkpoint.save_stage(self.exp_dir, opt, trainer)
+        self.trainers.append(trainer)
+        self.logs.append(log)
+        return trainer
+
+    def preview(self, trainer, out, batch, iteration):
+        """real, generated (alpha > 0) and fake of this iteration (train_video_baselines.py:190-196); no extra draws."""
+        opt = self.opt
+        real = batch[0] if isinstance(batch, (list, tuple)) else batch
+        d = os.path.join(self.exp_dir, 'previews')
+        os.makedirs(d, exist_ok=True)
+        for name, x in (('real', real), ('generated', out['generated']), ('fake', out['fake'])):
+            if x is None:
+                continue
+            u8 = ops.video_to_u8(x.float()).cpu().numpy()
+            for b in range(u8.shape[0]):
+                write_frames(u8[b], os.path.join(d, 'scale{}_iter{:06d}_{}_{}.gif'.format(opt.scale_idx, iteration, name, b)),
+                             opt.fps)
+
+
+def baseline_main(argv=None):
+    BaselineProgram(argv).run()
+    return 0
+
+
 # ------------------------------------------------------------------------------------------------------------ generate
 def generate_parser():
     p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.generate",
                                 description="Sample videos / images from a trained experiment directory.")
-    p.add_argument('--exp-dir', required=True, help='experiment_<n> directory of train_video / train_image')
+    p.add_argument('--exp-dir', required=True, help='experiment_<n> directory of train_video / train_image / '
+                   'train_video_baselines')
     p.add_argument('--num-samples', type=int, default=8, help='number of samples')
     p.add_argument('--batch-size', type=int, default=None, help='samples per generator pass (default: the run\'s)')
     p.add_argument('--seed', type=int, default=0, help='seed of the noise')
@@ -441,12 +650,16 @@ def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None):
     else:
         level0 = hp_utils.images.level_shape_2d(0, opt)
         fps = 1
-    size = [bs, opt.latent_dim, *level0]
+    baseline = getattr(opt, 'program', None) == 'train_video_baselines'
+    size = [bs, 3 if baseline else opt.latent_dim, *level0]
     samples = []
     with torch.no_grad(), ops.noise_stream(device):
         for _ in range(math.ceil(num_samples / bs)):
             noise_init = hp_utils.generate_noise(size=size, device=device)
-            fake, _ = netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
+            if baseline:
+                fake = netG(noise_init, opt.Noise_Amps, mode='rand')
+            else:
+                fake, _ = netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
             samples.append(ops.video_to_u8(fake).cpu().numpy())
     arr = np.concatenate(samples, 0)[:num_samples]
     out = out or os.path.join(exp_dir, 'eval', 'samples')

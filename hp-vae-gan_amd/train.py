@@ -299,30 +299,34 @@ def train(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
         opt.fps, opt.td, opt.fps_index = fps, td, fps_index
     trainer = StageTrainer(opt, netG, netD)
     trainer.loss_log = loss_log
+
+    def inputs(item):
+        return item if opt.scale_idx > 0 else (item, item)
+    return _train_loop(opt, trainer, data, opt.niter if niter is None else niter, inputs, callback)
+
+
+def _train_loop(opt, trainer, data, n, inputs, callback):
+    """The stage loop of train() and train_baseline(): `n` iterations of trainer.step(*inputs(item)) over `data` (restarted
+    when exhausted), callback(trainer, out) after each, and the switch to hipGraph replay after two eager iterations."""
     iterator = iter(data)
-    n = opt.niter if niter is None else niter
     while trainer.iteration < n:
         try:
             item = next(iterator)
         except StopIteration:
             iterator = iter(data)
             item = next(iterator)
-        if opt.scale_idx > 0:
-            real, real_zero = item
-        else:
-            real = item
-            real_zero = real
-        out = trainer.step(real, real_zero)
+        args = inputs(item)
+        out = trainer.step(*args)
         if callback is not None:
             callback(trainer, out)
         # after two eager iterations (noise-amplitude calibration done, every workspace at its final size) the iteration
         # is captured once and replayed as a hipGraph: the host leaves the critical path (opt.hip_graph = False: stay
         # eager).  Capturing runs one more real iteration on this batch first (side-stream warm-up), which counts.
         if (trainer.iteration == 2 and n - trainer.iteration >= 2 and getattr(opt, 'hip_graph', True)
-                and getattr(trainer, '_graph', None) is None and real.is_cuda):
+                and getattr(trainer, '_graph', None) is None and args[0].is_cuda):
             before = trainer.iteration
             try:
-                trainer.enable_graph(real, real_zero)
+                trainer.enable_graph(*args)
             except GraphCaptureRefused as e:
                 # a torch lowering change put a memcpy / memset node into the iteration: say so and train on eagerly (the
                 # trainer's host state was put back by _capture_iteration)
@@ -364,6 +368,8 @@ class BaselineStageTrainer:
         self.optimizerG = hp_optim.FlatAdam(self.arenaG, groups, betas=(opt.beta1, 0.999))
         self.iteration = 0
         self.after_d_step = None   # test hook: callable(trainer, j) after the j-th discriminator update (see StageTrainer)
+        # telemetry.LossLog with the columns of baseline_loss_log_columns(opt.alpha), or None (see StageTrainer.loss_log)
+        self.loss_log = None
 
     def enable_graph(self, real, real_zero=None):
         """Capture one iteration into a hipGraph and replay it from then on (see StageTrainer.enable_graph: call after >= 1
@@ -439,4 +445,27 @@ class BaselineStageTrainer:
         self.iteration += 1
         out.update(errD_real=errD_real.detach(), errD_fake=errD_fake.detach(), gradient_penalty=gradient_penalty.detach(),
                    errG=errG.detach(), fake=fake.detach(), generated=None if generated is None else generated.detach())
+        if self.loss_log is not None:
+            self.loss_log.append([out[k] for k in baseline_loss_log_columns(opt.alpha)])
         return out
+
+
+def baseline_loss_log_columns(alpha):
+    """Columns of a BaselineStageTrainer.loss_log row (train_video_baselines.py:178-184, plus the gradient penalty)."""
+    cols = ["errD_real", "errD_fake", "gradient_penalty", "errG"]
+    return cols + ["rec_loss"] if alpha > 0 else cols
+
+
+def train_baseline(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
+    """train() for the SinGAN baselines (reference: train_video_baselines.py:24-213): stage opt.scale_idx with a
+    BaselineStageTrainer (opt.Z_init set by the caller), the same eager start, hipGraph switch, GraphCaptureRefused
+    handling and hooks.  `data` yields `real` (stage 0) or `(real, real_zero)`; real_zero is not used.  loss_log: a
+    telemetry.LossLog with baseline_loss_log_columns(opt.alpha) columns."""
+    fps, td, fps_index = utils.get_fps_td_by_index(opt.scale_idx, opt)
+    opt.fps, opt.td, opt.fps_index = fps, td, fps_index
+    trainer = BaselineStageTrainer(opt, netG, netD)
+    trainer.loss_log = loss_log
+
+    def inputs(item):
+        return (item[0],) if opt.scale_idx > 0 else (item,)
+    return _train_loop(opt, trainer, data, opt.niter if niter is None else niter, inputs, callback)

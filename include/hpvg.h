@@ -182,6 +182,12 @@ int hpvg_add_f32(const float* a, const float* b, float* out, long n, void* strea
 /* dst = src, or dst = 0 when src is NULL - as a kernel (concatenations / zero fills of an iteration that may be captured
  * into a hipGraph must not become memcpy / memset nodes) */
 int hpvg_copy_f32(const float* src, float* dst, long n, void* stream);
+/* dst[bc, t, h, w] = src[bc, t - oT, h - oH, w - oW] where that index lies inside src, +0.0f elsewhere: the zero pad (offset +p)
+ * and crop (offset -c) of the SinGAN baselines' valid convolutions and padded volumes (networks_3d.py:205,247-268,300-318) and their
+ * backwards (-p / +c), as one kernel indexed by destination (no memset / memcpy node in a captured iteration).  src: [BC][sT][sH][sW],
+ * dst: [BC][dT][dH][dW]; 2-D: sT = dT = 1, oT = 0.  Offsets may be negative; dT * dH * dW <= 2^30. */
+int hpvg_box_copy_f32(const float* src, float* dst, long BC, int sT, int sH, int sW, int dT, int dH, int dW, int oT, int oH,
+                      int oW, void* stream);
 int hpvg_tanh_fwd_f32(const float* x, const float* res /*nullable*/, float* y, long n, void* stream);
 int hpvg_tanh_bwd_f32(const float* dy, const float* y, float* dx, long n, void* stream);
 int hpvg_reparam_fwd_f32(const float* mu, const float* logvar, const float* eps, float* z, long n, void* stream);

@@ -1212,7 +1212,13 @@ Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
     const int nrange = hpvg_cdiv(flat, Lmax);
     int L = hpvg_cdiv(flat, nrange);
     L += L & 1;
-    const int PL = 2 * W + Lmax + 8;                          // reads reach sh + 2 * (Lmax/2 - 1) + 2 * W + 3 <= 2 W + Lmax + 5
+    // The image sits one float into its plane slot and is WRITTEN in whole 16-byte groups: up to (2 W + Lmax + 8) / 4 of
+    // them, so the slot holds 1 + 2 W + Lmax + 8 floats, rounded up to an even count (reads reach sh + 2 * (Lmax/2 - 1) +
+    // 2 * W + 3 <= 2 W + Lmax + 5 only).  With 2 W + Lmax + 8 floats the last group of the last plane ended one float past
+    // the workgroup's LDS, and where the allocation is a whole number of LDS granules (24 planes x 680 floats at W = 208,
+    // x 800 at W = 268) the hardware dropped that whole group: the last pair of every tile read a stale d3 for one channel
+    // of each chunk.
+    const int PL = 2 * W + Lmax + 10;
     const size_t lds = (size_t)WINO_CC * KT * PL * sizeof(float);
     const int ngmax = (L + 2 * W + 2 + 3 + 3) >> 2;           // 16-byte groups of the staged span: one per lane
     const long ntl = (long)B * T * nrange * gridy;

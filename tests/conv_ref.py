@@ -10,6 +10,7 @@ max |ref|) lets a kernel be 1 % wrong in one weight tap; this one does not (test
 Memory.  The references loop over batch samples: torch's CPU conv in float64 builds an im2col buffer of ~6.6 GB for one
 sample at the finest video level (64 channels, 13 x 144 x 256), and the B = 4 reference of that level stays near 10 GB.
 Values are kept in float64; the scales A in float32 (a scale, rounded by 6e-8 of itself)."""
+import itertools
 import os
 import sys
 
@@ -108,6 +109,88 @@ def bias_sum64(dy, prefixes=None):
     want = sorted(set(prefixes)) if prefixes is not None else [dy.shape[0]]
     out = {n: (per[:n].sum(0), pera[:n].sum(0).float()) for n in want}
     return out if prefixes is not None else out[dy.shape[0]]
+
+
+# ---------------------------------------------------------------------------- the same references as plain sums over taps
+# For the baselines' padded volumes (64 channels at 27 x 158 x 270) the im2col of the functions above needs ~16 GB per sample
+# and minutes of CPU time per launch.  The functions below state the same three operations as a sum over the 27 (or 9) taps of
+# a channel matmul on shifted views of the zero-padded input, in float64 on whatever device the inputs live on (torch's own
+# matmul: no code of libhpvg, no MIOpen).  tests/test_baseline_launch_host.py pins them against the functions above.
+def _taps(nd):
+    return itertools.product(range(3), repeat=nd)
+
+
+def _pad1(t):
+    return F.pad(t, (1, 1) * (t.dim() - 2))
+
+
+def _shifted(tp, k, sp):
+    """[B, C, S] copy of the view of tp (padded by 1) that starts at offset k: element pos is tp[pos + k] = t[pos + k - 1]."""
+    v = tp[(slice(None), slice(None)) + tuple(slice(a, a + n) for a, n in zip(k, sp))]
+    return v.reshape(tp.shape[0], tp.shape[1], -1)
+
+
+def _tap(w, k):
+    return w[(slice(None), slice(None)) + tuple(k)]
+
+
+def _fwd_taps(x64, w64):
+    sp = tuple(x64.shape[2:])
+    xp = _pad1(x64)
+    y = torch.zeros(x64.shape[0], w64.shape[0], x64[0, 0].numel(), dtype=torch.float64, device=x64.device)
+    for k in _taps(len(sp)):
+        y += torch.einsum("oc,bcs->bos", _tap(w64, k), _shifted(xp, k, sp))
+    return y.reshape((x64.shape[0], w64.shape[0]) + sp)
+
+
+def _bwd_data_taps(dy64, w64):
+    sp = tuple(dy64.shape[2:])
+    dp = _pad1(dy64)
+    dx = torch.zeros(dy64.shape[0], w64.shape[1], dy64[0, 0].numel(), dtype=torch.float64, device=dy64.device)
+    for k in _taps(len(sp)):
+        # y[pos] takes w[k] x[pos + k - 1], so x[q] gives w[k] to y[q - k + 1]: dy's view at offset 2 - k
+        dx += torch.einsum("oc,bos->bcs", _tap(w64, k), _shifted(dp, tuple(2 - a for a in k), sp))
+    return dx.reshape((dy64.shape[0], w64.shape[1]) + sp)
+
+
+def _bwd_weight_taps(dy64, x64):
+    sp = tuple(dy64.shape[2:])
+    xp = _pad1(x64)
+    d = dy64.reshape(dy64.shape[0], dy64.shape[1], -1)
+    dw = torch.empty((dy64.shape[1], x64.shape[1]) + (3,) * len(sp), dtype=torch.float64, device=dy64.device)
+    for k in _taps(len(sp)):
+        dw[(slice(None), slice(None)) + tuple(k)] = torch.einsum("bos,bcs->oc", d, _shifted(xp, k, sp))
+    return dw
+
+
+def conv_fwd64_taps(x, w, b=None):
+    """conv_fwd64 as a sum over taps, on x's device -> (y, A) (A in float32)."""
+    x64, w64 = x.detach().double(), w.detach().double().to(x.device)
+    y = _fwd_taps(x64, w64)
+    A = _fwd_taps(x64.abs(), w64.abs())
+    if b is not None:
+        b64 = b.detach().double().to(x.device).view(1, -1, *([1] * (x.dim() - 2)))
+        y += b64
+        A += b64.abs()
+    return y, A.float()
+
+
+def conv_bwd_data64_taps(dy, w):
+    """conv_bwd_data64 as a sum over taps, on dy's device -> (dx, A)."""
+    d64, w64 = dy.detach().double(), w.detach().double().to(dy.device)
+    return _bwd_data_taps(d64, w64), _bwd_data_taps(d64.abs(), w64.abs()).float()
+
+
+def conv_bwd_weight64_taps(dy, x):
+    """conv_bwd_weight64 (all samples) as one matmul over samples and positions per tap, on dy's device -> (dw, A)."""
+    d64, x64 = dy.detach().double(), x.detach().double()
+    return _bwd_weight_taps(d64, x64), _bwd_weight_taps(d64.abs(), x64.abs()).float()
+
+
+def bias_sum64_on(dy):
+    """bias_sum64 (all samples) on dy's device -> (db, A)."""
+    d = dy.detach().double().flatten(2)
+    return d.sum(dim=(0, 2)), d.abs().sum(dim=(0, 2)).float()
 
 
 def lrelu(t, slope=0.2):
@@ -231,4 +314,140 @@ def expected_kinds(B, layer, sp):
     """(forward, backward-data, weight-gradient kind, fuses_bias) of KINDS for one launch."""
     s = {p[0]: p[1:] for p in KINDS[tuple(sp)][BATCHES.index(B)].split()}
     j = KIND_LAYERS.index(tuple(layer))
+    return int(s["f"][j]), int(s["d"][j]), int(s["w"][j]), int(s["b"][j])
+
+
+# ------------------------------------------------------------------------------------------------ the baselines' launches
+# The SinGAN-3D baselines (bench.py --config baseline, BASELINE configs[4]; the train_video_baselines program) run VALID
+# convolutions as a padding-1 conv plus a crop on volumes padded by num_layer + 2 (GeneratorSG, WDiscriminatorBaselines) or
+# num_layer (GeneratorCSG; its head and tail: 1) voxels per side (modules/_nets.py), so their launches are at none of the
+# level shapes above.  All of them are B = 2: the baseline trainers never merge passes, and the multi-GPU form is a stage
+# pipeline.
+BASELINE_NETS = ("GeneratorSG", "GeneratorCSG", "WDiscriminatorBaselines")
+
+
+def baseline_opt(device="cpu", **kw):
+    """(opt, level shapes): bench.py's option set of the baseline config (bench.video_opt under CONFIG = "baseline", kw on
+    top) with stop_scale set, and its level shapes."""
+    import bench
+    keep = bench.CONFIG
+    bench.CONFIG = "baseline"
+    try:
+        opt = bench.video_opt(device, **kw)
+    finally:
+        bench.CONFIG = keep
+    shapes = [tuple(int(v) for v in s) for s in bench.stage_shapes(opt, bench._HipGeom)]
+    return opt, shapes
+
+
+def baseline_level_shapes():
+    """Level shapes of the baseline config from bench.py's own geometry; they are video8's."""
+    _, shapes = baseline_opt()
+    assert shapes == level_shapes()["video8"], shapes
+    return shapes
+
+
+def grown(sp, k):
+    return tuple(int(v) + k for v in sp)
+
+
+def baseline_net_groups(net, lvl, opt=None, shapes=None):
+    """[((Cin, Cout), shape)] of the conv launches of pyramid level `lvl` of one baselines network, in forward order (the
+    num_layer equal convs of the critic once), with the pads as modules/_nets.py computes them from opt.num_layer."""
+    if opt is None:
+        opt, shapes = baseline_opt()
+    sp, n, N, nc = shapes[lvl], int(opt.num_layer), int(opt.nfc), int(opt.nc_im)
+    if net == "GeneratorSG":
+        # pad = num_layer + 2; head at the padded size, every conv (padding 1 + crop) sheds one voxel per side
+        full = 2 * (n + 2)
+        return [((nc, N), grown(sp, full))] + [((N, N), grown(sp, full - 2 * (i + 1))) for i in range(n)] + \
+               [((N, nc), grown(sp, full - 2 * (n + 1)))]
+    if net == "GeneratorCSG":
+        # one head (level 0, pad 1); per level num_layer blocks on a volume padded by num_layer; the tail (pad 1) at the
+        # level a step ends on
+        head = [((nc, N), grown(sp, 2))] if lvl == 0 else []
+        return head + [((N, N), grown(sp, 2 * n - 2 * i)) for i in range(n)] + [((N, nc), grown(sp, 2))]
+    if net == "WDiscriminatorBaselines":
+        # input padded by num_layer + 2, padd_size = 1 convs: every conv at the padded size
+        assert int(opt.padd_size) == 1
+        big = grown(sp, 2 * (n + 2))
+        return [((nc, N), big), ((N, N), big), ((N, 1), big)]
+    raise ValueError(net)
+
+
+def baseline_step_groups(generator, discriminator, stage, opt=None, shapes=None):
+    """{((Cin, Cout), shape)} of the conv launches (forward, backward-data and weight gradient alike) of ONE
+    BaselineStageTrainer.step at `stage`: the generator's levels 0 ... stage (GeneratorCSG: one tail, after the last), and
+    the critic at the stage's level - WDiscriminatorBaselines on the padded volume, WDiscriminator3D on the level shape
+    itself (those are launch_groups()'s)."""
+    if opt is None:
+        opt, shapes = baseline_opt()
+    out = set()
+    for lvl in range(stage + 1):
+        g = baseline_net_groups(generator, lvl, opt, shapes)
+        out.update(g[:-1] if generator == "GeneratorCSG" and lvl < stage else g)
+    if discriminator == "WDiscriminatorBaselines":
+        out.update(baseline_net_groups(discriminator, stage, opt, shapes))
+    else:
+        N, nc = int(opt.nfc), int(opt.nc_im)
+        out.update(((ci, co), tuple(shapes[stage])) for ci, co in ((nc, N), (N, N), (N, 1)))
+    return out
+
+
+def baseline_launch_groups():
+    """[("baseline", level, (Cin, Cout), shape)]: every distinct (layer, shape) the three baselines networks launch over
+    the eight levels of the baseline config, in level order; each is launched at B = 2."""
+    opt, shapes = baseline_opt()
+    assert shapes == level_shapes()["video8"], shapes
+    seen, out = set(), []
+    for lvl in range(len(shapes)):
+        for net in BASELINE_NETS:
+            for key in baseline_net_groups(net, lvl, opt, shapes):
+                if key not in seen:
+                    seen.add(key)
+                    out.append(("baseline", lvl, key[0], key[1]))
+    return out
+
+
+BASELINE_B = 2
+
+
+# Expected kernel kinds of the baselines' launches at B = 2, per padded shape, in the notation of KINDS with one digit per
+# layer of LAYERS (3->64, 64->64, 64->3, 64->1); the host test checks all four layers at every shape, the GPU test launches
+# the (layer, shape) pairs of baseline_launch_groups().  The 64->64 forward / backward-data conv leaves the two-axis kernel
+# at all seven shapes of the finest level (W = 258 ... 270) and at four small shapes.
+_B2 = "f0233 d3200 w4344 b0100"     # 64->64 two-axis
+_B1 = "f0133 d3100 w4344 b0100"     # 64->64 forward and backward-data one-axis (the weight gradient stays two-axis)
+BASELINE_KINDS = {
+    # level 0 (4, 27, 48) + 2 ... + 14
+    (6, 29, 50): _B1, (8, 31, 52): _B1, (10, 33, 54): _B2, (12, 35, 56): _B2, (14, 37, 58): _B2, (16, 39, 60): _B2,
+    (18, 41, 62): _B2,
+    # level 1 (4, 34, 61) + 2 ... + 14
+    (6, 36, 63): _B1, (8, 38, 65): _B2, (10, 40, 67): _B2, (12, 42, 69): _B1, (14, 44, 71): _B2, (16, 46, 73): _B2,
+    (18, 48, 75): _B2,
+    # level 2 (4, 43, 78) + 2 ... + 14
+    (6, 45, 80): _B2, (8, 47, 82): _B2, (10, 49, 84): _B2, (12, 51, 86): _B2, (14, 53, 88): _B2, (16, 55, 90): _B2,
+    (18, 57, 92): _B2,
+    # level 3 (5, 55, 99) + 2 ... + 14
+    (7, 57, 101): _B2, (9, 59, 103): _B2, (11, 61, 105): _B2, (13, 63, 107): _B2, (15, 65, 109): _B2, (17, 67, 111): _B2,
+    (19, 69, 113): _B2,
+    # level 4 (5, 70, 125) + 2 ... + 14
+    (7, 72, 127): _B2, (9, 74, 129): _B2, (11, 76, 131): _B2, (13, 78, 133): _B2, (15, 80, 135): _B2, (17, 82, 137): _B2,
+    (19, 84, 139): _B2,
+    # level 5 (7, 89, 159) + 2 ... + 14
+    (9, 91, 161): _B2, (11, 93, 163): _B2, (13, 95, 165): _B2, (15, 97, 167): _B2, (17, 99, 169): _B2, (19, 101, 171): _B2,
+    (21, 103, 173): _B2,
+    # level 6 (7, 113, 202) + 2 ... + 14
+    (9, 115, 204): _B2, (11, 117, 206): _B2, (13, 119, 208): _B2, (15, 121, 210): _B2, (17, 123, 212): _B2,
+    (19, 125, 214): _B2, (21, 127, 216): _B2,
+    # level 7 (13, 144, 256) + 2 ... + 14
+    (15, 146, 258): _B1, (17, 148, 260): _B1, (19, 150, 262): _B1, (21, 152, 264): _B1, (23, 154, 266): _B1,
+    (25, 156, 268): _B1, (27, 158, 270): _B1,
+}
+
+
+def baseline_expected_kinds(layer, sp):
+    """(forward, backward-data, weight-gradient kind, fuses_bias) of BASELINE_KINDS for one B = 2 launch."""
+    s = {p[0]: p[1:] for p in BASELINE_KINDS[tuple(sp)].split()}
+    j = LAYERS.index(tuple(layer))
     return int(s["f"][j]), int(s["d"][j]), int(s["w"][j]), int(s["b"][j])

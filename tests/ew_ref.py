@@ -403,3 +403,71 @@ BN2_PLANS = {
 
 def expected_plan(sp, B, groups):
     return BN_PLANS[tuple(sp)][BN_BATCHES.index((B, groups))]
+
+
+# ------------------------------------------------------------------------------------------------ the baselines' launches
+def baseline_bn_shapes():
+    """[(level, shape)]: what the baselines' BatchNorms see at B = 2 beyond the level shapes themselves - the cropped conv
+    outputs level + 12 ... + 2 (GeneratorSG's head and blocks, GeneratorCSG's blocks) and level + 14 (WDiscriminatorBaselines:
+    padding-1 convs on the padded input).  level + 0 (the last block, GeneratorCSG's head) is in bn_launches()."""
+    opt, shapes = conv_ref.baseline_opt()
+    full = 2 * (int(opt.num_layer) + 2)
+    return [(lvl, conv_ref.grown(sp, k)) for lvl, sp in enumerate(shapes) for k in range(2, full + 1, 2)]
+
+
+def baseline_resize_launches():
+    """[(level, C, in shape, out shape, in-kernel noise)] of the baselines generators' level i -> i + 1 resizes at B = 2:
+    GeneratorSG resizes its 3-channel image to the level and, with noise made in the kernel, straight to the padded size
+    level + 2 (num_layer + 2); GeneratorCSG its nfc-channel features to the level and, with noise, to level + 2 num_layer.
+    (The plain 3-channel level -> level resize is resize_launches()'s.)"""
+    opt, shapes = conv_ref.baseline_opt()
+    n, N, nc = int(opt.num_layer), int(opt.nfc), int(opt.nc_im)
+    out = []
+    for lvl in range(len(shapes) - 1):
+        a, b = shapes[lvl], shapes[lvl + 1]
+        out.append((lvl, nc, a, conv_ref.grown(b, 2 * (n + 2)), True))
+        out.append((lvl, N, a, b, False))
+        out.append((lvl, N, a, conv_ref.grown(b, 2 * n), True))
+    return out
+
+
+def all_level_shapes():
+    """[(config, level, shape)] of all four configs (video, video8, image, baseline = video8's shapes), distinct shapes once."""
+    seen, out = set(), []
+    for cfg, shapes in conv_ref.level_shapes().items():
+        for lvl, sp in enumerate(shapes):
+            if sp not in seen:
+                seen.add(sp)
+                out.append((cfg, lvl, sp))
+    return out
+
+
+# (fused, nsplit, V) of the baselines' first-order BatchNorm launches (B = 2, C = 64, groups = 1) at the shapes of
+# baseline_bn_shapes(), in the notation of BN_PLANS.  (0, 16, 1) - three launches per group with scalar loads - is reached
+# by no launch of BN_PLANS.
+BASELINE_BN_PLANS = {
+    # level 0 (4, 27, 48) + 2 ... + 14
+    (6, 29, 50): (1, 9, 4), (8, 31, 52): (1, 13, 4), (10, 33, 54): (1, 16, 4), (12, 35, 56): (1, 16, 4),
+    (14, 37, 58): (1, 16, 4), (16, 39, 60): (1, 16, 4), (18, 41, 62): (1, 16, 4),
+    # level 1 (4, 34, 61) + 2 ... + 14
+    (6, 36, 63): (1, 14, 4), (8, 38, 65): (1, 16, 4), (10, 40, 67): (1, 16, 4), (12, 42, 69): (1, 16, 4),
+    (14, 44, 71): (1, 16, 4), (16, 46, 73): (1, 16, 4), (18, 48, 75): (1, 16, 4),
+    # level 2 (4, 43, 78) + 2 ... + 14
+    (6, 45, 80): (1, 16, 4), (8, 47, 82): (1, 16, 4), (10, 49, 84): (1, 16, 4), (12, 51, 86): (1, 16, 4),
+    (14, 53, 88): (1, 16, 4), (16, 55, 90): (1, 16, 4), (18, 57, 92): (1, 16, 4),
+    # level 3 (5, 55, 99) + 2 ... + 14
+    (7, 57, 101): (1, 16, 1), (9, 59, 103): (1, 16, 1), (11, 61, 105): (1, 16, 1), (13, 63, 107): (1, 16, 1),
+    (15, 65, 109): (1, 16, 1), (17, 67, 111): (1, 16, 1), (19, 69, 113): (1, 16, 1),
+    # level 4 (5, 70, 125) + 2 ... + 14
+    (7, 72, 127): (1, 16, 4), (9, 74, 129): (1, 16, 2), (11, 76, 131): (1, 16, 4), (13, 78, 133): (1, 16, 2),
+    (15, 80, 135): (1, 16, 4), (17, 82, 137): (1, 16, 2), (19, 84, 139): (1, 16, 4),
+    # level 5 (7, 89, 159) + 2 ... + 14
+    (9, 91, 161): (1, 16, 1), (11, 93, 163): (1, 16, 1), (13, 95, 165): (1, 16, 1), (15, 97, 167): (1, 16, 1),
+    (17, 99, 169): (0, 16, 1), (19, 101, 171): (0, 16, 1), (21, 103, 173): (0, 16, 1),
+    # level 6 (7, 113, 202) + 2 ... + 14
+    (9, 115, 204): (1, 16, 4), (11, 117, 206): (0, 16, 2), (13, 119, 208): (0, 16, 4), (15, 121, 210): (0, 16, 2),
+    (17, 123, 212): (0, 16, 4), (19, 125, 214): (0, 16, 2), (21, 127, 216): (0, 16, 4),
+    # level 7 (13, 144, 256) + 2 ... + 14
+    (15, 146, 258): (0, 16, 4), (17, 148, 260): (0, 16, 4), (19, 150, 262): (0, 16, 4), (21, 152, 264): (0, 16, 4),
+    (23, 154, 266): (0, 16, 4), (25, 156, 268): (0, 16, 4), (27, 158, 270): (0, 16, 4),
+}

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import conv_ref as R
+import launch_common as C
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,7 @@ DEV = "cuda"
 CASES = [(cfg, lvl, layer, sp, B) for (cfg, lvl, layer, sp) in R.launch_groups() for B in R.BATCH_ORDER]
 # worst |got - ref| / A per (quantity, kernel kind), printed at the end of the module
 _STATS = {}
-_GROUP = {}
+_GROUP = C.GroupCache()
 
 
 def _id(case):
@@ -52,9 +53,10 @@ def lib(ops):
 
 def _group(key, layer, sp):
     """Inputs, weights and float64 references of one (level shape, layer), for the batch sizes of R.BATCHES."""
-    if _GROUP.get("key") == key:
-        return _GROUP
-    _GROUP.clear()
+    return _GROUP.get_group(key, lambda: _make_group(key, layer, sp))
+
+
+def _make_group(key, layer, sp):
     Ci, Co = layer
     nd = len(sp)
     n = max(R.BATCHES)
@@ -67,25 +69,16 @@ def _group(key, layer, sp):
     bbase = torch.randn(Co, generator=g)
     y, yA = R.conv_fwd64(x, w, b)
     dx, dxA = R.conv_bwd_data64(dy, w)
-    _GROUP.update(key=key, x=x.to(DEV), dy=dy.to(DEV), w=w.to(DEV), b=b.to(DEV), base=base.to(DEV), bbase=bbase.to(DEV),
-                  x_cpu=x, base64=base.double(), bbase64=bbase.double(), y=y, yA=yA, dx=dx, dxA=dxA,
-                  dw=R.conv_bwd_weight64(dy, x, w.shape, prefixes=R.BATCHES), db=R.bias_sum64(dy, prefixes=R.BATCHES))
-    return _GROUP
+    return dict(x=x.to(DEV), dy=dy.to(DEV), w=w.to(DEV), b=b.to(DEV), base=base.to(DEV), bbase=bbase.to(DEV),
+                x_cpu=x, base64=base.double(), bbase64=bbase.double(), y=y, yA=yA, dx=dx, dxA=dxA,
+                dw=R.conv_bwd_weight64(dy, x, w.shape, prefixes=R.BATCHES), db=R.bias_sum64(dy, prefixes=R.BATCHES))
 
 
 def _check(got, ref, A, what, quantity, kind, **kw):
-    r = R.check(got, ref, A, what, **kw)
-    k = (quantity, kind)
-    _STATS[k] = max(_STATS.get(k, 0.0), r)
+    C.checked(_STATS, got, ref, A, what, quantity, kind, **kw)
 
 
-def _decode_bits(bits, B, C, S):
-    """[B][ceil(C/32)][S] int32 mask words -> bool [B][C][S]: bit c % 32 of word c / 32."""
-    mt = (C + 31) // 32
-    assert bits.numel() == B * mt * S
-    words = bits.view(B, mt, 1, S).cpu()
-    sh = torch.arange(32, dtype=torch.int32).view(1, 1, 32, 1)
-    return ((words >> sh) & 1).view(B, mt * 32, S)[:, :C].bool()
+_decode_bits = C.decode_bits
 
 
 @pytest.mark.parametrize("cfg,lvl,layer,sp,B", CASES, ids=[_id(c) for c in CASES])
@@ -151,9 +144,5 @@ def test_conv_launch_against_float64(ops, lib, cfg, lvl, layer, sp, B):
     _check(r["db"], dbref, dbA, tag + "channel sum", "bias.sum", "-")
 
     # the same launches on a workspace full of NaN (0xFF bytes): every slot a launch reads it must have written itself
-    for buf in ops._ws_cache.values():
-        buf.fill_(0xFF)
-    r2 = launch()
-    for k, v in r.items():
-        if isinstance(v, torch.Tensor):
-            assert torch.equal(r2[k], v), tag + "%s differs after the workspace was filled with 0xFF" % k
+    C.fill_workspaces(ops)
+    C.assert_same(r, launch(), tag)

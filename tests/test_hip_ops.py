@@ -996,3 +996,22 @@ print("first generation ok")
     env = dict(os.environ, HPVG_WINO2R="0")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "first generation ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_conv_wino_rows_staging_last_group_inside_lds(ops):
+    """The one-axis Winograd kernel with rows-as-in-memory staging at 2 x 64 x 6 x 119 x 208 (reached through the fp32
+    out-mask form of the backward-data conv; 2 * 6 * 97 = 1164 tiles of L = 256): the staged image of a plane is 170 16-byte
+    groups behind a one-float offset.  With a plane slot of 680 floats the last group of the last plane crossed the end of a
+    65280-byte LDS allocation (exactly 51 granules), was dropped, and position 255 of every tile was wrong by up to
+    2.7e-2 of A.  Every element against float64, |got - ref| <= TAU * A."""
+    import conv_ref as R
+    g = torch.Generator().manual_seed(208)
+    sp = (6, 119, 208)
+    x = torch.randn(2, 64, *sp, generator=g).to(DEV)
+    dy = torch.randn(2, 64, *sp, generator=g).to(DEV)
+    w = (torch.randn(64, 64, 3, 3, 3, generator=g) / (64 * 27) ** 0.5).to(DEV)
+    got = ops.conv_fwd_raw(dy, w, None, flip=True, out_mask=x)
+    torch.cuda.synchronize()
+    dx, dxA = R.conv_bwd_data64_taps(dy, w)
+    f = torch.where(x > 0, 1.0, 0.2).double()
+    R.check(got, dx * f, dxA * f, "backward-data with fp32 mask, 6 x 119 x 208")

@@ -1,0 +1,314 @@
+// Exact patch nearest neighbours between two uint8 volumes (the evaluate program's hot path): for every space-time patch of a
+// query volume, the smallest squared distance to any patch of a reference volume and the smallest index that attains it
+// (bidirectional patch similarity, Simakov et al. 2008: coherence one way, completeness the other).
+//
+// Volumes are channels-last uint8 [T][H][W][3]; patch i of a volume is the pt x ph x pw x 3 block at the i-th position, in
+// (t, y, x) raster order, of the grid with the side's stride.  D = 3 * pt * ph * pw bytes per patch.
+//
+// Three kernels:
+//   1. patchnn_pack_kernel (once per side): the centred int8 patch matrix [N padded to 128][D padded to 64, zeros] with
+//      value = byte - 128, and the int32 squared norm of every row.  The query side also presets its rows' merge keys.
+//   2. patchnn_min_kernel: an NT GEMM on v_mfma_i32_32x32x32_i8 (int32 accumulation) whose epilogue never stores the
+//      Nq x Nr products: d2 = |q|^2 + |r|^2 - 2 q.r is exact in int32 as long as D * 255^2 < 2^31 (the centring shifts both
+//      operands alike, so the distance is unchanged), each lane keeps a running (min, index) for its rows over the column tiles
+//      its workgroup walks, the 32 lanes of a row merge once at the end and the row's winner goes into a 64-bit key
+//      (d2 << 32) | j with a vector global atomic umin.  min is associative and commutative and the index rides in the low
+//      bits, so the result is independent of the launch geometry and of timing, and ties resolve to the smallest index.
+//   3. patchnn_unpack_kernel: key -> d2, nn.
+//
+// Tile: 128 x 128 per workgroup of four waves (each 64 x 64 = 2 x 2 MFMA tiles of 32 x 32), K step 64 bytes, both operands
+// staged through LDS with 16-byte global loads (two LDS buffers: the next step's loads are in flight during the products, one
+// barrier per step).  LDS rows are 80 bytes apart, so the 16 rows a quarter-wave reads lie on 16 different 16-byte bank slots.
+// A and B fragments are read the same way from row-major [row][k] images (lane l: row l & 31, 16 bytes at k = 16 * (l >> 5)),
+// so whatever order the instruction gives the 32 k values, both operands use the same one and the dot product is unaffected.
+#include <limits.h>
+
+#include "hpvg_common.h"
+#include "hpvg.h"
+
+namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int PNN_TILE = 128;       // rows (query patches) and columns (reference patches) per workgroup tile
+constexpr int PNN_BK = 64;          // bytes of K per step; patch rows are padded to a multiple of it
+constexpr int PNN_LDS_ROW = 80;     // LDS row pitch in bytes (64 + 16)
+constexpr int PNN_TARGET_WGS = 2048;  // the column range is split until the grid has about this many workgroups
+
+struct PnnSide {
+  int T, H, W;      // volume
+  int nT, nY, nX;   // patch grid
+  int st, sy, sx;   // stride
+  long N;           // patches
+  long Npad;        // padded to PNN_TILE
+};
+
+struct PnnGeom {
+  PnnSide q, r;
+  int pt, ph, pw;
+  int D, Dp;
+  size_t off_qmat, off_rmat, off_qn, off_rn, off_keys, bytes;
+};
+
+inline bool pnn_side(PnnSide& s, int T, int H, int W, const int* patch, const int* stride) {
+  if (T < 1 || H < 1 || W < 1 || !stride || stride[0] < 1 || stride[1] < 1 || stride[2] < 1) return false;
+  if (patch[0] > T || patch[1] > H || patch[2] > W) return false;
+  s.T = T; s.H = H; s.W = W;
+  s.st = stride[0]; s.sy = stride[1]; s.sx = stride[2];
+  s.nT = (T - patch[0]) / s.st + 1;
+  s.nY = (H - patch[1]) / s.sy + 1;
+  s.nX = (W - patch[2]) / s.sx + 1;
+  const double n = (double)s.nT * (double)s.nY * (double)s.nX;
+  if (n >= 2147483648.0) return false;
+  s.N = (long)s.nT * s.nY * s.nX;
+  s.Npad = (s.N + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
+  return true;
+}
+
+inline size_t pnn_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline bool pnn_geom(PnnGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                     const int* rstride) {
+  if (!patch || patch[0] < 1 || patch[1] < 1 || patch[2] < 1) return false;
+  const double d = 3.0 * (double)patch[0] * (double)patch[1] * (double)patch[2];
+  if (d * 65025.0 >= 2147483648.0) return false;
+  if (!pnn_side(g.q, Tq, Hq, Wq, patch, qstride) || !pnn_side(g.r, Tr, Hr, Wr, patch, rstride)) return false;
+  g.pt = patch[0]; g.ph = patch[1]; g.pw = patch[2];
+  g.D = 3 * g.pt * g.ph * g.pw;
+  g.Dp = (g.D + PNN_BK - 1) / PNN_BK * PNN_BK;
+  size_t o = 0;
+  g.off_qmat = o; o = pnn_align(o + (size_t)g.q.Npad * g.Dp);
+  g.off_rmat = o; o = pnn_align(o + (size_t)g.r.Npad * g.Dp);
+  g.off_qn = o; o = pnn_align(o + (size_t)g.q.Npad * 4);
+  g.off_rn = o; o = pnn_align(o + (size_t)g.r.Npad * 4);
+  g.off_keys = o; o = pnn_align(o + (size_t)g.q.Npad * 8);
+  g.bytes = o;
+  return true;
+}
+
+// One wave per patch row: lane l writes the 4-byte words l, l + 64, ... of the row (zeros past D) and the wave sums the
+// squares.  Rows past N (tile padding) are all zeros.
+__global__ __launch_bounds__(256) void patchnn_pack_kernel(const unsigned char* __restrict__ vol, signed char* __restrict__ mat,
+                                                            int* __restrict__ norms, unsigned long long* __restrict__ keys,
+                                                            PnnSide s, int ph, int pw, int D, int Dp) {
+  const int lane = threadIdx.x & 63;
+  const int run = pw * 3;  // contiguous bytes of one patch line
+  const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  for (long row = wave0; row < s.Npad; row += (long)gridDim.x * 4) {
+    unsigned* out = (unsigned*)(mat + row * Dp);
+    int sq = 0;
+    if (row < s.N) {
+      const int gx = (int)(row % s.nX);
+      const int gy = (int)((row / s.nX) % s.nY);
+      const int gt = (int)(row / ((long)s.nX * s.nY));
+      const unsigned char* base = vol + (((long)gt * s.st * s.H + (long)gy * s.sy) * s.W + (long)gx * s.sx) * 3;
+      for (int w = lane; w < Dp / 4; w += 64) {
+        unsigned word = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int e = w * 4 + b;
+          if (e < D) {
+            const int line = e / run, off = e - line * run;
+            const int dt = line / ph, dy = line - dt * ph;
+            const int v = (int)base[((long)dt * s.H + dy) * s.W * 3 + off] - 128;
+            sq += v * v;
+            word |= (unsigned)(v & 0xff) << (8 * b);
+          }
+        }
+        out[w] = word;
+      }
+    } else {
+      for (int w = lane; w < Dp / 4; w += 64) out[w] = 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    if (lane == 0) {
+      norms[row] = sq;
+      if (keys) keys[row] = ~0ull;
+    }
+  }
+}
+
+__device__ __forceinline__ void pnn_load_tile(const signed char* __restrict__ A, const signed char* __restrict__ B, long arow0,
+                                              long brow0, int Dp, int k0, int tid, i32x4 (&ra)[2], i32x4 (&rb)[2]) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int c = tid + 256 * u, row = c >> 2, kc = c & 3;
+    ra[u] = *(const i32x4*)(A + (arow0 + row) * Dp + k0 + kc * 16);
+    rb[u] = *(const i32x4*)(B + (brow0 + row) * Dp + k0 + kc * 16);
+  }
+}
+
+__device__ __forceinline__ void pnn_store_tile(signed char* sa, signed char* sb, int tid, const i32x4 (&ra)[2],
+                                               const i32x4 (&rb)[2]) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int c = tid + 256 * u, row = c >> 2, kc = c & 3;
+    *(i32x4*)(sa + row * PNN_LDS_ROW + kc * 16) = ra[u];
+    *(i32x4*)(sb + row * PNN_LDS_ROW + kc * 16) = rb[u];
+  }
+}
+
+// grid: (row tiles, column splits).  Workgroup (x, y) owns query rows [128 x, 128 x + 128) and walks the column tiles
+// [y * tiles_per_split, (y + 1) * tiles_per_split) of the reference side.
+__global__ __launch_bounds__(256) void patchnn_min_kernel(const signed char* __restrict__ A, const signed char* __restrict__ B,
+                                                           const int* __restrict__ qn, const int* __restrict__ rn,
+                                                           unsigned long long* __restrict__ keys, long Nq, long Nr, int Dp,
+                                                           int ncol_tiles, int tiles_per_split) {
+  __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
+  const long arow0 = (long)blockIdx.x * PNN_TILE;
+  const int jt0 = blockIdx.y * tiles_per_split;
+  const int jt1 = min(jt0 + tiles_per_split, ncol_tiles);
+  const int nk = Dp / PNN_BK;
+
+  int best[2][16], bj[2][16];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      best[m][g] = INT_MAX;
+      bj[m][g] = INT_MAX;
+    }
+
+  for (int jt = jt0; jt < jt1; ++jt) {
+    const long brow0 = (long)jt * PNN_TILE;
+    i32x16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
+
+    i32x4 ra[2], rb[2];
+    pnn_load_tile(A, B, arow0, brow0, Dp, 0, tid, ra, rb);  // (the K loop's closing barrier covers buffer 0's last reads)
+    pnn_store_tile(lds[0][0], lds[0][1], tid, ra, rb);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+      const int cur = kt & 1;
+      if (kt + 1 < nk) pnn_load_tile(A, B, arow0, brow0, Dp, (kt + 1) * PNN_BK, tid, ra, rb);
+      const signed char* sa = lds[cur][0] + (wr * 64 + lr) * PNN_LDS_ROW + lh * 16;
+      const signed char* sb = lds[cur][1] + (wc * 64 + lr) * PNN_LDS_ROW + lh * 16;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        i32x4 fa[2], fb[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) fa[m] = *(const i32x4*)(sa + m * 32 * PNN_LDS_ROW + ks * 32);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) fb[n] = *(const i32x4*)(sb + n * 32 * PNN_LDS_ROW + ks * 32);
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
+      }
+      if (kt + 1 < nk) pnn_store_tile(lds[cur ^ 1][0], lds[cur ^ 1][1], tid, ra, rb);
+      __syncthreads();
+    }
+
+    // epilogue: this lane's column of each 32-wide tile against its running minima.  Columns are visited in ascending
+    // order (jt, then n), so a strict < keeps the smallest index among equals.  qn is added once, after the merge.
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      const long j = brow0 + wc * 64 + n * 32 + lr;
+      const bool ok = j < Nr;
+      const int rnj = rn[j];  // padded rows exist (norm 0)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+          const int s = ok ? rnj - 2 * acc[m][n][g] : INT_MAX;
+          if (s < best[m][g]) {
+            best[m][g] = s;
+            bj[m][g] = (int)j;
+          }
+        }
+    }
+  }
+
+  // merge the 32 lanes (columns) of each row, then one atomic per row and wave
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      int b = best[m][g], j = bj[m][g];
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) {
+        const int ob = __shfl_xor(b, o, 64), oj = __shfl_xor(j, o, 64);
+        if (ob < b || (ob == b && oj < j)) {
+          b = ob;
+          j = oj;
+        }
+      }
+      const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+      if (lr == 0 && row < Nq && b != INT_MAX) {
+        const unsigned d2 = (unsigned)qn[row] + (unsigned)b;
+        atomicMin(&keys[row], ((unsigned long long)d2 << 32) | (unsigned)j);
+      }
+    }
+}
+
+__global__ __launch_bounds__(256) void patchnn_unpack_kernel(const unsigned long long* __restrict__ keys, int* __restrict__ d2,
+                                                              int* __restrict__ nn, long N) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    const unsigned long long k = keys[i];
+    d2[i] = (int)(unsigned)(k >> 32);
+    nn[i] = (int)(unsigned)(k & 0xffffffffull);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpvg_patchnn_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
+                        int* out3) {
+  PnnGeom g;
+  if (!out3 || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  out3[0] = (int)g.q.N;
+  out3[1] = (int)g.r.N;
+  out3[2] = g.D;
+  return HPVG_OK;
+}
+
+size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                             const int* rstride) {
+  PnnGeom g;
+  if (!pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return 0;
+  return g.bytes;
+}
+
+int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
+                    const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream) {
+  PnnGeom g;
+  if (!q || !r || !d2 || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+  char* w = (char*)ws;
+  signed char* qmat = (signed char*)(w + g.off_qmat);
+  signed char* rmat = (signed char*)(w + g.off_rmat);
+  int* qn = (int*)(w + g.off_qn);
+  int* rn = (int*)(w + g.off_rn);
+  unsigned long long* keys = (unsigned long long*)(w + g.off_keys);
+  hipStream_t st = (hipStream_t)stream;
+  const long qblocks = g.q.Npad / 4 < 16384 ? g.q.Npad / 4 : 16384;
+  const long rblocks = g.r.Npad / 4 < 16384 ? g.r.Npad / 4 : 16384;
+  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)qblocks), dim3(256), 0, st, q, qmat, qn, keys, g.q, g.ph, g.pw, g.D, g.Dp);
+  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)rblocks), dim3(256), 0, st, r, rmat, rn, (unsigned long long*)nullptr, g.r,
+                     g.ph, g.pw, g.D, g.Dp);
+  const long nrt = g.q.Npad / PNN_TILE, nct = g.r.Npad / PNN_TILE;
+  long splits = (PNN_TARGET_WGS + nrt - 1) / nrt;
+  if (splits > nct) splits = nct;
+  if (splits < 1) splits = 1;
+  const long per = (nct + splits - 1) / splits;
+  splits = (nct + per - 1) / per;
+  hipLaunchKernelGGL(patchnn_min_kernel, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn, keys, g.q.N,
+                     g.r.N, g.Dp, (int)nct, (int)per);
+  long ub = (g.q.N + 255) / 256;
+  if (ub > 4096) ub = 4096;
+  hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, d2, nn, g.q.N);
+  return hpvg_launch_status();
+}
+
+}  // extern "C"

@@ -57,6 +57,12 @@ class _DeviceFrames:
                    count, h, w, 1 if hflip else 0, 1 if quantize else 0, hplib.stream())
         return out
 
+    def clip_u8(self, first, step, count, h, w):
+        """The quantised clip (no flip) back at its uint8 levels, channels-last [count][h][w][3]: the kernel stores
+        (v / 255 - 0.5) / 0.5 in fp32, a few ulp from the level, so rounding (x / 2 + 0.5) * 255 recovers v exactly."""
+        x = self.clip(first, step, count, h, w, False, True)
+        return torch.round((x * 0.5 + 0.5) * 255.0).to(torch.uint8).permute(1, 2, 3, 0).contiguous()
+
 
 class SingleVideoDataset(torch.utils.data.Dataset):
     """datasets/video.py:13-93.  opt.frames (uint8 [N,H,W,3]) or opt.video_path (frame directory / .npy);

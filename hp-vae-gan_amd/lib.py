@@ -100,6 +100,9 @@ _SIGS = {
     "hpvg_frames_resize_norm_u8_f32": [P, P, I, I, I, I, I, I, I, I, I, I, P],
     "hpvg_video_to_u8_f32": [P, P, I, I, I, I, I, P],
     "hpvg_scalar_log_append_f32": [ScalarPtrs, I, P, I, P, P],
+    "hpvg_patchnn_counts": [I, I, I, I, I, I, P, P, P, P],
+    "hpvg_patchnn_ws_bytes": [I, I, I, I, I, I, P, P, P],
+    "hpvg_patchnn_u8": [P, I, I, I, P, I, I, I, P, P, P, P, P, P, Z, P],
     "hpvg_upsample_linear_ac_bwd_f32": [P, P, P, L, I, I, I, I, I, I, P],
     "hpvg_sn_power_iter_f32": [P, P, P, P, P, P, I, I, I, F, P, Z, P],
     "hpvg_div_scalar_f32": [P, P, P, L, P],
@@ -121,7 +124,8 @@ _SIGS = {
     "hpvg_kl_bern_fwd_f32": [P, P, P, Z, L, P],
     "hpvg_kl_bern_bwd_f32": [P, P, P, L, P],
 }
-_SIZE_FUNCS = {"hpvg_conv_wpack_floats_for", "hpvg_conv_mask_words", "hpvg_bn_bwd2_ws_bytes", "hpvg_channel_sum_ws_bytes", "hpvg_conv_fwd_ws_bytes", "hpvg_conv_wpack_floats", "hpvg_conv_bwd_weight_ws_bytes", "hpvg_bn_ws_bytes", "hpvg_reduce_ws_bytes", "hpvg_sn_bwd_ws_bytes"}
+_SIZE_FUNCS = {"hpvg_conv_wpack_floats_for", "hpvg_conv_mask_words", "hpvg_bn_bwd2_ws_bytes", "hpvg_channel_sum_ws_bytes", "hpvg_conv_fwd_ws_bytes", "hpvg_conv_wpack_floats", "hpvg_conv_bwd_weight_ws_bytes", "hpvg_bn_ws_bytes", "hpvg_reduce_ws_bytes", "hpvg_sn_bwd_ws_bytes",
+               "hpvg_patchnn_ws_bytes"}
 
 
 def header_symbols():

@@ -1341,6 +1341,49 @@ def video_to_u8(x):
     return out
 
 
+def _triple(v, name):
+    v = tuple(int(e) for e in v)
+    if len(v) != 3:
+        raise RuntimeError("patch_nn: %s must have 3 entries (t, h, w), got %d" % (name, len(v)))
+    return (ctypes.c_int * 3)(*v)
+
+
+def patch_nn_counts(qshape, rshape, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """(Nq, Nr, D) of a patch_nn call on volumes of (T, H, W) = qshape / rshape (hpvg_patchnn_counts; host only)."""
+    out = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *(int(e) for e in qshape), *(int(e) for e in rshape), _triple(patch, "patch"),
+         _triple(qstride, "qstride"), _triple(rstride, "rstride"), out)
+    return out[0], out[1], out[2]
+
+
+def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """Exact patch nearest neighbours (hpvg_patchnn_u8, i8 matrix cores): query / ref are uint8 device tensors [T,H,W,3] or
+    [H,W,3]; for every patch of the query's strided grid, d2 = the smallest squared distance to a patch of ref's grid and nn =
+    the smallest index (raster order of ref's grid) that attains it.  Both int32, shaped as the query's patch grid."""
+    vols = []
+    for name, t in (("query", query_u8), ("ref", ref_u8)):
+        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise RuntimeError("patch_nn: %s must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (name, t.dtype, tuple(t.shape)))
+        vols.append(_c(t if t.dim() == 4 else t[None]))
+    q, r = vols
+    if query_u8.dim() != ref_u8.dim():
+        raise RuntimeError("patch_nn: query and ref must both be volumes or both be images")
+    if q.device != r.device:
+        raise RuntimeError("patch_nn: query on %s, ref on %s" % (q.device, r.device))
+    pa, qs, rs = _triple(patch, "patch"), _triple(qstride, "qstride"), _triple(rstride, "rstride")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, (ctypes.c_int * 3)())   # refuses bad arguments by name
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
+    ws = workspace(nbytes, q.device)
+    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
+    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
+    call("hpvg_patchnn_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(d2), ptr(nn), ptr(ws), ws.numel(), stream())
+    if query_u8.dim() == 3:
+        d2, nn = d2[0], nn[0]
+    return d2, nn
+
+
 def scalar_log_append_(scalars, table, cursor):
     """Append (*scalars[0], ..., *scalars[K-1]) to row cursor % capacity of `table` [capacity][K] and advance the device int
     `cursor` (hpvg_scalar_log_append_f32: one single-wave kernel; captured into a graph it appends on every replay).

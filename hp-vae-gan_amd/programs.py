@@ -1,5 +1,6 @@
 """Shared code of the programs: `python -m hp_vae_gan_amd.train_video`, `.train_image`, `.train_video_baselines` (its own
-notes are in train_video_baselines.py) and `.generate`.
+notes are in train_video_baselines.py), `.generate` and `.evaluate` (scores of the samples against the training clip: exact patch
+nearest-neighbour coherence / completeness on the i8 matrix cores, ops.patch_nn, and SinGAN's diversity).
 
 The trainers follow the reference's programs (train_video.py:265-417, train_image.py:279-440): the same flags, the same
 setup (noise_amp_init / scale_factor_init, adjust_scales2image, manualSeed drawn when absent and logged, then random.seed
@@ -675,6 +676,155 @@ def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None):
 def generate_main(argv=None):
     a = generate_parser().parse_args(argv)
     generate(a.exp_dir, a.num_samples, a.batch_size, a.seed, a.out)
+    return 0
+
+
+# ------------------------------------------------------------------------------------------------------------ evaluate
+def evaluate_parser():
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.evaluate",
+                                description="Score samples against the training clip: exact patch nearest-neighbour "
+                                "coherence / completeness (bidirectional similarity) and SinGAN's diversity.")
+    p.add_argument('--exp-dir', default=None, help='experiment_<n> directory (gives the samples\' default place and the real volume)')
+    p.add_argument('--samples', default=None, help='samples.npy, uint8 [N,T,H,W,3] or [N,H,W,3] (default: <exp-dir>/eval/samples/'
+                   'samples.npy, as `generate` writes it)')
+    p.add_argument('--real', default=None, help='the real clip / image (.npy, frame directory or image file); with --exp-dir it '
+                   'replaces the run\'s input and is trimmed, sampled and resized like it; without, it is used as it is')
+    p.add_argument('--patch', type=int, nargs=3, default=None, metavar=('T', 'H', 'W'), help='patch (default 3 7 7, images 1 7 7)')
+    p.add_argument('--stride', type=int, nargs=3, default=[1, 1, 1], metavar=('T', 'H', 'W'),
+                   help='stride of the query side of each direction (the other side is always dense)')
+    p.add_argument('--max-samples', type=int, default=None, help='score only the first N samples')
+    p.add_argument('--out', default=None, help='directory of metrics.json (default: beside the samples)')
+    return p
+
+
+def patch_score(d2, D):
+    """coherence / completeness of one direction: mean_i d2[i] / (D * 255^2), from the integer sum (exactly 0.0 for a copy and
+    exactly 1.0 for black against white)."""
+    d2 = torch.as_tensor(d2)
+    return int(d2.sum(dtype=torch.int64)) / (d2.numel() * int(D) * 255 * 255)
+
+
+def nn_unique_frac(nn, Nr):
+    """Distinct nearest-neighbour indices over min(Nq, Nr): low for a sample stitched from a few source patches."""
+    nn = torch.as_tensor(nn)
+    return int(torch.unique(nn).numel()) / min(int(nn.numel()), int(Nr))
+
+
+def diversity(samples, real):
+    """SinGAN's diversity: the mean over pixels of the standard deviation across samples of the channel-mean intensity, over the
+    standard deviation of that intensity over the real volume (population standard deviations).  samples: uint8 [N,T,H,W,3] /
+    [N,H,W,3], real: [T',H,W,3] / [H,W,3]; None when there are fewer than 2 samples, H or W differ, or the real volume is
+    shorter than the samples (its first T frames are used)."""
+    samples, real = torch.as_tensor(samples), torch.as_tensor(real)
+    if samples.shape[0] < 2 or samples.dim() != real.dim() + 1:
+        return None
+    if samples.dim() == 5:
+        T = samples.shape[1]
+        if real.shape[0] < T:
+            return None
+        real = real[:T]
+    if tuple(samples.shape[1:]) != tuple(real.shape):
+        return None
+    s = samples.to(torch.float64).mean(-1)
+    r = real.to(torch.float64).mean(-1)
+    denom = float(r.std(unbiased=False))
+    if denom == 0.0:
+        return None
+    return float(s.std(0, unbiased=False).mean()) / denom
+
+
+def real_volume(opt, real_path=None, device=None):
+    """The real volume the last stage was trained on, as uint8 [T,H,W,3] (images [H,W,3]) on the device: the run's input (or
+    real_path) trimmed by start_frame / max_frames as the dataset does, frames 0, e, 2e, ... with e the last stage's sampling
+    rate, resized to the last stage's size by the dataset's kernel (quantize on, no flip) and mapped back to its uint8 levels."""
+    path = real_path or (opt.video_path if opt.dims == 3 else opt.image_path)
+    frames = datasets.load_frames(path)
+    size = datasets._stage_size(opt, opt.stop_scale)
+    if opt.dims == 3:
+        start = getattr(opt, "start_frame", 0)
+        frames = frames[start:start + opt.max_frames] if getattr(opt, "max_frames", None) else frames[start:]
+        every = opt.sampling_rates[hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[2]]
+        store = datasets._DeviceFrames(frames, device)
+        return store.clip_u8(0, every, len(range(0, store.N, every)), size[0], size[1])
+    store = datasets._DeviceFrames(frames[:1], device)
+    return store.clip_u8(0, 1, 1, size[0], size[1])[0]
+
+
+def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None):
+    """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
+    `out` and returns the metrics."""
+    import types
+    if exp_dir is None and (samples is None or real is None):
+        raise SystemExit("evaluate: give --exp-dir, or both --samples and --real")
+    spath = samples or os.path.join(exp_dir, 'eval', 'samples', 'samples.npy')
+    if not os.path.isfile(spath):
+        raise SystemExit("evaluate: no samples at {}; run `python -m hp_vae_gan_amd.generate --exp-dir {}` first "
+                         "(or pass --samples)".format(spath, exp_dir or '<experiment>'))
+    if not torch.cuda.is_available():
+        raise SystemExit("hp-vae-gan_amd: no GPU visible; every op runs on an MI355X")
+    device = torch.device('cuda', torch.cuda.current_device())
+    arr = np.load(spath, allow_pickle=False)
+    if arr.dtype != np.uint8 or arr.ndim not in (4, 5) or arr.shape[-1] != 3:
+        raise SystemExit("evaluate: samples must be uint8 [N,T,H,W,3] or [N,H,W,3], got {} {}".format(arr.dtype, arr.shape))
+    if max_samples:
+        arr = arr[:max_samples]
+    video = arr.ndim == 5
+    out = out or os.path.dirname(os.path.abspath(spath))
+    os.makedirs(out, exist_ok=True)
+    if exp_dir is not None:
+        with open(os.path.join(exp_dir, 'opt.json')) as f:
+            opt = types.SimpleNamespace(**json.load(f))
+        if (opt.dims == 3) != video:
+            raise SystemExit("evaluate: the samples' rank does not match the experiment ({}-D)".format(opt.dims))
+        real_dev = real_volume(opt, real, device)
+        np.save(os.path.join(out, 'real.npy'), real_dev.cpu().numpy())
+    else:
+        ra = datasets.load_frames(real)
+        if ra.dtype != np.uint8 or ra.shape[-1] != 3:
+            raise SystemExit("evaluate: --real must be uint8 [...,3], got {} {}".format(ra.dtype, ra.shape))
+        if not video and ra.ndim == 4:
+            ra = ra[0]
+        if ra.ndim != arr.ndim - 1:
+            raise SystemExit("evaluate: --real {} does not match samples {}".format(ra.shape, arr.shape))
+        real_dev = torch.from_numpy(np.ascontiguousarray(ra)).to(device)
+    patch = tuple(patch) if patch else ((3, 7, 7) if video else (1, 7, 7))
+    stride = tuple(stride)
+    samples_dev = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+    vol = (lambda t: tuple(t.shape[:3])) if video else (lambda t: (1,) + tuple(t.shape[:2]))
+    coh_counts = ops.patch_nn_counts(vol(samples_dev[0]), vol(real_dev), patch, qstride=stride)
+    com_counts = ops.patch_nn_counts(vol(real_dev), vol(samples_dev[0]), patch, qstride=stride)
+    D = coh_counts[2]
+    per_sample = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    seconds = 0.0
+    for smp in samples_dev:
+        e0.record()
+        d2c, nnc = ops.patch_nn(smp, real_dev, patch, qstride=stride)
+        d2r, _ = ops.patch_nn(real_dev, smp, patch, qstride=stride)
+        e1.record()
+        e1.synchronize()
+        seconds += e0.elapsed_time(e1) / 1e3
+        per_sample.append({"coherence": patch_score(d2c, D), "completeness": patch_score(d2r, D),
+                           "nn_unique_frac": nn_unique_frac(nnc, coh_counts[1])})
+    n = len(per_sample)
+    metrics = {"samples": os.path.abspath(spath), "num_samples": n, "patch": list(patch), "stride": list(stride),
+               "Nq": coh_counts[0], "Nr": coh_counts[1], "D": D, "Nq_completeness": com_counts[0], "Nr_completeness": com_counts[1],
+               "per_sample": per_sample, "patchnn_seconds": seconds, "diversity": diversity(samples_dev, real_dev)}
+    for k in ("coherence", "completeness", "nn_unique_frac"):
+        metrics[k] = sum(p[k] for p in per_sample) / n
+    with open(os.path.join(out, 'metrics.json'), 'w') as f:
+        json.dump(metrics, f, indent=1, sort_keys=True)
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {} "
+          "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
+                                               metrics["nn_unique_frac"],
+                                               "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
+                                               seconds, os.path.join(out, 'metrics.json')))
+    return metrics
+
+
+def evaluate_main(argv=None):
+    a = evaluate_parser().parse_args(argv)
+    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out)
     return 0
 
 

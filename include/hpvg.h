@@ -246,6 +246,25 @@ int hpvg_video_to_u8_f32(const float* x, unsigned char* out, int B, int C, int T
 typedef struct { const float* p[HPVG_LOG_MAX_K]; } hpvg_scalar_ptrs;
 int hpvg_scalar_log_append_f32(hpvg_scalar_ptrs src, int K, float* table, int capacity, int* cursor, void* stream);
 
+/* ---- evaluation: exact patch nearest neighbours between two uint8 volumes (bidirectional patch similarity, Simakov et al. 2008;
+ * the reference has no such measure - its samples are judged by eye or by SVFID, which needs pretrained C3D weights).
+ * q [Tq][Hq][Wq][3] and r [Tr][Hr][Wr][3] are channels-last uint8 (images: T = 1).  Patch i of a volume is the
+ * patch[0] x patch[1] x patch[2] x 3 block at the i-th position, in (t, y, x) raster order, of the grid with that side's stride
+ * (qstride / rstride, each 3 ints, >= 1); D = 3 * patch[0] * patch[1] * patch[2].  patch / qstride / rstride: host arrays.
+ * d2[i] = min_j sum (q_i - r_j)^2 and nn[i] = the SMALLEST j that attains it, both int32 [Nq] and exact: the contraction runs
+ * on the i8 matrix cores with int32 accumulation, which needs D * 255^2 < 2^31.  The result does not depend on launch geometry
+ * or timing.  HPVG_ERR_ARG: a patch larger than a volume, a stride < 1, D * 255^2 >= 2^31, Nq or Nr >= 2^31. */
+/* host only: out3 = Nq, Nr, D */
+int hpvg_patchnn_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
+                        int* out3);
+/* host only: bytes of workspace (both packed int8 patch matrices, their squared norms, one 64-bit merge key per query patch);
+ * 0 for arguments hpvg_patchnn_u8 refuses */
+size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                             const int* rstride);
+/* ws: 16-byte aligned, at least hpvg_patchnn_ws_bytes() bytes (HPVG_ERR_WORKSPACE otherwise) */
+int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
+                    const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- spectral norm (nn.utils.spectral_norm, networks_3d.py:63): one power iteration, sigma, 1/sigma; backward through sigma */
 int hpvg_sn_power_iter_f32(const float* w, float* u, float* v, float* sigma, float* inv_sigma, float* uv_copy, int Co, int K,
                            int do_iter, float eps, void* ws, size_t ws_bytes, void* stream);

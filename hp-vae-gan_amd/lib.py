@@ -103,6 +103,10 @@ _SIGS = {
     "hpvg_patchnn_counts": [I, I, I, I, I, I, P, P, P, P],
     "hpvg_patchnn_ws_bytes": [I, I, I, I, I, I, P, P, P],
     "hpvg_patchnn_u8": [P, I, I, I, P, I, I, I, P, P, P, P, P, P, Z, P],
+    "hpvg_patchproj_bins": [P],
+    "hpvg_patchproj_ws_bytes": [I, I, I, P, P, I],
+    "hpvg_patchproj_hist_u8": [P, I, I, I, P, P, P, I, P, P, Z, P],
+    "hpvg_hist_w1_i32": [P, L, P, L, I, L, P, P],
     "hpvg_upsample_linear_ac_bwd_f32": [P, P, P, L, I, I, I, I, I, I, P],
     "hpvg_sn_power_iter_f32": [P, P, P, P, P, P, I, I, I, F, P, Z, P],
     "hpvg_div_scalar_f32": [P, P, P, L, P],
@@ -125,7 +129,7 @@ _SIGS = {
     "hpvg_kl_bern_bwd_f32": [P, P, P, L, P],
 }
 _SIZE_FUNCS = {"hpvg_conv_wpack_floats_for", "hpvg_conv_mask_words", "hpvg_bn_bwd2_ws_bytes", "hpvg_channel_sum_ws_bytes", "hpvg_conv_fwd_ws_bytes", "hpvg_conv_wpack_floats", "hpvg_conv_bwd_weight_ws_bytes", "hpvg_bn_ws_bytes", "hpvg_reduce_ws_bytes", "hpvg_sn_bwd_ws_bytes",
-               "hpvg_patchnn_ws_bytes"}
+               "hpvg_patchnn_ws_bytes", "hpvg_patchproj_bins", "hpvg_patchproj_ws_bytes"}
 
 
 def header_symbols():
@@ -176,7 +180,7 @@ def ptr(t):
         return None
     if not t.is_cuda:
         raise RuntimeError("hp-vae-gan_amd: tensor is on %s; these ops run only on an MI355X device (no CPU fallback)" % t.device)
-    if t.dtype not in (torch.float32, torch.float64, torch.uint8, torch.int32):  # int32 also carries the 1-bit mask words
+    if t.dtype not in (torch.float32, torch.float64, torch.uint8, torch.int8, torch.int32, torch.int64):  # int32 also carries the 1-bit mask words
         raise RuntimeError("hp-vae-gan_amd: unsupported dtype %s" % t.dtype)
     if not t.is_contiguous():
         raise RuntimeError("hp-vae-gan_amd: tensor must be contiguous")

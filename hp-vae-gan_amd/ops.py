@@ -1341,10 +1341,10 @@ def video_to_u8(x):
     return out
 
 
-def _triple(v, name):
+def _triple(v, name, op="patch_nn"):
     v = tuple(int(e) for e in v)
     if len(v) != 3:
-        raise RuntimeError("patch_nn: %s must have 3 entries (t, h, w), got %d" % (name, len(v)))
+        raise RuntimeError("%s: %s must have 3 entries (t, h, w), got %d" % (op, name, len(v)))
     return (ctypes.c_int * 3)(*v)
 
 
@@ -1382,6 +1382,76 @@ def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
     if query_u8.dim() == 3:
         d2, nn = d2[0], nn[0]
     return d2, nn
+
+
+# one hpvg_patchproj_hist_u8 launch fills at most this many bytes of histogram: the atomics' footprint stays within the 256 MB
+# last-level cache, and the benchmarked case (512 directions at 3 x 7 x 7: 231 MB) is still one launch.  More directions go in
+# chunks of whole 128-direction tiles (one direction at a time where a single histogram row passes the cap), each chunk packing
+# the volume's patches again.
+PATCH_PROJ_HIST_CAP_BYTES = 256 << 20
+
+
+def patch_proj_bins(patch):
+    """NB = 256 D + 1, the bins of one direction's projection histogram for this patch (hpvg_patchproj_bins; host only)."""
+    nb = call("hpvg_patchproj_bins", _triple(patch, "patch", "patch_proj_hist"))
+    if nb == 0:
+        raise RuntimeError("patch_proj_hist: patch %s refused (entries >= 1 and 3 * t * h * w * 255^2 < 2^31)" % (tuple(patch),))
+    return int(nb)
+
+
+def patch_proj_hist(vol_u8, patch, dirs_i8, stride=(1, 1, 1)):
+    """Histograms of the integer projections of every patch of a volume on P directions (hpvg_patchproj_hist_u8, i8 matrix
+    cores): vol is a uint8 device tensor [T,H,W,3] or [H,W,3], dirs an int8 device tensor [P, D] with entries in {-1, 0, +1},
+    D = 3 * t * h * w of the patch.  Returns int32 [P, NB], NB = 256 D + 1: hist[p][b] = the number of patches of the strided
+    grid with sum_k dirs[p][k] * (byte[k] - 128) == b - 128 D.  Exact; every row sums to the patch count."""
+    if vol_u8.dtype != torch.uint8 or vol_u8.dim() not in (3, 4) or vol_u8.shape[-1] != 3:
+        raise RuntimeError("patch_proj_hist: vol must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (vol_u8.dtype, tuple(vol_u8.shape)))
+    v = _c(vol_u8 if vol_u8.dim() == 4 else vol_u8[None])
+    pa, st = _triple(patch, "patch", "patch_proj_hist"), _triple(stride, "stride", "patch_proj_hist")
+    NB = patch_proj_bins(patch)
+    D = (NB - 1) // 256
+    if dirs_i8.dtype != torch.int8 or dirs_i8.dim() != 2 or dirs_i8.shape[0] < 1 or dirs_i8.shape[1] != D:
+        raise RuntimeError("patch_proj_hist: dirs must be int8 [P, %d] with P >= 1 for patch %s, got %s %s"
+                           % (D, tuple(pa), dirs_i8.dtype, tuple(dirs_i8.shape)))
+    dirs = _c(dirs_i8)
+    worst = int(dirs.to(torch.int16).abs().max())
+    if worst > 1:
+        raise RuntimeError("patch_proj_hist: dirs entries must be -1, 0 or +1, got one of magnitude %d" % worst)
+    if not vol_u8.is_cuda or not dirs_i8.is_cuda or vol_u8.device != dirs_i8.device:
+        raise RuntimeError("patch_proj_hist: vol on %s, dirs on %s; both must be on one MI355X device" % (vol_u8.device, dirs_i8.device))
+    P = dirs.shape[0]
+    g = tuple(v.shape[:3])
+    if call("hpvg_patchproj_ws_bytes", *g, pa, st, 1) == 0:
+        raise RuntimeError("patch_proj_hist: vol %s, patch %s, stride %s refused (patch larger than the volume, or a stride < 1)"
+                           % (g, tuple(pa), tuple(st)))
+    chunk = max(1, PATCH_PROJ_HIST_CAP_BYTES // (4 * NB))
+    if chunk >= 128:
+        chunk = chunk // 128 * 128
+    hist = torch.empty(P, NB, dtype=torch.int32, device=v.device)
+    for p0 in range(0, P, chunk):
+        n = min(chunk, P - p0)
+        nbytes = call("hpvg_patchproj_ws_bytes", *g, pa, st, n)
+        ws = workspace(nbytes, v.device)
+        call("hpvg_patchproj_hist_u8", ptr(v), *g, pa, st, ptr(dirs[p0:p0 + n]), n, ptr(hist[p0:p0 + n]), ptr(ws), ws.numel(), stream())
+    return hist
+
+
+def hist_w1(histA, Na, histB, Nb):
+    """num[p] = sum_b |Nb * cA_p(b) - Na * cB_p(b)| over the cumulative counts of two patch_proj_hist results [P, NB]
+    (hpvg_hist_w1_i32): Na * Nb times the 1-D Wasserstein-1 distance of the two projection distributions, int64 [P], exact.
+    Na / Nb are the patch counts of the two volumes."""
+    for name, h in (("histA", histA), ("histB", histB)):
+        if h.dtype != torch.int32 or h.dim() != 2:
+            raise RuntimeError("hist_w1: %s must be int32 [P, NB], got %s %s" % (name, h.dtype, tuple(h.shape)))
+    if histA.shape != histB.shape:
+        raise RuntimeError("hist_w1: histA %s and histB %s must have one shape" % (tuple(histA.shape), tuple(histB.shape)))
+    if not histA.is_cuda or histA.device != histB.device:
+        raise RuntimeError("hist_w1: histA on %s, histB on %s; both must be on one MI355X device" % (histA.device, histB.device))
+    a, b = _c(histA), _c(histB)
+    P, NB = a.shape
+    num = torch.empty(P, dtype=torch.int64, device=a.device)
+    call("hpvg_hist_w1_i32", ptr(a), int(Na), ptr(b), int(Nb), int(P), int(NB), ptr(num), stream())
+    return num
 
 
 def scalar_log_append_(scalars, table, cursor):

@@ -1,6 +1,7 @@
 """Shared code of the programs: `python -m hp_vae_gan_amd.train_video`, `.train_image`, `.train_video_baselines` (its own
 notes are in train_video_baselines.py), `.generate` and `.evaluate` (scores of the samples against the training clip: exact patch
-nearest-neighbour coherence / completeness on the i8 matrix cores, ops.patch_nn, and SinGAN's diversity).
+nearest-neighbour coherence / completeness on the i8 matrix cores, ops.patch_nn, SinGAN's diversity and, with --swd, the exact
+sliced Wasserstein distance between the patch distributions, ops.patch_proj_hist / ops.hist_w1).
 
 The trainers follow the reference's programs (train_video.py:265-417, train_image.py:279-440): the same flags, the same
 setup (noise_amp_init / scale_factor_init, adjust_scales2image, manualSeed drawn when absent and logged, then random.seed
@@ -694,6 +695,9 @@ def evaluate_parser():
                    help='stride of the query side of each direction (the other side is always dense)')
     p.add_argument('--max-samples', type=int, default=None, help='score only the first N samples')
     p.add_argument('--out', default=None, help='directory of metrics.json (default: beside the samples)')
+    p.add_argument('--swd', type=int, default=0, metavar='P', help='also report the exact sliced Wasserstein distance between the '
+                   'patch distributions over P random directions with entries in {-1, 0, +1} (default 0: off)')
+    p.add_argument('--swd-seed', type=int, default=0, help='seed of the directions')
     return p
 
 
@@ -733,6 +737,30 @@ def diversity(samples, real):
     return float(s.std(0, unbiased=False).mean()) / denom
 
 
+def swd_directions(P, D, seed):
+    """int8 [P][D] directions for the sliced Wasserstein distance: entries drawn uniformly from {-1, 0, +1} by
+    numpy.random.default_rng(seed) on the host, all-zero rows drawn again."""
+    rng = np.random.default_rng(seed)
+    dirs = rng.integers(-1, 2, size=(int(P), int(D)), dtype=np.int8)
+    while True:
+        zero = np.flatnonzero(~dirs.any(1))
+        if len(zero) == 0:
+            return dirs
+        dirs[zero] = rng.integers(-1, 2, size=(len(zero), int(D)), dtype=np.int8)
+
+
+def swd_score(num, Na, Nb, dirs):
+    """Sliced Wasserstein distance from the integer numerators of ops.hist_w1: the mean over directions of
+    num[p] / (Na * Nb * 255 * sqrt(nnz_p)), i.e. W1 along the unit vector dirs[p] / sqrt(nnz_p) in units of the full intensity
+    range.  Exactly 0.0 when every numerator is 0 (equal patch multisets)."""
+    num = [int(v) for v in (num.tolist() if hasattr(num, "tolist") else num)]
+    nnz = [int(v) for v in np.count_nonzero(np.asarray(dirs), axis=1)]
+    if len(num) != len(nnz) or not num:
+        raise ValueError("swd_score: %d numerators for %d directions" % (len(num), len(nnz)))
+    scale = int(Na) * int(Nb) * 255
+    return sum((n / scale) / math.sqrt(z) for n, z in zip(num, nnz)) / len(num)   # n / scale: Python's correctly rounded int / int
+
+
 def real_volume(opt, real_path=None, device=None):
     """The real volume the last stage was trained on, as uint8 [T,H,W,3] (images [H,W,3]) on the device: the run's input (or
     real_path) trimmed by start_frame / max_frames as the dataset does, frames 0, e, 2e, ... with e the last stage's sampling
@@ -750,9 +778,9 @@ def real_volume(opt, real_path=None, device=None):
     return store.clip_u8(0, 1, 1, size[0], size[1])[0]
 
 
-def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None):
+def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0):
     """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
-    `out` and returns the metrics."""
+    `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions."""
     import types
     if exp_dir is None and (samples is None or real is None):
         raise SystemExit("evaluate: give --exp-dir, or both --samples and --real")
@@ -812,19 +840,35 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
                "per_sample": per_sample, "patchnn_seconds": seconds, "diversity": diversity(samples_dev, real_dev)}
     for k in ("coherence", "completeness", "nn_unique_frac"):
         metrics[k] = sum(p[k] for p in per_sample) / n
+    swd_text = ""
+    if swd and swd > 0:
+        # the sample side carries the stride, the real side stays dense (as for coherence); its histograms are made once
+        dirs = swd_directions(swd, D, swd_seed)
+        dirs_dev = torch.from_numpy(dirs).to(device)
+        Ns, Nr = coh_counts[0], coh_counts[1]
+        e0.record()
+        hist_real = ops.patch_proj_hist(real_dev, patch, dirs_dev)
+        nums = [ops.hist_w1(ops.patch_proj_hist(smp, patch, dirs_dev, stride), Ns, hist_real, Nr) for smp in samples_dev]
+        e1.record()
+        e1.synchronize()
+        for p, num in zip(per_sample, nums):
+            p["swd"] = swd_score(num.cpu(), Ns, Nr, dirs)
+        metrics.update({"swd": sum(p["swd"] for p in per_sample) / n, "swd_directions": int(swd), "swd_seed": int(swd_seed),
+                        "swd_seconds": e0.elapsed_time(e1) / 1e3})
+        swd_text = " swd {:.6f}".format(metrics["swd"])
     with open(os.path.join(out, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1, sort_keys=True)
-    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {} "
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{} "
           "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
                                                metrics["nn_unique_frac"],
                                                "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
-                                               seconds, os.path.join(out, 'metrics.json')))
+                                               swd_text, seconds, os.path.join(out, 'metrics.json')))
     return metrics
 
 
 def evaluate_main(argv=None):
     a = evaluate_parser().parse_args(argv)
-    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out)
+    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed)
     return 0
 
 

@@ -265,6 +265,24 @@ size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, con
 int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
                     const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- evaluation: exact sliced Wasserstein distance between the patch distributions of two uint8 volumes (the SWD of PGGAN /
+ * GPNN / GPDM with integer directions).  Patches, patch and stride as above.  dirs: int8 [P][D] on the device, entries in
+ * {-1, 0, +1}.  proj(i, p) = sum_k dirs[p][k] * (byte[i][k] - 128) lies in [-128 D, +128 D]; hist[p][proj + 128 D] counts the
+ * patches of the volume, int32 [P][NB] with NB = 256 D + 1 bins.  The contraction runs on the i8 matrix cores, the counts are
+ * integer atomic adds: exact, and independent of launch geometry and timing.  hist is cleared by the call itself.  An entry
+ * outside {-1, 0, +1} is the caller's error: projections that leave the bin range are not counted. */
+/* host only: NB for a patch; 0 for a patch hpvg_patchproj_hist_u8 refuses */
+size_t hpvg_patchproj_bins(const int* patch);
+/* host only: bytes of workspace (the packed int8 patch matrix and the packed directions); 0 for arguments the call refuses */
+size_t hpvg_patchproj_ws_bytes(int T, int H, int W, const int* patch, const int* stride, int P);
+/* HPVG_ERR_ARG: the geometry refusals of hpvg_patchnn_u8, P < 1, hist not 4-byte aligned; ws as for hpvg_patchnn_u8 */
+int hpvg_patchproj_hist_u8(const unsigned char* vol, int T, int H, int W, const int* patch, const int* stride, const signed char* dirs,
+                           int P, int* hist, void* ws, size_t ws_bytes, void* stream);
+/* num[p] = sum_b |Nb * cA_p(b) - Na * cB_p(b)| over the cumulative counts of histA / histB [P][NB]: Na * Nb * W1 of the two
+ * empirical distributions of direction p, int64 [P], exact.  Na / Nb: the patch counts (each row's sum).  HPVG_ERR_ARG: P < 1,
+ * Na or Nb outside [1, 2^31), NB not 256 D + 1 for a D = 3 pt ph pw that hpvg_patchproj_bins accepts, Na * Nb * 256 D >= 2^63. */
+int hpvg_hist_w1_i32(const int* histA, long Na, const int* histB, long Nb, int P, long NB, long long* num, void* stream);
+
 /* ---- spectral norm (nn.utils.spectral_norm, networks_3d.py:63): one power iteration, sigma, 1/sigma; backward through sigma */
 int hpvg_sn_power_iter_f32(const float* w, float* u, float* v, float* sigma, float* inv_sigma, float* uv_copy, int Co, int K,
                            int do_iter, float eps, void* ws, size_t ws_bytes, void* stream);

@@ -16,6 +16,16 @@
 //      bits, so the result is independent of the launch geometry and of timing, and ties resolve to the smallest index.
 //   3. patchnn_unpack_kernel: key -> d2, nn.
 //
+// Weighted search (the patch nearest-neighbour generator's completeness normalisation, GPNN): score = float32(d2) * w_j with a
+// per-reference-patch weight.  patchnn_min_kernel<true> is the same tile with another epilogue: |q_i|^2 is no longer constant
+// along a row of scores, so the epilogue forms the whole d2 = |q_i|^2 + |r_j|^2 - 2 acc in int32 (the row norms of the tile
+// wait in LDS), converts it (round to nearest even) and multiplies once in fp32.  A non-negative float's bit pattern orders
+// like an unsigned integer, so the key (bits << 32) | j and the same atomic umin merge it; a row no comparison won (NaN
+// weights, outside the contract) keeps its preset key and unpacks as score = +inf, nn = -1.
+//
+// Vote (the generator's fold): patch_vote_kernel rebuilds a volume from chosen patches as a gather, one thread per output voxel
+// over the query-grid patches that cover it: no atomics, no zero fill, and integer sums, so the result is exact.
+//
 // Tile: 128 x 128 per workgroup of four waves (each 64 x 64 = 2 x 2 MFMA tiles of 32 x 32), K step 64 bytes, both operands
 // staged through LDS with 16-byte global loads (two LDS buffers: the next step's loads are in flight during the products, one
 // barrier per step).  LDS rows are 80 bytes apart, so the 16 rows a quarter-wave reads lie on 16 different 16-byte bank slots.
@@ -35,6 +45,8 @@
 //   7. hist_w1_kernel: one workgroup per direction walks the NB bins of two histograms in chunks of 1024 with a carried block
 //      prefix sum and accumulates num = sum_b |Nb cA(b) - Na cB(b)| = Na Nb W1 in 64 bits (exact while Na Nb 256 D < 2^63).
 #include <limits.h>
+
+#include <type_traits>
 
 #include "hpvg_common.h"
 #include "hpvg.h"
@@ -192,11 +204,16 @@ __device__ __forceinline__ void pnn_store_tile(signed char* sa, signed char* sb,
 }
 
 // grid: (row tiles, column splits).  Workgroup (x, y) owns query rows [128 x, 128 x + 128) and walks the column tiles
-// [y * tiles_per_split, (y + 1) * tiles_per_split) of the reference side.
-__global__ __launch_bounds__(256) void patchnn_min_kernel(const signed char* __restrict__ A, const signed char* __restrict__ B,
-                                                           const int* __restrict__ qn, const int* __restrict__ rn,
-                                                           unsigned long long* __restrict__ keys, long Nq, long Nr, int Dp,
-                                                           int ncol_tiles, int tiles_per_split) {
+// [y * tiles_per_split, (y + 1) * tiles_per_split) of the reference side.  WEIGHTED: the running minimum is the fp32 score
+// float(d2) * rw[j] instead of the int32 d2 - |q|^2 (rw: [Nr], not padded).  Its epilogue holds 64 more values in flight: left
+// alone the compiler takes 292 registers for it, i.e. one wave per SIMD; asked for the two waves the unweighted kernel runs at
+// (232 registers) it fits 214 without spilling.  amdgpu_waves_per_eu(0) is clang's spelling of "no request" (the attribute is
+// dropped), so the unweighted instantiation keeps its code.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTED ? 2 : 0))) void patchnn_min_kernel(
+    const signed char* __restrict__ A, const signed char* __restrict__ B, const int* __restrict__ qn, const int* __restrict__ rn,
+    const float* __restrict__ rw, unsigned long long* __restrict__ keys, long Nq, long Nr, int Dp, int ncol_tiles,
+    int tiles_per_split) {
   __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
@@ -205,14 +222,23 @@ __global__ __launch_bounds__(256) void patchnn_min_kernel(const signed char* __r
   const int jt1 = min(jt0 + tiles_per_split, ncol_tiles);
   const int nk = Dp / PNN_BK;
 
-  int best[2][16], bj[2][16];
+  typename std::conditional<WEIGHTED, float, int>::type best[2][16];
+  int bj[2][16];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
-      best[m][g] = INT_MAX;
+      if constexpr (WEIGHTED) best[m][g] = __builtin_inff();
+      else best[m][g] = INT_MAX;
       bj[m][g] = INT_MAX;
     }
+  const int* qns = nullptr;
+  if constexpr (WEIGHTED) {
+    // the tile's row norms (padded rows exist); the K loop's barriers come before the first read
+    __shared__ __attribute__((aligned(16))) int qn_tile[PNN_TILE];
+    if (tid < PNN_TILE) qn_tile[tid] = qn[arow0 + tid];
+    qns = qn_tile;
+  }
 
   for (int jt = jt0; jt < jt1; ++jt) {
     const long brow0 = (long)jt * PNN_TILE;
@@ -251,44 +277,96 @@ __global__ __launch_bounds__(256) void patchnn_min_kernel(const signed char* __r
 
     // epilogue: this lane's column of each 32-wide tile against its running minima.  Columns are visited in ascending
     // order (jt, then n), so a strict < keeps the smallest index among equals.  qn is added once, after the merge.
+    if constexpr (!WEIGHTED) {
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-      const long j = brow0 + wc * 64 + n * 32 + lr;
-      const bool ok = j < Nr;
-      const int rnj = rn[j];  // padded rows exist (norm 0)
+      for (int n = 0; n < 2; ++n) {
+        const long j = brow0 + wc * 64 + n * 32 + lr;
+        const bool ok = j < Nr;
+        const int rnj = rn[j];  // padded rows exist (norm 0)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int g = 0; g < 16; ++g) {
+            const int s = ok ? rnj - 2 * acc[m][n][g] : INT_MAX;
+            if (s < best[m][g]) {
+              best[m][g] = s;
+              bj[m][g] = (int)j;
+            }
+          }
+      }
+    } else {
+      // weighted: the score depends on the row's norm too, so the whole exact d2 is formed here, converted (v_cvt_f32_i32
+      // rounds to nearest even) and multiplied once.  A padded column gets the weight +inf: its score is +inf, or NaN where
+      // d2 == 0, and neither passes the strict <; nor does a NaN weight.  No per-element branch.
+      // this lane's 32 row norms: register g of tile m is row m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh
+      i32x4 qrow[2][4];
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          const int s = ok ? rnj - 2 * acc[m][n][g] : INT_MAX;
-          if (s < best[m][g]) {
-            best[m][g] = s;
-            bj[m][g] = (int)j;
+        for (int b = 0; b < 4; ++b) qrow[m][b] = *(const i32x4*)(qns + wr * 64 + m * 32 + 8 * b + 4 * lh);
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        const long j = brow0 + wc * 64 + n * 32 + lr;
+        const int rnj = rn[j];
+        const float wj = j < Nr ? rw[j] : __builtin_inff();  // rw has Nr entries, no padding
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int g = 0; g < 16; ++g) {
+            const int d2 = qrow[m][g >> 2][g & 3] + rnj - 2 * acc[m][n][g];
+            const float s = __fmul_rn((float)d2, wj);
+            if (s < best[m][g]) {
+              best[m][g] = s;
+              bj[m][g] = (int)j;
+            }
           }
-        }
+      }
     }
   }
 
   // merge the 32 lanes (columns) of each row, then one atomic per row and wave
+  if constexpr (!WEIGHTED) {
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+    for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      int b = best[m][g], j = bj[m][g];
+      for (int g = 0; g < 16; ++g) {
+        int b = best[m][g], j = bj[m][g];
 #pragma unroll
-      for (int o = 16; o > 0; o >>= 1) {
-        const int ob = __shfl_xor(b, o, 64), oj = __shfl_xor(j, o, 64);
-        if (ob < b || (ob == b && oj < j)) {
-          b = ob;
-          j = oj;
+        for (int o = 16; o > 0; o >>= 1) {
+          const int ob = __shfl_xor(b, o, 64), oj = __shfl_xor(j, o, 64);
+          if (ob < b || (ob == b && oj < j)) {
+            b = ob;
+            j = oj;
+          }
+        }
+        const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+        if (lr == 0 && row < Nq && b != INT_MAX) {
+          const unsigned d2 = (unsigned)qn[row] + (unsigned)b;
+          atomicMin(&keys[row], ((unsigned long long)d2 << 32) | (unsigned)j);
         }
       }
-      const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
-      if (lr == 0 && row < Nq && b != INT_MAX) {
-        const unsigned d2 = (unsigned)qn[row] + (unsigned)b;
-        atomicMin(&keys[row], ((unsigned long long)d2 << 32) | (unsigned)j);
+  } else {
+    // weighted: scores are >= +0 (or +inf), so their bit patterns compare like the floats; a lane that never won carries
+    // (+inf, INT_MAX) and loses to every lane that did.  A row nobody won keeps its preset key.
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        unsigned b = __float_as_uint(best[m][g]);
+        int j = bj[m][g];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) {
+          const unsigned ob = (unsigned)__shfl_xor((int)b, o, 64);
+          const int oj = __shfl_xor(j, o, 64);
+          if (ob < b || (ob == b && oj < j)) {
+            b = ob;
+            j = oj;
+          }
+        }
+        const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+        if (lr == 0 && row < Nq && j != INT_MAX) atomicMin(&keys[row], ((unsigned long long)b << 32) | (unsigned)j);
       }
-    }
+  }
 }
 
 __global__ __launch_bounds__(256) void patchnn_unpack_kernel(const unsigned long long* __restrict__ keys, int* __restrict__ d2,
@@ -297,6 +375,57 @@ __global__ __launch_bounds__(256) void patchnn_unpack_kernel(const unsigned long
     const unsigned long long k = keys[i];
     d2[i] = (int)(unsigned)(k >> 32);
     nn[i] = (int)(unsigned)(k & 0xffffffffull);
+  }
+}
+
+// key -> score, nn of the weighted search; a key nobody lowered (see patchnn_min_kernel) gives +inf and -1
+__global__ __launch_bounds__(256) void patchnn_unpack_weighted_kernel(const unsigned long long* __restrict__ keys,
+                                                                       float* __restrict__ score, int* __restrict__ nn, long N) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    const unsigned long long k = keys[i];
+    const bool none = k == ~0ull;
+    score[i] = none ? __builtin_inff() : __uint_as_float((unsigned)(k >> 32));
+    nn[i] = none ? -1 : (int)(unsigned)(k & 0xffffffffull);
+  }
+}
+
+// One thread per output voxel (3 channels).  Along each axis the query-grid patches that cover coordinate c are
+// g in [ceil((c - p + 1) / s), floor(c / s)] clipped to the grid, at offset d = c - g s inside the patch.
+__global__ __launch_bounds__(256) void patch_vote_kernel(const unsigned char* __restrict__ v, const int* __restrict__ nn,
+                                                          const unsigned char* __restrict__ fallback, unsigned char* __restrict__ out,
+                                                          PnnSide q, PnnSide r, int pt, int ph, int pw) {
+  const long total = (long)q.T * q.H * q.W;
+  for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
+    const int x = (int)(o % q.W);
+    const int y = (int)((o / q.W) % q.H);
+    const int t = (int)(o / ((long)q.W * q.H));
+    const int gt0 = t < pt ? 0 : (t - pt) / q.st + 1, gt1 = min(t / q.st, q.nT - 1);
+    const int gy0 = y < ph ? 0 : (y - ph) / q.sy + 1, gy1 = min(y / q.sy, q.nY - 1);
+    const int gx0 = x < pw ? 0 : (x - pw) / q.sx + 1, gx1 = min(x / q.sx, q.nX - 1);
+    int s0 = 0, s1 = 0, s2 = 0, cnt = 0;
+    for (int gt = gt0; gt <= gt1; ++gt)
+      for (int gy = gy0; gy <= gy1; ++gy)
+        for (int gx = gx0; gx <= gx1; ++gx) {
+          const int j = nn[((long)gt * q.nY + gy) * q.nX + gx];
+          if (j < 0 || j >= r.N) continue;
+          const int rx = j % r.nX, ry = (j / r.nX) % r.nY, rt = j / (r.nX * r.nY);
+          const int vt = rt * r.st + (t - gt * q.st), vy = ry * r.sy + (y - gy * q.sy), vx = rx * r.sx + (x - gx * q.sx);
+          const unsigned char* b = v + (((long)vt * r.H + vy) * r.W + vx) * 3;
+          s0 += b[0];
+          s1 += b[1];
+          s2 += b[2];
+          ++cnt;
+        }
+    unsigned char* dst = out + o * 3;
+    if (cnt) {
+      dst[0] = (unsigned char)((2 * s0 + cnt) / (2 * cnt));
+      dst[1] = (unsigned char)((2 * s1 + cnt) / (2 * cnt));
+      dst[2] = (unsigned char)((2 * s2 + cnt) / (2 * cnt));
+    } else {
+      dst[0] = fallback[o * 3];
+      dst[1] = fallback[o * 3 + 1];
+      dst[2] = fallback[o * 3 + 2];
+    }
   }
 }
 
@@ -469,11 +598,13 @@ size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, con
   return g.bytes;
 }
 
-int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
-                    const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream) {
-  PnnGeom g;
-  if (!q || !r || !d2 || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
-  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+}  // extern "C"
+
+namespace {
+
+// pack both sides, the min kernel, unpack.  rweight == nullptr: d2 / nn into out0 (int); otherwise score / nn, out0 (float).
+int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r, const float* rweight, void* out0, int* nn, void* ws,
+               void* stream) {
   char* w = (char*)ws;
   signed char* qmat = (signed char*)(w + g.off_qmat);
   signed char* rmat = (signed char*)(w + g.off_rmat);
@@ -492,11 +623,69 @@ int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsign
   if (splits < 1) splits = 1;
   const long per = (nct + splits - 1) / splits;
   splits = (nct + per - 1) / per;
-  hipLaunchKernelGGL(patchnn_min_kernel, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn, keys, g.q.N,
-                     g.r.N, g.Dp, (int)nct, (int)per);
   long ub = (g.q.N + 255) / 256;
   if (ub > 4096) ub = 4096;
-  hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, d2, nn, g.q.N);
+  if (!rweight) {
+    hipLaunchKernelGGL(patchnn_min_kernel<false>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
+                       (const float*)nullptr, keys, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
+    hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (int*)out0, nn, g.q.N);
+  } else {
+    hipLaunchKernelGGL(patchnn_min_kernel<true>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
+                       rweight, keys, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
+    hipLaunchKernelGGL(patchnn_unpack_weighted_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (float*)out0, nn, g.q.N);
+  }
+  return hpvg_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
+                    const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream) {
+  PnnGeom g;
+  if (!q || !r || !d2 || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+  return pnn_launch(g, q, r, nullptr, d2, nn, ws, stream);
+}
+
+int hpvg_patchnn_weighted_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                             const int* patch, const int* qstride, const int* rstride, const float* rweight, float* score, int* nn,
+                             void* ws, size_t ws_bytes, void* stream) {
+  PnnGeom g;
+  if (!q || !r || !rweight || !score || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+  return pnn_launch(g, q, r, rweight, score, nn, ws, stream);
+}
+
+int hpvg_patch_vote_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
+                           long* out3) {
+  PnnGeom g;
+  if (!out3 || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  // along one axis a grid of n patches of p at stride s covers (n - 1) s + p coordinates when s <= p, and n p otherwise
+  const long ct = g.q.st <= g.pt ? (long)(g.q.nT - 1) * g.q.st + g.pt : (long)g.q.nT * g.pt;
+  const long cy = g.q.sy <= g.ph ? (long)(g.q.nY - 1) * g.q.sy + g.ph : (long)g.q.nY * g.ph;
+  const long cx = g.q.sx <= g.pw ? (long)(g.q.nX - 1) * g.q.sx + g.pw : (long)g.q.nX * g.pw;
+  out3[0] = g.q.N;
+  out3[1] = g.r.N;
+  out3[2] = (long)Tq * Hq * Wq - ct * cy * cx;
+  return HPVG_OK;
+}
+
+int hpvg_patch_vote_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int* nn, int Tq, int Hq, int Wq, const int* patch,
+                       const int* qstride, const int* rstride, const unsigned char* fallback, unsigned char* out, void* stream) {
+  PnnGeom g;
+  if (!v || !nn || !fallback || !out || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  // the gather reads v, nn and fallback while other threads write out: out may overlap none of them
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)Tq * Hq * Wq * 3;
+  const uintptr_t in0[3] = {(uintptr_t)fallback, (uintptr_t)v, (uintptr_t)nn};
+  const size_t inb[3] = {(size_t)Tq * Hq * Wq * 3, (size_t)Tr * Hr * Wr * 3, (size_t)g.q.N * 4};
+  for (int k = 0; k < 3; ++k)
+    if (o0 < in0[k] + inb[k] && in0[k] < o1) return HPVG_ERR_ARG;
+  long blocks = ((long)Tq * Hq * Wq + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(patch_vote_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, nn, fallback, out, g.q, g.r,
+                     g.pt, g.ph, g.pw);
   return hpvg_launch_status();
 }
 

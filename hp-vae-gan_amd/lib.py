@@ -103,6 +103,9 @@ _SIGS = {
     "hpvg_patchnn_counts": [I, I, I, I, I, I, P, P, P, P],
     "hpvg_patchnn_ws_bytes": [I, I, I, I, I, I, P, P, P],
     "hpvg_patchnn_u8": [P, I, I, I, P, I, I, I, P, P, P, P, P, P, Z, P],
+    "hpvg_patchnn_weighted_u8": [P, I, I, I, P, I, I, I, P, P, P, P, P, P, P, Z, P],
+    "hpvg_patch_vote_u8": [P, I, I, I, P, I, I, I, P, P, P, P, P, P],
+    "hpvg_patch_vote_counts": [I, I, I, I, I, I, P, P, P, P],
     "hpvg_patchproj_bins": [P],
     "hpvg_patchproj_ws_bytes": [I, I, I, P, P, I],
     "hpvg_patchproj_hist_u8": [P, I, I, I, P, P, P, I, P, P, Z, P],

@@ -1384,6 +1384,84 @@ def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
     return d2, nn
 
 
+def _patch_volumes(op, pairs):
+    """The uint8 [T,H,W,3] views of volumes or images (all of one rank, on one device), and whether they are images."""
+    vols = []
+    for name, t in pairs:
+        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise RuntimeError("%s: %s must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (op, name, t.dtype, tuple(t.shape)))
+        if t.dim() != pairs[0][1].dim():
+            raise RuntimeError("%s: %s and %s must both be volumes or both be images" % (op, pairs[0][0], name))
+        if t.device != pairs[0][1].device:
+            raise RuntimeError("%s: %s on %s, %s on %s" % (op, pairs[0][0], pairs[0][1].device, name, t.device))
+        vols.append(_c(t if t.dim() == 4 else t[None]))
+    return vols, pairs[0][1].dim() == 3
+
+
+def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """patch_nn with a weight per reference patch (hpvg_patchnn_weighted_u8, i8 matrix cores; GPNN's completeness
+    normalisation): score = min_j float32(d2_ij) * ref_weight[j], the exact int32 distance converted and multiplied once in
+    fp32, and nn = the smallest j that attains it.  ref_weight: float32 device tensor of Nr entries (flat, or shaped as ref's
+    patch grid), every one finite and > 0.  Returns (score float32, nn int32), shaped as the query's patch grid."""
+    (q, r), image = _patch_volumes("patch_nn_weighted", (("query", query_u8), ("ref", ref_u8)))
+    pa, qs, rs = _triple(patch, "patch", "patch_nn_weighted"), _triple(qstride, "qstride", "patch_nn_weighted"), \
+        _triple(rstride, "rstride", "patch_nn_weighted")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
+    Nr = counts[1]
+    rgrid = tuple((rg[a] - pa[a]) // rs[a] + 1 for a in range(3))
+    w = ref_weight
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != r.device or \
+            tuple(w.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
+        raise RuntimeError("patch_nn_weighted: ref_weight must be float32 [%d] or %s on %s, got %s %s on %s"
+                           % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(w, "dtype", type(w)),
+                              tuple(getattr(w, "shape", ())), getattr(w, "device", None)))
+    w = _c(w)
+    if not bool((torch.isfinite(w) & (w > 0)).all()):   # one device reduction
+        raise RuntimeError("patch_nn_weighted: every ref_weight must be finite and > 0")
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
+    ws = workspace(nbytes, q.device)
+    score = torch.empty(grid, dtype=torch.float32, device=q.device)
+    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
+    call("hpvg_patchnn_weighted_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(w), ptr(score), ptr(nn), ptr(ws), ws.numel(), stream())
+    if image:
+        score, nn = score[0], nn[0]
+    return score, nn
+
+
+def patch_vote_counts(out_shape, values_shape, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """(Nq, Nr, uncovered) of a patch_vote call: the patches of the output's grid, those of the values volume's grid, and the
+    output voxels no patch of the output's grid covers, which take the fallback (hpvg_patch_vote_counts; host only)."""
+    out = (ctypes.c_long * 3)()
+    call("hpvg_patch_vote_counts", *(int(e) for e in out_shape), *(int(e) for e in values_shape), _triple(patch, "patch", "patch_vote"),
+         _triple(qstride, "qstride", "patch_vote"), _triple(rstride, "rstride", "patch_vote"), out)
+    return out[0], out[1], out[2]
+
+
+def patch_vote(values_u8, nn, patch, out_shape, fallback_u8, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """Rebuild a volume from chosen patches (hpvg_patch_vote_u8; the fold of the patch nearest-neighbour generator): every
+    output voxel is the mean, halves rounded up, of the bytes that the patches of the output's grid (qstride) covering it take
+    from the patches nn[i] of values_u8's grid (rstride).  values_u8 / fallback_u8: uint8 device tensors [T,H,W,3] or [H,W,3];
+    out_shape = fallback's (T, H, W) or (H, W); nn: int32 with one entry per patch of the output's grid.  Entries outside
+    [0, Nr) are skipped, and a voxel with no vote takes fallback's byte.  Returns a new uint8 tensor shaped as fallback_u8."""
+    (v, fb), image = _patch_volumes("patch_vote", (("values", values_u8), ("fallback", fallback_u8)))
+    oshape = tuple(int(e) for e in out_shape)
+    if oshape != tuple(fallback_u8.shape[:-1]):
+        raise RuntimeError("patch_vote: out_shape %s is not the fallback's %s" % (oshape, tuple(fallback_u8.shape[:-1])))
+    pa, qs, rs = _triple(patch, "patch", "patch_vote"), _triple(qstride, "qstride", "patch_vote"), _triple(rstride, "rstride", "patch_vote")
+    og, vg = tuple(fb.shape[:3]), tuple(v.shape[:3])
+    Nq = patch_vote_counts(og, vg, patch, qstride, rstride)[0]    # refuses bad arguments by name
+    if not isinstance(nn, torch.Tensor) or nn.dtype != torch.int32 or nn.numel() != Nq or nn.device != v.device:
+        raise RuntimeError("patch_vote: nn must be int32 with %d entries on %s, got %s %s on %s"
+                           % (Nq, v.device, getattr(nn, "dtype", type(nn)), tuple(getattr(nn, "shape", ())), getattr(nn, "device", None)))
+    nn = _c(nn)
+    out = torch.empty_like(fb)
+    call("hpvg_patch_vote_u8", ptr(v), *vg, ptr(nn), *og, pa, qs, rs, ptr(fb), ptr(out), stream())
+    return out[0] if image else out
+
+
 # one hpvg_patchproj_hist_u8 launch fills at most this many bytes of histogram: the atomics' footprint stays within the 256 MB
 # last-level cache, and the benchmarked case (512 directions at 3 x 7 x 7: 231 MB) is still one launch.  More directions go in
 # chunks of whole 128-direction tiles (one direction at a time where a single histogram row passes the cap), each chunk packing

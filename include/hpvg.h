@@ -265,6 +265,30 @@ size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, con
 int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
                     const int* qstride, const int* rstride, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- generation: the two kernels of the patch nearest-neighbour generator (GPNN, Granot et al. 2022; VGPNN, Haim et al. 2022;
+ * the generate_patchnn program).  Volumes, patches, strides, geometry refusals and the workspace are those of hpvg_patchnn_u8.
+ * The search with a weight per reference patch (GPNN's completeness normalisation): rweight is float [Nr] on the device,
+ * score[i] = min_j float32(d2_ij) * rweight[j] with d2_ij the exact int32 squared distance, converted round-to-nearest-even
+ * and multiplied once in fp32; nn[i] = the SMALLEST j that attains the minimum.  score: float [Nq], nn: int32 [Nq].  Contract:
+ * every weight is a finite, positive, normal fp32 and every product stays normal (or is 0); then the result is defined bit for
+ * bit and does not depend on launch geometry or timing.  Outside the contract no index leaves [0, Nr): a query patch that no
+ * comparison won (NaN weights) gets score = +inf, nn = -1.  Workspace: hpvg_patchnn_ws_bytes(). */
+int hpvg_patchnn_weighted_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                             const int* patch, const int* qstride, const int* rstride, const float* rweight, float* score, int* nn,
+                             void* ws, size_t ws_bytes, void* stream);
+/* The vote (fold): out [Tq][Hq][Wq][3] rebuilt from patches of the values volume v [Tr][Hr][Wr][3].  nn: int32 [Nq], for every
+ * patch i of the (Tq, Hq, Wq) grid at qstride the index, in v's grid at rstride, of the patch voted there.  For every output
+ * voxel and channel: sum = the sum over the grid patches i that cover the voxel of the byte of values patch nn[i] at the same
+ * offset inside the patch, cnt = their number, out = (2 sum + cnt) / (2 cnt) in integer arithmetic (the mean, halves rounded
+ * up).  Patches with nn[i] < 0 or nn[i] >= Nr are skipped (nothing outside v is read); where cnt == 0 - the uncovered tail of
+ * a strided grid, or only skipped patches - out takes fallback's byte.  fallback: [Tq][Hq][Wq][3]; out must NOT overlap
+ * fallback, v or nn (HPVG_ERR_ARG): they are read while out is written.  A gather, one thread per voxel: exact, no atomics, no workspace. */
+int hpvg_patch_vote_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int* nn, int Tq, int Hq, int Wq, const int* patch,
+                       const int* qstride, const int* rstride, const unsigned char* fallback, unsigned char* out, void* stream);
+/* host only: out3 = Nq, Nr, the number of output voxels that no patch of the query grid covers */
+int hpvg_patch_vote_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
+                           long* out3);
+
 /* ---- evaluation: exact sliced Wasserstein distance between the patch distributions of two uint8 volumes (the SWD of PGGAN /
  * GPNN / GPDM with integer directions).  Patches, patch and stride as above.  dirs: int8 [P][D] on the device, entries in
  * {-1, 0, +1}.  proj(i, p) = sum_k dirs[p][k] * (byte[i][k] - 128) lies in [-128 D, +128 D]; hist[p][proj + 128 D] counts the

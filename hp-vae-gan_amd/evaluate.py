@@ -1,12 +1,183 @@
 """`python -m hp_vae_gan_amd.evaluate --exp-dir run/<clip>/<checkname>/experiment_<n>` (after `generate`), or
 `--samples S.npy --real R.npy` without an experiment: patch nearest-neighbour coherence / completeness, nn_unique_frac and
-diversity of the samples against the training clip, written to metrics.json (see programs.evaluate)."""
-from .programs import evaluate_main, main_guard
+diversity of the samples against the training clip, written to metrics.json."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume
+
+
+def evaluate_parser():
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.evaluate",
+                                description="Score samples against the training clip: exact patch nearest-neighbour "
+                                "coherence / completeness (bidirectional similarity) and SinGAN's diversity.")
+    p.add_argument('--exp-dir', default=None, help='experiment_<n> directory (gives the samples\' default place and the real volume)')
+    p.add_argument('--samples', default=None, help='samples.npy, uint8 [N,T,H,W,3] or [N,H,W,3] (default: <exp-dir>/eval/samples/'
+                   'samples.npy, as `generate` writes it)')
+    p.add_argument('--real', default=None, help='the real clip / image (.npy, frame directory or image file); with --exp-dir it '
+                   'replaces the run\'s input and is trimmed, sampled and resized like it; without, it is used as it is')
+    p.add_argument('--patch', type=int, nargs=3, default=None, metavar=('T', 'H', 'W'), help='patch (default 3 7 7, images 1 7 7)')
+    p.add_argument('--stride', type=int, nargs=3, default=[1, 1, 1], metavar=('T', 'H', 'W'),
+                   help='stride of the query side of each direction (the other side is always dense)')
+    p.add_argument('--max-samples', type=int, default=None, help='score only the first N samples')
+    p.add_argument('--out', default=None, help='directory of metrics.json (default: beside the samples)')
+    p.add_argument('--swd', type=int, default=0, metavar='P', help='also report the exact sliced Wasserstein distance between the '
+                   'patch distributions over P random directions with entries in {-1, 0, +1} (default 0: off)')
+    p.add_argument('--swd-seed', type=int, default=0, help='seed of the directions')
+    return p
+
+
+def patch_score(d2, D):
+    """coherence / completeness of one direction: mean_i d2[i] / (D * 255^2), from the integer sum (exactly 0.0 for a copy and
+    exactly 1.0 for black against white)."""
+    d2 = torch.as_tensor(d2)
+    return int(d2.sum(dtype=torch.int64)) / (d2.numel() * int(D) * 255 * 255)
+
+
+def nn_unique_frac(nn, Nr):
+    """Distinct nearest-neighbour indices over min(Nq, Nr): low for a sample stitched from a few source patches."""
+    nn = torch.as_tensor(nn)
+    return int(torch.unique(nn).numel()) / min(int(nn.numel()), int(Nr))
+
+
+def diversity(samples, real):
+    """SinGAN's diversity: the mean over pixels of the standard deviation across samples of the channel-mean intensity, over the
+    standard deviation of that intensity over the real volume (population standard deviations).  samples: uint8 [N,T,H,W,3] /
+    [N,H,W,3], real: [T',H,W,3] / [H,W,3]; None when there are fewer than 2 samples, H or W differ, or the real volume is
+    shorter than the samples (its first T frames are used)."""
+    samples, real = torch.as_tensor(samples), torch.as_tensor(real)
+    if samples.shape[0] < 2 or samples.dim() != real.dim() + 1:
+        return None
+    if samples.dim() == 5:
+        T = samples.shape[1]
+        if real.shape[0] < T:
+            return None
+        real = real[:T]
+    if tuple(samples.shape[1:]) != tuple(real.shape):
+        return None
+    s = samples.to(torch.float64).mean(-1)
+    r = real.to(torch.float64).mean(-1)
+    denom = float(r.std(unbiased=False))
+    if denom == 0.0:
+        return None
+    return float(s.std(0, unbiased=False).mean()) / denom
+
+
+def swd_directions(P, D, seed):
+    """int8 [P][D] directions for the sliced Wasserstein distance: entries drawn uniformly from {-1, 0, +1} by
+    numpy.random.default_rng(seed) on the host, all-zero rows drawn again."""
+    rng = np.random.default_rng(seed)
+    dirs = rng.integers(-1, 2, size=(int(P), int(D)), dtype=np.int8)
+    while True:
+        zero = np.flatnonzero(~dirs.any(1))
+        if len(zero) == 0:
+            return dirs
+        dirs[zero] = rng.integers(-1, 2, size=(len(zero), int(D)), dtype=np.int8)
+
+
+def swd_score(num, Na, Nb, dirs):
+    """Sliced Wasserstein distance from the integer numerators of ops.hist_w1: the mean over directions of
+    num[p] / (Na * Nb * 255 * sqrt(nnz_p)), i.e. W1 along the unit vector dirs[p] / sqrt(nnz_p) in units of the full intensity
+    range.  Exactly 0.0 when every numerator is 0 (equal patch multisets)."""
+    num = [int(v) for v in (num.tolist() if hasattr(num, "tolist") else num)]
+    nnz = [int(v) for v in np.count_nonzero(np.asarray(dirs), axis=1)]
+    if len(num) != len(nnz) or not num:
+        raise ValueError("swd_score: %d numerators for %d directions" % (len(num), len(nnz)))
+    scale = int(Na) * int(Nb) * 255
+    return sum((n / scale) / math.sqrt(z) for n, z in zip(num, nnz)) / len(num)   # n / scale: Python's correctly rounded int / int
+
+
+def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0):
+    """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
+    `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions."""
+    if exp_dir is None and (samples is None or real is None):
+        raise SystemExit("evaluate: give --exp-dir, or both --samples and --real")
+    spath = samples or os.path.join(exp_dir, 'eval', 'samples', 'samples.npy')
+    if not os.path.isfile(spath):
+        raise SystemExit("evaluate: no samples at {}; run `python -m hp_vae_gan_amd.generate --exp-dir {}` first "
+                         "(or pass --samples)".format(spath, exp_dir or '<experiment>'))
+    device = gpu_device()
+    arr = np.load(spath, allow_pickle=False)
+    if arr.dtype != np.uint8 or arr.ndim not in (4, 5) or arr.shape[-1] != 3:
+        raise SystemExit("evaluate: samples must be uint8 [N,T,H,W,3] or [N,H,W,3], got {} {}".format(arr.dtype, arr.shape))
+    if max_samples:
+        arr = arr[:max_samples]
+    video = arr.ndim == 5
+    out = out or os.path.dirname(os.path.abspath(spath))
+    os.makedirs(out, exist_ok=True)
+    if exp_dir is not None:
+        opt = load_opt(exp_dir)
+        if (opt.dims == 3) != video:
+            raise SystemExit("evaluate: the samples' rank does not match the experiment ({}-D)".format(opt.dims))
+        real_dev = real_volume(opt, real, device)
+        np.save(os.path.join(out, 'real.npy'), real_dev.cpu().numpy())
+    else:
+        real_dev = load_u8_frames(real, device, not video, "evaluate: --real must be uint8 [...,3]")
+        if real_dev.dim() != arr.ndim - 1:
+            raise SystemExit("evaluate: --real {} does not match samples {}".format(tuple(real_dev.shape), arr.shape))
+    patch = tuple(patch) if patch else default_patch(video)
+    stride = tuple(stride)
+    samples_dev = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+    vol = (lambda t: tuple(t.shape[:3])) if video else (lambda t: (1,) + tuple(t.shape[:2]))
+    coh_counts = ops.patch_nn_counts(vol(samples_dev[0]), vol(real_dev), patch, qstride=stride)
+    com_counts = ops.patch_nn_counts(vol(real_dev), vol(samples_dev[0]), patch, qstride=stride)
+    D = coh_counts[2]
+    per_sample = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    seconds = 0.0
+    for smp in samples_dev:
+        e0.record()
+        d2c, nnc = ops.patch_nn(smp, real_dev, patch, qstride=stride)
+        d2r, _ = ops.patch_nn(real_dev, smp, patch, qstride=stride)
+        e1.record()
+        e1.synchronize()
+        seconds += e0.elapsed_time(e1) / 1e3
+        per_sample.append({"coherence": patch_score(d2c, D), "completeness": patch_score(d2r, D),
+                           "nn_unique_frac": nn_unique_frac(nnc, coh_counts[1])})
+    n = len(per_sample)
+    metrics = {"samples": os.path.abspath(spath), "num_samples": n, "patch": list(patch), "stride": list(stride),
+               "Nq": coh_counts[0], "Nr": coh_counts[1], "D": D, "Nq_completeness": com_counts[0], "Nr_completeness": com_counts[1],
+               "per_sample": per_sample, "patchnn_seconds": seconds, "diversity": diversity(samples_dev, real_dev)}
+    for k in ("coherence", "completeness", "nn_unique_frac"):
+        metrics[k] = sum(p[k] for p in per_sample) / n
+    swd_text = ""
+    if swd and swd > 0:
+        # the sample side carries the stride, the real side stays dense (as for coherence); its histograms are made once
+        dirs = swd_directions(swd, D, swd_seed)
+        dirs_dev = torch.from_numpy(dirs).to(device)
+        Ns, Nr = coh_counts[0], coh_counts[1]
+        e0.record()
+        hist_real = ops.patch_proj_hist(real_dev, patch, dirs_dev)
+        nums = [ops.hist_w1(ops.patch_proj_hist(smp, patch, dirs_dev, stride), Ns, hist_real, Nr) for smp in samples_dev]
+        e1.record()
+        e1.synchronize()
+        for p, num in zip(per_sample, nums):
+            p["swd"] = swd_score(num.cpu(), Ns, Nr, dirs)
+        metrics.update({"swd": sum(p["swd"] for p in per_sample) / n, "swd_directions": int(swd), "swd_seed": int(swd_seed),
+                        "swd_seconds": e0.elapsed_time(e1) / 1e3})
+        swd_text = " swd {:.6f}".format(metrics["swd"])
+    with open(os.path.join(out, 'metrics.json'), 'w') as f:
+        json.dump(metrics, f, indent=1, sort_keys=True)
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{} "
+          "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
+                                               metrics["nn_unique_frac"],
+                                               "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
+                                               swd_text, seconds, os.path.join(out, 'metrics.json')))
+    return metrics
 
 
 def main(argv=None):
-    return evaluate_main(argv)
+    a = evaluate_parser().parse_args(argv)
+    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed)
+    return 0
 
 
 if __name__ == "__main__":
-    main_guard(main)
+    sys.exit(main())

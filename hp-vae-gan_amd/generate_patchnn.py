@@ -1,12 +1,232 @@
 """`python -m hp_vae_gan_amd.generate_patchnn --exp-dir run/<clip>/<checkname>/experiment_<n>` (or `--video-path clip.npy --out
 dir`, `--image-path img.png --out dir`): training-free samples of the clip by coarse-to-fine patch nearest neighbours (GPNN /
-VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json (see programs.generate_patchnn)."""
-from .programs import generate_patchnn_main, main_guard
+VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from . import utils as hp_utils
+from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume, write_samples
+
+
+# The training-free counterpart of the trained generator: GPNN (Granot et al., "Drop the GAN", CVPR 2022) and its video form
+# VGPNN (Haim et al., ECCV 2022) on the exact patch engine of `evaluate`.  Everything is a uint8 volume [T,H,W,3]; an image is
+# the volume with T = 1.  Coarse to fine over a spatial pyramid of the real volume (T is kept; a spatio-temporal pyramid is
+# not built), every level repeats one step: search, for each patch of the current guess, the key patch that minimises
+# d2 / (alpha_abs + the key's distance to ITS nearest guess patch) (the completeness normalisation: key patches the guess
+# does not use yet become cheap), then vote the value patches of the winners into the next guess.
+def generate_patchnn_parser():
+    def alpha(s):
+        v = float(s)
+        if not v > 0:
+            raise argparse.ArgumentTypeError("--alpha must be > 0 (inf: no completeness normalisation)")
+        return v
+    p = argparse.ArgumentParser(prog="python -m hp_vae_gan_amd.generate_patchnn",
+                                description="Training-free samples of one clip / image by coarse-to-fine patch nearest "
+                                "neighbours (GPNN / VGPNN) on the exact patch engine of `evaluate`.")
+    p.add_argument('--exp-dir', default=None, help='experiment_<n> directory: the real volume is the one `evaluate` compares against')
+    p.add_argument('--video-path', default=None, help='a clip taken as it is (.npy [N,H,W,3] uint8 or a frame directory); needs --out')
+    p.add_argument('--image-path', default=None, help='an image taken as it is (.npy [H,W,3] uint8 or an image file); needs --out')
+    p.add_argument('--out', default=None, help='output directory (default: <exp-dir>/eval/samples_patchnn)')
+    p.add_argument('--num-samples', type=int, default=8, help='number of samples')
+    p.add_argument('--seed', type=int, default=0, help='sample i draws its noise under seed + i')
+    p.add_argument('--patch', type=int, nargs=3, default=None, metavar=('T', 'H', 'W'), help='patch (default 3 7 7, images 1 7 7)')
+    p.add_argument('--ratio', type=float, default=0.75, help='size ratio between two levels of the pyramid')
+    p.add_argument('--min-size', type=int, default=16, help='the coarsest level keeps min(H, W) >= this')
+    p.add_argument('--iters', type=int, default=10, help='refine steps per level')
+    p.add_argument('--alpha', type=alpha, default=0.005, help='completeness normalisation, in units of D * 255^2 (the unit of '
+                   '`evaluate`\'s coherence); inf turns it off')
+    p.add_argument('--noise', type=float, default=0.75, help='standard deviation, in units of 255, of the noise added to the coarsest guess')
+    p.add_argument('--size', type=int, nargs=3, default=None, metavar=('T', 'H', 'W'), help='size of the samples (default: the real '
+                   'volume\'s; another size retargets)')
+    p.add_argument('--save-levels', action='store_true', help='also write levels.npz: the real pyramid (level_<l>) and the blurred '
+                   'keys of every level above the coarsest (keys_<l>)')
+    return p
+
+
+def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7)):
+    """[(T, H, W)] of the pyramid of a (T, H, W) volume from coarse to fine: level l of L has (H, W) scaled by ratio^(L-1-l) and
+    rounded (halves up), the finest is the volume itself and T is kept.  L is the largest count whose coarsest level has
+    min(H, W) >= min_size (at least 1).  Refuses a coarsest level smaller than the patch.  Host only."""
+    T, H, W = (int(e) for e in shape)
+    ratio = float(ratio)
+    if not 0.0 < ratio < 1.0:
+        raise ValueError("patchnn_pyramid_sizes: ratio must lie in (0, 1), got %r" % (ratio,))
+    if min(T, H, W) < 1:
+        raise ValueError("patchnn_pyramid_sizes: bad volume %s" % ((T, H, W),))
+
+    def at(k):
+        return T, int(math.floor(H * ratio ** k + 0.5)), int(math.floor(W * ratio ** k + 0.5))
+    L = 1
+    while min(at(L)[1:]) >= max(int(min_size), 1):
+        L += 1
+    sizes = [at(L - 1 - l) for l in range(L)]
+    if any(s < p for s, p in zip(sizes[0], patch)):
+        raise ValueError("patchnn_pyramid_sizes: the coarsest level %s is smaller than the patch %s (raise min_size)"
+                         % (sizes[0], tuple(patch)))
+    return sizes
+
+
+def _resize_u8(vol, size):
+    """uint8 [T,H,W,3] -> uint8 [*size, 3]: the trilinear align-corners resize (ops.UpsampleAC, fp32), rounded and clamped."""
+    size = tuple(int(e) for e in size)
+    if tuple(vol.shape[:3]) == size:
+        return vol.contiguous()
+    x = vol.permute(3, 0, 1, 2)[None].to(torch.float32).contiguous()
+    with torch.no_grad():
+        y = ops.UpsampleAC.apply(x, size, None, 0.0)
+    return torch.round(y).clamp_(0, 255).to(torch.uint8)[0].permute(1, 2, 3, 0).contiguous()
+
+
+def patchnn_real_levels(real, sizes):
+    """(levels, keys) of the real volume [T,H,W,3]: levels[l] is the full-size volume resized to sizes[l]; keys[l] (l > 0) is
+    levels[l-1] resized to sizes[l], the blurred keys of the first step of level l (keys[0] is levels[0])."""
+    levels = [_resize_u8(real, s) for s in sizes]
+    keys = [levels[0]] + [_resize_u8(levels[l - 1], sizes[l]) for l in range(1, len(sizes))]
+    return levels, keys
+
+
+def patchnn_weights(m, alpha_abs):
+    """w = 1 / (float32(m) + float32(alpha_abs)) for the int32 distances m: one fp32 add and one correctly rounded fp32 divide
+    per key patch (the generator's results are defined bit for bit, so this must equal numpy's float32 arithmetic)."""
+    return 1.0 / (m.to(torch.float32) + torch.tensor(alpha_abs, dtype=torch.float32, device=m.device))
+
+
+def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False):
+    """One GPNN step on uint8 volumes (or images): m = for every key patch the distance to its nearest query patch,
+    w = 1 / (float32(m) + float32(alpha_abs)), nn = the weighted nearest key of every query patch, result = the vote of the
+    value patches nn (keys and values share one grid) with the query as fallback.  alpha_abs = inf: the plain nearest key,
+    one search.  return_score: also the mean of the minimised quantity (d2 * w; d2 for inf)."""
+    if math.isinf(alpha_abs):
+        score, nn = ops.patch_nn(query, keys, patch)
+    else:
+        m, _ = ops.patch_nn(keys, query, patch)
+        score, nn = ops.patch_nn_weighted(query, keys, patchnn_weights(m, alpha_abs), patch)
+    out = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query)
+    if return_score:
+        return out, float(score.to(torch.float64).mean())
+    return out
+
+
+def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, alpha=0.005, seed=0, index=0,
+                       pyramid=None):
+    """One sample of the uint8 device volume `real` ([T,H,W,3]; images [H,W,3]) -> (sample, mean final score).  size: the
+    sample's (T, H, W) (default real's).  The coarsest guess is real level 0 (resized to the sample's coarsest size) plus
+    noise * 255 * N(0, 1) drawn under torch.manual_seed(seed + index); level 0 runs `iters` steps with keys = values = real
+    level 0; level l > 0 starts from the previous result resized, runs one step with the blurred keys (real level l-1 resized
+    to level l) and values real level l, then iters - 1 steps with keys = values = real level l.  pyramid: a
+    (sizes, levels, keys) triple of patchnn_pyramid_sizes / patchnn_real_levels to reuse between samples."""
+    image = real.dim() == 3
+    vol = real[None] if image else real
+    patch = tuple(patch) if patch else default_patch(not image)
+    if pyramid is None:
+        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
+        pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+    sizes, levels, keys = pyramid
+    L = len(sizes)
+    if size is None or tuple(size) == tuple(vol.shape[:3]):
+        qsizes = sizes
+    else:
+        St, Sh, Sw = (int(e) for e in size)
+        qsizes = [(St, int(math.floor(Sh * ratio ** (L - 1 - l) + 0.5)), int(math.floor(Sw * ratio ** (L - 1 - l) + 0.5)))
+                  for l in range(L)]
+        if any(s < p for s, p in zip(qsizes[0], patch)):
+            raise ValueError("patchnn_synthesize: the sample's coarsest level %s is smaller than the patch %s" % (qsizes[0], patch))
+    alpha_abs = float(alpha) * 3 * patch[0] * patch[1] * patch[2] * 255 * 255
+    iters = max(int(iters), 1)
+    q = _resize_u8(levels[0], qsizes[0])
+    if noise:
+        torch.manual_seed(int(seed) + int(index))
+        with ops.noise_stream(q.device):
+            z = ops.normal_(torch.empty(q.shape, dtype=torch.float32, device=q.device))
+        q = torch.round(q.to(torch.float32) + (float(noise) * 255.0) * z).clamp_(0, 255).to(torch.uint8)
+    score = None
+    for l in range(L):
+        if l > 0:
+            q = _resize_u8(q, qsizes[l])
+        for it in range(iters):
+            k = keys[l] if (l > 0 and it == 0) else levels[l]
+            q, score = patchnn_refine(q, k, levels[l], patch, alpha_abs, return_score=True)
+    return (q[0] if image else q), score
+
+
+def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
+                     min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False):
+    """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
+    patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample)."""
+    given = [a for a in (exp_dir, video_path, image_path) if a is not None]
+    if len(given) != 1:
+        raise SystemExit("generate_patchnn: give exactly one of --exp-dir, --video-path and --image-path")
+    if exp_dir is None and out is None:
+        raise SystemExit("generate_patchnn: --video-path / --image-path need --out")
+    device = gpu_device()
+    fps = 10
+    if exp_dir is not None:
+        opt = load_opt(exp_dir)
+        real = real_volume(opt, None, device)
+        if opt.dims == 3:
+            fps = hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[0]
+        out = out or os.path.join(exp_dir, 'eval', 'samples_patchnn')
+    else:
+        real = load_u8_frames(video_path or image_path, device, image_path is not None,
+                              "generate_patchnn: the input must be uint8 [N,H,W,3] or [H,W,3]", ranks=(3, 4))
+        if video_path is not None and real.dim() == 3:
+            real = real[None]   # one frame given as a clip
+    image = real.dim() == 3
+    vol = real[None] if image else real
+    patch = tuple(patch) if patch else default_patch(not image)
+    size = tuple(size) if size else tuple(vol.shape[:3])
+    try:
+        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
+    except ValueError as e:
+        raise SystemExit("generate_patchnn: {}".format(e))
+    if image and size[0] != 1:
+        raise SystemExit("generate_patchnn: an image's --size has T = 1")
+    pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+    os.makedirs(out, exist_ok=True)
+    if save_levels:
+        np.savez(os.path.join(out, 'levels.npz'), **{"level_%d" % l: v.cpu().numpy() for l, v in enumerate(pyramid[1])},
+                 **{"keys_%d" % l: v.cpu().numpy() for l, v in enumerate(pyramid[2]) if l > 0})
+    samples, seconds, scores = [], [], []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for i in range(num_samples):
+        e0.record()
+        try:
+            smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid)
+        except ValueError as e:
+            raise SystemExit("generate_patchnn: {}".format(e))
+        e1.record()
+        e1.synchronize()
+        seconds.append(e0.elapsed_time(e1) / 1e3)
+        scores.append(score)
+        samples.append((smp[0] if image else smp).cpu().numpy())
+    arr = np.stack(samples)
+    write_samples(out, arr, fps)
+    info = {"input": os.path.abspath(exp_dir or video_path or image_path), "real_shape": list(vol.shape[:3]), "size": list(size),
+            "num_samples": int(num_samples), "seed": int(seed), "patch": list(patch), "ratio": float(ratio), "min_size": int(min_size),
+            "iters": int(iters), "alpha": (float(alpha) if math.isfinite(alpha) else "inf"), "noise": float(noise),
+            "level_sizes": [list(s) for s in sizes], "seconds_per_sample": seconds, "final_score_per_sample": scores,
+            "final_score": "mean over the sample's patches of the last step's minimum: d2 / (alpha D 255^2 + the key's distance "
+                           "to its nearest sample patch); plain d2 for alpha = inf"}
+    with open(os.path.join(out, 'patchnn.json'), 'w') as f:
+        json.dump(info, f, indent=1, sort_keys=True)
+    print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
+        len(arr), tuple(arr.shape[1:]), len(sizes), sum(seconds) / max(len(seconds), 1), out))
+    return arr
 
 
 def main(argv=None):
-    return generate_patchnn_main(argv)
+    a = generate_patchnn_parser().parse_args(argv)
+    generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
+                     a.alpha, a.noise, a.size, a.save_levels)
+    return 0
 
 
 if __name__ == "__main__":
-    main_guard(main)
+    sys.exit(main())

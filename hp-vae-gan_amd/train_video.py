@@ -1,6 +1,9 @@
 """`python -m hp_vae_gan_amd.train_video --video-path ... --checkname ...`: train HP-VAE-GAN on one video (the reference's
-train_video.py).  Flags, run directory, scalars, previews and the resume rule: see programs.py."""
-from .programs import main_guard, train_main
+train_video.py).  The trainer is programs.Program, shared with train_image: flags, run directory, scalars, previews and
+the resume rule are described in programs.py."""
+import sys
+
+from .programs import train_main
 
 
 def main(argv=None):
@@ -8,4 +11,4 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
-    main_guard(main)
+    sys.exit(main())

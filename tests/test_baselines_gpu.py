@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from helpers import NoiseFeed, hip_opt, load_golden  # noqa: E402
-from hp_vae_gan_amd import datasets, ops, programs, telemetry  # noqa: E402
+from hp_vae_gan_amd import datasets, ops, telemetry, train_video_baselines  # noqa: E402
 from hp_vae_gan_amd import train as hp_train  # noqa: E402
 from hp_vae_gan_amd import utils as hu  # noqa: E402
 from hp_vae_gan_amd.modules import _nets, networks_3d  # noqa: E402
@@ -233,7 +233,7 @@ def test_program_defaults_under_replay(tmp_path):
     np.save(str(tmp_path / "clip.npy"), _clip())
     ops._rng_states.clear()
     torch.manual_seed(0)
-    opt = programs.build_baseline_parser().parse_args(["--video-path", str(tmp_path / "clip.npy")] + SMALL)
+    opt = train_video_baselines.build_baseline_parser().parse_args(["--video-path", str(tmp_path / "clip.npy")] + SMALL)
     assert (opt.generator, opt.discriminator) == ("GeneratorCSG", "WDiscriminator3D")
     opt.device, opt.dims, opt.hip_graph = DEV, 3, True
     opt.noise_amp_init, opt.scale_factor_init = opt.noise_amp, opt.scale_factor
@@ -252,7 +252,7 @@ def test_program_defaults_under_replay(tmp_path):
         opt.fps, opt.td, opt.fps_index = hu.get_fps_td_by_index(s, opt)
         ds.generate_frames(s)
         if s == 0:
-            opt.Z_init = hu.generate_noise(size=programs.z_init_shape(opt), device=DEV)
+            opt.Z_init = hu.generate_noise(size=train_video_baselines.z_init_shape(opt), device=DEV)
         items = [ds[i] for i in range(opt.batch_size)]
         data = [tuple(torch.stack([it[j] for it in items]) for j in range(2))] if s > 0 else [torch.stack(items)]
         netD = networks_3d.WDiscriminator3D(opt).to(DEV)

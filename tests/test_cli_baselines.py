@@ -11,7 +11,7 @@ import types
 
 import pytest
 
-from hp_vae_gan_amd import programs
+from hp_vae_gan_amd import programs, train_video_baselines
 from hp_vae_gan_amd import train as hp_train
 from hp_vae_gan_amd import utils as hu
 
@@ -27,7 +27,7 @@ def _actions(parser):
 def test_parser_matches_reference_flags():
     with open(os.path.join(GOLDEN, "cli_flags_baselines.json")) as f:
         ref = json.load(f)["train_video_baselines"]
-    acts = _actions(programs.build_baseline_parser())
+    acts = _actions(train_video_baselines.build_baseline_parser())
     assert set(acts) == {e["dest"] for e in ref} | set(EXTRA)
     for e in ref:
         a = acts[e["dest"]]
@@ -52,8 +52,8 @@ def test_parser_matches_reference_flags():
 
 
 def _opt(argv=()):
-    opt = programs.build_baseline_parser().parse_args(["--video-path", "clip.npy", "--min-size", "16", "--max-size", "40",
-                                                       "--img-size", "40"] + list(argv))
+    opt = train_video_baselines.build_baseline_parser().parse_args(["--video-path", "clip.npy", "--min-size", "16",
+                                                                    "--max-size", "40", "--img-size", "40"] + list(argv))
     opt.noise_amp_init = opt.noise_amp
     opt.scale_factor_init = opt.scale_factor
     hu.adjust_scales2image(opt.img_size, opt)
@@ -70,34 +70,34 @@ def test_z_init_shape_fresh_and_resumed():
     w0 = hu.get_scales_by_index(0, opt.scale_factor, S, opt.img_size)
     # a fresh run draws it at scale 0: exactly level 0's volume
     opt.td = hu.get_fps_td_by_index(0, opt)[1]
-    assert programs.z_init_shape(opt) == [3, 3] + hu.images.level_shape_3d(0, opt)
+    assert train_video_baselines.z_init_shape(opt) == [3, 3] + hu.images.level_shape_3d(0, opt)
     # a resume at the last scale draws it there: level 0's height and width, the resumed scale's time depth
     opt.td = hu.get_fps_td_by_index(S, opt)[1]
     assert opt.td != hu.images.level_shape_3d(0, opt)[0]
-    assert programs.z_init_shape(opt) == [3, 3, opt.td, int(w0 * opt.ar), w0]
+    assert train_video_baselines.z_init_shape(opt) == [3, 3, opt.td, int(w0 * opt.ar), w0]
 
 
 def test_netD_warm_start_directory():
     fresh = types.SimpleNamespace(netG="", resumed_idx=-1, scale_idx=0)
-    assert programs.baseline_netD_dir(fresh, "exp") is None
+    assert train_video_baselines.baseline_netD_dir(fresh, "exp") is None
     fresh.scale_idx = 3
-    assert programs.baseline_netD_dir(fresh, "exp") == "exp"
+    assert train_video_baselines.baseline_netD_dir(fresh, "exp") == "exp"
     resumed = types.SimpleNamespace(netG="old/netG.pth", resume_dir="old", resumed_idx=4, scale_idx=4)
-    assert programs.baseline_netD_dir(resumed, "exp") == "old"     # the resumed scale: the resume directory
+    assert train_video_baselines.baseline_netD_dir(resumed, "exp") == "old"     # the resumed scale: the resume directory
     resumed.scale_idx = 5
-    assert programs.baseline_netD_dir(resumed, "exp") == "exp"     # later scales: this run's own
+    assert train_video_baselines.baseline_netD_dir(resumed, "exp") == "exp"     # later scales: this run's own
     resumed.resumed_idx, resumed.scale_idx = 0, 0
-    assert programs.baseline_netD_dir(resumed, "exp") is None
+    assert train_video_baselines.baseline_netD_dir(resumed, "exp") is None
 
 
 def test_loss_log_columns_and_tags():
     assert hp_train.baseline_loss_log_columns(0.0) == ["errD_real", "errD_fake", "gradient_penalty", "errG"]
     assert hp_train.baseline_loss_log_columns(10.0) == ["errD_real", "errD_fake", "gradient_penalty", "errG", "rec_loss"]
-    tags = programs.BASELINE_TAGS
+    tags = train_video_baselines.BASELINE_TAGS
     assert set(hp_train.baseline_loss_log_columns(1.0)) == set(tags)
     assert {tags[k] for k in ("errG", "errD_fake", "errD_real", "rec_loss")} == {"errG", "errD_fake", "errD_real", "rec_loss"}
     assert tags["gradient_penalty"] == "gradient_penalty"
-    assert programs.BaselineProgram.tags is tags and programs.Program.tags is programs.TAGS
+    assert train_video_baselines.BaselineProgram.tags is tags and programs.Program.tags is programs.TAGS
     assert programs.TAGS["rec_loss"] == "rec loss"                 # train_video's tag is unchanged
 
 
@@ -120,6 +120,6 @@ def test_cli_refusals(tmp_path):
 
 @pytest.mark.parametrize("alpha", [0.0, 10.0])
 def test_noise_amp_scalar_only_with_reconstruction(alpha):
-    prog = programs.BaselineProgram.__new__(programs.BaselineProgram)
+    prog = train_video_baselines.BaselineProgram.__new__(train_video_baselines.BaselineProgram)
     prog.opt = types.SimpleNamespace(alpha=alpha)
     assert prog.logs_noise_amp() == (alpha > 0)

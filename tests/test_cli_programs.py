@@ -2,6 +2,7 @@
 
 The parsers are held to tests/golden/cli_flags.json, which tests/golden/make_cli_flags.py reads from the reference's two
 programs with `ast` (names, types, defaults, nargs, actions and `required` only)."""
+import ast
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from hp_vae_gan_amd import programs, telemetry
+from hp_vae_gan_amd import programs, telemetry, train_video_baselines
 from hp_vae_gan_amd import train as hp_train
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,6 +46,22 @@ def test_parser_matches_reference_flags(kind):
     for dest, default in EXTRA[kind].items():
         assert acts[dest].default == default
     assert acts["no_hip_graph"].const is True
+
+
+# the flags both trainer parsers hold differ only here: the generator's default (golden) and four help texts
+FORKED_HELP = {"generator", "discriminator", "mode", "visualize"}
+
+
+def test_shared_flags_are_not_forked():
+    video, base = _actions(programs.build_parser("video")), _actions(train_video_baselines.build_baseline_parser())
+    shared = set(video) & set(base)
+    assert len(shared) >= 35 and FORKED_HELP <= shared
+    for dest in sorted(shared):
+        a, b = video[dest], base[dest]
+        assert (a.type, a.nargs) == (b.type, b.nargs), dest
+        assert a.default == b.default or dest == "generator", dest
+        assert (a.help == b.help) == (dest not in FORKED_HELP), dest
+    assert (video["generator"].default, base["generator"].default) == ("GeneratorHPVAEGAN", "GeneratorCSG")   # the goldens'
 
 
 def test_experiment_numbering(tmp_path):
@@ -124,3 +141,23 @@ def test_cli_refusals(tmp_path):
     r = _run(["hp_vae_gan_amd.train_video"], str(tmp_path))
     assert r.returncode == 2 and "--video-path" in r.stderr
     assert not os.path.exists(tmp_path / "run")
+
+
+# module -> flags that no other program holds together (train_video and generate have no flag to themselves)
+ONLY = {"train_video": ("--vae-levels", "--sampling-rates"), "train_image": ("--tag",), "train_video_baselines": ("--Dsteps",),
+        "generate": ("--num-samples", "--batch-size"), "evaluate": ("--swd-seed",), "generate_patchnn": ("--save-levels",)}
+
+
+@pytest.mark.parametrize("name", sorted(ONLY))
+def test_every_program_module_runs_alone(name, tmp_path):
+    """`python -m` loads the module as __main__ in a fresh process: it must import on its own, without another program module,
+    and show its own flags."""
+    r = _run(["hp_vae_gan_amd." + name, "--help"], str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "hp_vae_gan_amd." + name + " " in r.stdout
+    assert all(flag in r.stdout for flag in ONLY[name]), r.stdout
+    for other, flags in ONLY.items():
+        assert other == name or not all(flag in r.stdout for flag in flags), other
+    with open(os.path.join(ROOT, "hp-vae-gan_amd", name + ".py")) as f:
+        froms = [n for n in ast.walk(ast.parse(f.read())) if isinstance(n, ast.ImportFrom)]
+    assert not ({n.module for n in froms} | {a.name for n in froms for a in n.names}) & (set(ONLY) - {name})

@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from test_evaluate_gpu import KEYS, _clip  # noqa: E402
 from test_patchswd import ref_hist, ref_num  # noqa: E402
 
-from hp_vae_gan_amd import programs  # noqa: E402
+from hp_vae_gan_amd import evaluate  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -37,11 +37,11 @@ def test_swd_keys_scores_and_zero_for_a_copy(tmp_path):
     assert all(set(p) == {"coherence", "completeness", "nn_unique_frac", "swd"} for p in m["per_sample"])
     assert (m["swd_directions"], m["swd_seed"]) == (16, 3) and m["swd_seconds"] > 0
     assert (m["Nq"], m["Nr"], m["D"]) == (4 * 14 * 18, 4 * 14 * 18, 441)
-    dirs = programs.swd_directions(16, 441, 3)
+    dirs = evaluate.swd_directions(16, 441, 3)
     hr, Nr = ref_hist(real, (3, 7, 7), dirs)
     for s, p in zip(S, m["per_sample"]):
         hs, Ns = ref_hist(s, (3, 7, 7), dirs)
-        assert p["swd"] == programs.swd_score(ref_num(hs, Ns, hr, Nr), Ns, Nr, dirs)
+        assert p["swd"] == evaluate.swd_score(ref_num(hs, Ns, hr, Nr), Ns, Nr, dirs)
     assert m["per_sample"][0]["swd"] == 0.0 and m["per_sample"][1]["swd"] > 0.0
     assert m["swd"] == (m["per_sample"][0]["swd"] + m["per_sample"][1]["swd"]) / 2
     line = r.stdout.strip().splitlines()

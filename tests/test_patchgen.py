@@ -1,5 +1,5 @@
 """The two kernels of the patch nearest-neighbour generator (hpvg_patchnn_weighted_u8 / ops.patch_nn_weighted and
-hpvg_patch_vote_u8 / ops.patch_vote), one refine step (programs.patchnn_refine) and the host-side pieces of generate_patchnn,
+hpvg_patch_vote_u8 / ops.patch_vote), one refine step (generate_patchnn.patchnn_refine) and the host-side pieces of generate_patchnn,
 against numpy written from the definitions.  Every comparison is torch.equal / ==; there is no tolerance anywhere.
 
 Weighted search: the float64 distance matrix of test_patchnn's yardstick (exact integers) -> float32 (exact below 2^24, round to
@@ -20,7 +20,7 @@ from numpy.lib.stride_tricks import sliding_window_view
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
-from hp_vae_gan_amd import ops, programs  # noqa: E402
+from hp_vae_gan_amd import generate_patchnn, ops  # noqa: E402
 from test_patchnn import BAD, _case, _patches, _rand, brute  # noqa: E402
 
 ERR_ARG, ERR_WORKSPACE = -1, -2
@@ -311,12 +311,12 @@ def test_refine_step_equals_numpy_composition(alpha):
         assert (nn != brute(query, keys, patch)[1]).any()
         # the two intermediate results, bit for bit: the device's divide is the correctly rounded one, and so are the winners
         md = ops.patch_nn(_dev(keys), _dev(query), patch)[0]
-        wd = programs.patchnn_weights(md, alpha_abs)
+        wd = generate_patchnn.patchnn_weights(md, alpha_abs)
         assert wd.dtype == torch.float32 and torch.equal(wd.cpu().view(torch.int32), torch.from_numpy(w.view(np.int32)))
         nnd = ops.patch_nn_weighted(_dev(query), _dev(keys), wd, patch)[1]
         assert torch.equal(nnd.cpu().to(torch.int64), torch.from_numpy(nn))
     want = vote_ref(values, nn, patch, query)[0]
-    got = programs.patchnn_refine(_dev(query), _dev(keys), _dev(values), patch, alpha_abs)
+    got = generate_patchnn.patchnn_refine(_dev(query), _dev(keys), _dev(values), patch, alpha_abs)
     assert got.dtype == torch.uint8 and np.array_equal(got.cpu().numpy(), want)
 
 
@@ -375,7 +375,7 @@ def test_vote_counts_match_a_numpy_cover():
 
 
 def test_generate_patchnn_parser_defaults_and_arities():
-    p = programs.generate_patchnn_parser()
+    p = generate_patchnn.generate_patchnn_parser()
     a = p.parse_args(["--exp-dir", "e"])
     assert (a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters, a.alpha, a.noise,
             a.size) == ("e", None, None, None, 8, 0, None, 0.75, 16, 10, 0.005, 0.75, None)
@@ -390,7 +390,7 @@ def test_generate_patchnn_parser_defaults_and_arities():
 
 
 def test_pyramid_sizes_by_hand():
-    f = programs.patchnn_pyramid_sizes
+    f = generate_patchnn.patchnn_pyramid_sizes
     # 144 * 0.75^7 = 19.2 >= 16 > 144 * 0.75^8 = 14.4: eight levels.  60.75 -> 61, 45.5625 -> 46, 34.17 -> 34, 25.6 -> 26
     assert f((13, 144, 256), 0.75, 16) == [(13, 19, 34), (13, 26, 46), (13, 34, 61), (13, 46, 81), (13, 61, 108), (13, 81, 144),
                                            (13, 108, 192), (13, 144, 256)]
@@ -402,7 +402,7 @@ def test_pyramid_sizes_by_hand():
 
 
 def test_pyramid_sizes_refuse_a_patch_larger_than_the_coarsest_level():
-    f = programs.patchnn_pyramid_sizes
+    f = generate_patchnn.patchnn_pyramid_sizes
     with pytest.raises(ValueError, match="smaller than the patch"):
         f((13, 144, 256), 0.75, 4)            # coarsest 5 x 8 against 7 x 7
     with pytest.raises(ValueError, match="smaller than the patch"):
@@ -416,8 +416,8 @@ def test_pyramid_sizes_refuse_a_patch_larger_than_the_coarsest_level():
 
 def test_generate_patchnn_needs_one_input_and_an_out():
     with pytest.raises(SystemExit, match="exactly one"):
-        programs.generate_patchnn()
+        generate_patchnn.generate_patchnn()
     with pytest.raises(SystemExit, match="exactly one"):
-        programs.generate_patchnn(exp_dir="e", video_path="c.npy")
+        generate_patchnn.generate_patchnn(exp_dir="e", video_path="c.npy")
     with pytest.raises(SystemExit, match="need --out"):
-        programs.generate_patchnn(video_path="c.npy")
+        generate_patchnn.generate_patchnn(video_path="c.npy")

@@ -11,7 +11,7 @@ from numpy.lib.stride_tricks import sliding_window_view
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from hp_vae_gan_amd import programs  # noqa: E402
+from hp_vae_gan_amd import generate_patchnn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SHAPE = (6, 40, 48)
@@ -95,7 +95,7 @@ def test_retargeting_files_and_evaluate(tmp_path):
     out = os.path.join(tmp, "r")
     with open(os.path.join(out, "patchnn.json")) as f:
         info = json.load(f)
-    want = programs.patchnn_pyramid_sizes(SHAPE, 0.75, 30, (3, 7, 7))
+    want = generate_patchnn.patchnn_pyramid_sizes(SHAPE, 0.75, 30, (3, 7, 7))
     assert want == [(6, 30, 36), (6, 40, 48)]
     assert info["level_sizes"] == [list(v) for v in want]
     assert info["size"] == [6, 40, 64] and info["real_shape"] == list(SHAPE) and info["patch"] == [3, 7, 7]

@@ -17,7 +17,7 @@ import torch
 from numpy.lib.stride_tricks import sliding_window_view
 
 from hp_vae_gan_amd import lib as hplib
-from hp_vae_gan_amd import ops, programs
+from hp_vae_gan_amd import evaluate, ops
 
 ERR_ARG = -1
 I3 = ctypes.c_int * 3
@@ -244,7 +244,7 @@ def test_largest_allowed_patch_is_accepted():
 
 # ------------------------------------------------------------------------------------------------------ evaluate, host side
 def test_evaluate_parser_defaults_and_patch_arity():
-    p = programs.evaluate_parser()
+    p = evaluate.evaluate_parser()
     a = p.parse_args(["--exp-dir", "e"])
     assert (a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out) == ("e", None, None, None, [1, 1, 1], None, None)
     a = p.parse_args(["--samples", "s.npy", "--real", "r.npy", "--patch", "1", "5", "5", "--stride", "1", "2", "2", "--max-samples", "3"])
@@ -256,25 +256,25 @@ def test_evaluate_parser_defaults_and_patch_arity():
 
 def test_metric_arithmetic():
     D = 441
-    assert programs.patch_score(torch.zeros(4, 5, dtype=torch.int32), D) == 0.0
-    assert programs.patch_score(torch.full((2, 3, 4), D * 255 * 255, dtype=torch.int32), D) == 1.0
-    assert programs.patch_score(torch.tensor([0, D * 255 * 255], dtype=torch.int32), D) == 0.5
+    assert evaluate.patch_score(torch.zeros(4, 5, dtype=torch.int32), D) == 0.0
+    assert evaluate.patch_score(torch.full((2, 3, 4), D * 255 * 255, dtype=torch.int32), D) == 1.0
+    assert evaluate.patch_score(torch.tensor([0, D * 255 * 255], dtype=torch.int32), D) == 0.5
     # sums past 2^31 stay exact
-    assert programs.patch_score(torch.full((1000,), 118020375, dtype=torch.int32), 1815) == 1.0
+    assert evaluate.patch_score(torch.full((1000,), 118020375, dtype=torch.int32), 1815) == 1.0
     nn = torch.tensor([[0, 3, 3], [7, 7, 0]], dtype=torch.int32)
-    assert programs.nn_unique_frac(nn, 100) == 3 / 6
-    assert programs.nn_unique_frac(nn, 4) == 3 / 4
+    assert evaluate.nn_unique_frac(nn, 100) == 3 / 6
+    assert evaluate.nn_unique_frac(nn, 4) == 3 / 4
     # diversity: two constant samples 10 and 30 -> per-pixel deviation 10; real half 0, half 100 -> deviation 50
     s = torch.stack([torch.full((2, 4, 4, 3), 10, dtype=torch.uint8), torch.full((2, 4, 4, 3), 30, dtype=torch.uint8)])
     real = torch.cat([torch.zeros(3, 4, 2, 3), torch.full((3, 4, 2, 3), 100.0)], 2).to(torch.uint8)
-    assert programs.diversity(s, real) == 0.2   # real is cut to the samples' 2 frames
+    assert evaluate.diversity(s, real) == 0.2   # real is cut to the samples' 2 frames
     # the channel MEAN is what varies: samples that differ only in how a fixed sum is spread over the channels have none
     a = torch.zeros(1, 4, 4, 3, dtype=torch.uint8)
     a[..., 0] = 30
     b = torch.full((1, 4, 4, 3), 10, dtype=torch.uint8)
-    assert programs.diversity(torch.stack([a, b]), real[:1]) == 0.0
-    assert programs.diversity(s[:1], real) is None                      # one sample
-    assert programs.diversity(s, real[:1]) is None                      # real shorter than the samples
-    assert programs.diversity(s, real[:, :3]) is None                   # other H
+    assert evaluate.diversity(torch.stack([a, b]), real[:1]) == 0.0
+    assert evaluate.diversity(s[:1], real) is None                      # one sample
+    assert evaluate.diversity(s, real[:1]) is None                      # real shorter than the samples
+    assert evaluate.diversity(s, real[:, :3]) is None                   # other H
     img = torch.stack([torch.full((4, 4, 3), 10, dtype=torch.uint8), torch.full((4, 4, 3), 30, dtype=torch.uint8)])
-    assert programs.diversity(img, real[0]) == 0.2
+    assert evaluate.diversity(img, real[0]) == 0.2

@@ -22,7 +22,7 @@ from test_patchnn import _case as _nn_case  # noqa: E402
 from test_patchnn import _patches, _rand  # noqa: E402
 
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
-from hp_vae_gan_amd import ops, programs  # noqa: E402
+from hp_vae_gan_amd import evaluate, ops  # noqa: E402
 
 ERR_ARG, ERR_WS = -1, -2
 I3 = ctypes.c_int * 3
@@ -275,12 +275,12 @@ def test_w1_largest_numerator_the_entry_point_accepts():
 
 # ----------------------------------------------------------------------------------------------------------------- host
 def test_swd_directions():
-    a, b, c = programs.swd_directions(16, 441, 3), programs.swd_directions(16, 441, 3), programs.swd_directions(16, 441, 4)
+    a, b, c = evaluate.swd_directions(16, 441, 3), evaluate.swd_directions(16, 441, 3), evaluate.swd_directions(16, 441, 4)
     assert a.dtype == np.int8 and a.shape == (16, 441)
     assert np.array_equal(a, b) and not np.array_equal(a, c)
     assert set(np.unique(a)) == {-1, 0, 1}
     # D = 3: one row in 27 comes out all-zero on the first draw, so 4 000 rows hold some with certainty and they are redrawn
-    d = programs.swd_directions(4000, 3, 0)
+    d = evaluate.swd_directions(4000, 3, 0)
     first = np.random.default_rng(0).integers(-1, 2, size=(4000, 3), dtype=np.int8)
     assert (~first.any(1)).sum() > 50
     assert d.shape == (4000, 3) and d.any(1).all() and set(np.unique(d)) == {-1, 0, 1}
@@ -289,21 +289,21 @@ def test_swd_directions():
 
 def test_swd_score_arithmetic():
     dirs = np.array([[1, 0, 0, 0], [1, -1, 1, -1], [0, 1, 1, 0]], np.int8)   # nnz 1, 4, 2
-    assert programs.swd_score([0, 0, 0], 5, 7, dirs) == 0.0
+    assert evaluate.swd_score([0, 0, 0], 5, 7, dirs) == 0.0
     # W1 = 255 along e_0 alone: black against white is one full intensity range
-    assert programs.swd_score([5 * 7 * 255], 5, 7, dirs[:1]) == 1.0
-    assert programs.swd_score([5 * 7 * 255, 5 * 7 * 255 * 4, 0], 5, 7, dirs) == (1.0 + 2.0 + 0.0) / 3
+    assert evaluate.swd_score([5 * 7 * 255], 5, 7, dirs[:1]) == 1.0
+    assert evaluate.swd_score([5 * 7 * 255, 5 * 7 * 255 * 4, 0], 5, 7, dirs) == (1.0 + 2.0 + 0.0) / 3
     want = ((10 / (5 * 7 * 255)) / 1.0 + (20 / (5 * 7 * 255)) / 2.0 + (30 / (5 * 7 * 255)) / np.sqrt(2.0)) / 3
-    assert programs.swd_score(torch.tensor([10, 20, 30]), 5, 7, dirs) == want
+    assert evaluate.swd_score(torch.tensor([10, 20, 30]), 5, 7, dirs) == want
     # numerators and counts past 2^53 stay exact up to the one rounding of the quotient
     Na = Nb = 2 ** 27
-    assert programs.swd_score([Na * Nb * 768 - 1], Na, Nb, dirs[:1]) == (Na * Nb * 768 - 1) / (Na * Nb * 255)
+    assert evaluate.swd_score([Na * Nb * 768 - 1], Na, Nb, dirs[:1]) == (Na * Nb * 768 - 1) / (Na * Nb * 255)
     with pytest.raises(ValueError):
-        programs.swd_score([1, 2], 5, 7, dirs)
+        evaluate.swd_score([1, 2], 5, 7, dirs)
 
 
 def test_evaluate_parser_swd_flags():
-    p = programs.evaluate_parser()
+    p = evaluate.evaluate_parser()
     a = p.parse_args(["--exp-dir", "e"])
     assert (a.swd, a.swd_seed) == (0, 0)
     a = p.parse_args(["--exp-dir", "e", "--swd", "512", "--swd-seed", "7"])

@@ -1,7 +1,7 @@
 """The patch nearest-neighbour generator's pieces at the benchmarked size - a 13 x 144 x 256 guess against a 13 x 144 x 256 real
 volume, patch 3 x 7 x 7, dense (development tool, not a test): one hpvg_patchnn_u8 direction, one hpvg_patchnn_weighted_u8 pass
 (the C entry points, so the two differ by the kernels alone; ops.patch_nn_weighted's weight check is timed apart), one
-ops.patch_vote, and one full sample of programs.patchnn_synthesize with the program's defaults.  HIP events, warm-up, median
+ops.patch_vote, and one full sample of generate_patchnn.patchnn_synthesize with the program's defaults.  HIP events, warm-up, median
 of `reps`.  With --compare, the `hpvg_patchnn_u8` lines of two tools/perf_patchnn.py outputs (the parent commit's and this
 tree's, taken in the same session) are copied in and the tree's median is checked against the parent's own min-max spread
 widened by 2 %.
@@ -16,7 +16,7 @@ import torch  # noqa: E402
 
 import hp_vae_gan_amd  # noqa: E402,F401
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
-from hp_vae_gan_amd import ops, programs  # noqa: E402
+from hp_vae_gan_amd import generate_patchnn, ops  # noqa: E402
 
 argv = sys.argv[1:]
 compare = None
@@ -113,14 +113,14 @@ votes = float(T * H * W) * PATCH[0] * PATCH[1] * PATCH[2]
 say("(c) ops.patch_vote (%d voxels, up to %d covering patches each): median %.3f ms of %s = %.1f G votes/s"
     % (T * H * W, PATCH[0] * PATCH[1] * PATCH[2], med_v, fmt(ms_v, 3), votes / med_v / 1e6))
 
-sizes = programs.patchnn_pyramid_sizes((T, H, W), 0.75, 16, PATCH)
-pyramid = (sizes,) + programs.patchnn_real_levels(real, sizes)
+sizes = generate_patchnn.patchnn_pyramid_sizes((T, H, W), 0.75, 16, PATCH)
+pyramid = (sizes,) + generate_patchnn.patchnn_real_levels(real, sizes)
 index = [0]
 
 
 def sample():
     index[0] += 1
-    return programs.patchnn_synthesize(real, None, PATCH, 0.75, 16, 10, 0.75, 0.005, 0, index[0], pyramid)
+    return generate_patchnn.patchnn_synthesize(real, None, PATCH, 0.75, 16, 10, 0.75, 0.005, 0, index[0], pyramid)
 
 
 med_s, ms_s = timed(sample, 1, reps)

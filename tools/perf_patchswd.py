@@ -12,7 +12,7 @@ import torch  # noqa: E402
 
 import hp_vae_gan_amd  # noqa: E402,F401
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
-from hp_vae_gan_amd import ops, programs  # noqa: E402
+from hp_vae_gan_amd import evaluate, ops  # noqa: E402
 
 HBM_PEAK = 8.0e12   # bytes / s
 out_path = sys.argv[1] if len(sys.argv) > 1 else None
@@ -57,7 +57,7 @@ sample = torch.randint(0, 256, (T, H, W, 3), dtype=torch.uint8, device=dev)
 real = torch.randint(0, 256, (T, H, W, 3), dtype=torch.uint8, device=dev)
 N, _, D = ops.patch_nn_counts((T, H, W), (T, H, W), PATCH)
 NB = ops.patch_proj_bins(PATCH)
-dirs_np = programs.swd_directions(P, D, 0)
+dirs_np = evaluate.swd_directions(P, D, 0)
 dirs = torch.from_numpy(dirs_np).to(dev)
 I3 = ctypes.c_int * 3
 pa, one = I3(*PATCH), I3(1, 1, 1)
@@ -93,7 +93,7 @@ def w1():
 med_b, all_b = timed(w1, 2, reps)
 say("(b) hpvg_hist_w1_i32 (%d workgroups, %.1f MB of histograms read): median %.3f ms of %s = %.1f GB/s"
     % (P, 2 * P * NB * 4 / 1e6, med_b, ["%.3f" % m for m in all_b], 2 * P * NB * 4 / med_b / 1e6))
-swd = programs.swd_score(num[0].cpu(), N, N, dirs_np)
+swd = evaluate.swd_score(num[0].cpu(), N, N, dirs_np)
 say("    swd of two volumes of random bytes: %.6f" % swd)
 
 Xs, Xr = patch_matrix(sample), patch_matrix(real)

@@ -11,7 +11,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .lib import call, load, ptr, stream
+from .lib import PACK_BATCH_MAX, SN_BATCH_MAX, call, load, ptr, stream
 
 _ws_cache = {}
 _kernel_timer = None
@@ -81,11 +81,17 @@ def workspace(nbytes, device):
     return buf
 
 
+def _scratch(nbytes, device):
+    """The launch arguments (pointer, size) of the shared scratch buffer, grown to `nbytes`; the size is the buffer's own."""
+    ws = workspace(nbytes, device)
+    return ptr(ws), ws.numel()
+
+
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def geom(x, w_shape=None):
+def geom(x):
     """(B, C, T, H, W) of an NCDHW / NCHW activation."""
     if x.dim() == 5:
         B, C, T, H, W = x.shape
@@ -160,9 +166,6 @@ def pack_weight(w, flip, geom_k=None):
     return wp
 
 
-PACK_BATCH_MAX = 16
-
-
 def prepack_weights(ws, flips=(False, True), geom_k=None):
     """Pack several weights of one square layer shape (C -> C, C > 4) in ONE launch and leave the results in the pack cache,
     where the convs that follow find them (a discriminator forward packs its six spectral-norm weights twice each - forward
@@ -225,7 +228,7 @@ def conv_fwd_raw(x, w, bias, out_lrelu=False, flip=False, in_affine=None, in_lre
         var = "pro" if in_affine is not None else ("mask" if (out_mask is not None or mask_bits is not None) else ("bits" if want_bits else "plain"))
         timed = _kernel_timer.begin({"op": "conv", "Cin": cin_k, "Cout": cout_k, "KT": KT, "flip": flip, "var": var})
     nws = call("hpvg_conv_fwd_ws_bytes", B, cin_k, cout_k, T, H, W, KT)
-    ws = workspace(nws, x.device) if nws else None
+    ws = _scratch(nws, x.device) if nws else (None, 0)   # no workspace: NULL, 0 (one workgroup per tile)
     if out_mask is not None and tuple(out_mask.shape) != tuple(shape):
         raise RuntimeError("conv: out_mask has shape %s, the output %s" % (tuple(out_mask.shape), tuple(shape)))
     bits = None
@@ -234,12 +237,11 @@ def conv_fwd_raw(x, w, bias, out_lrelu=False, flip=False, in_affine=None, in_lre
             bits = torch.empty(call("hpvg_conv_mask_words", B, cout_k, T, H, W), dtype=torch.int32, device=x.device)
         if mask_bits is not None and mask_bits.numel() != call("hpvg_conv_mask_words", B, cout_k, T, H, W):
             raise RuntimeError("conv: mask_bits has %d words, the output needs %d" % (mask_bits.numel(), call("hpvg_conv_mask_words", B, cout_k, T, H, W)))
-        call("hpvg_conv_fwd_bits_f32", ptr(x), ptr(wp), ptr(bias), ptr(y), 1 if out_lrelu else 0, ptr(mask_bits), ptr(bits), ptr(ws),
-             ctypes.c_size_t(ws.numel() if ws is not None else 0), B, cin_k, cout_k, T, H, W, KT, stream())
+        call("hpvg_conv_fwd_bits_f32", ptr(x), ptr(wp), ptr(bias), ptr(y), 1 if out_lrelu else 0, ptr(mask_bits), ptr(bits), *ws,
+             B, cin_k, cout_k, T, H, W, KT, stream())
     else:
         call("hpvg_conv_fwd_f32", ptr(x), ptr(wp), ptr(bias), ptr(sc), ptr(sh), 1 if in_lrelu else 0, ptr(y),
-             1 if out_lrelu else 0, ptr(_c(out_mask)) if out_mask is not None else None, ptr(ws),
-             ctypes.c_size_t(ws.numel() if ws is not None else 0), B, cin_k, cout_k, T, H, W, KT, stream())
+             1 if out_lrelu else 0, ptr(_c(out_mask)) if out_mask is not None else None, *ws, B, cin_k, cout_k, T, H, W, KT, stream())
     if timed is not None:
         _kernel_timer.end(timed, (B, cin_k, cout_k, T, H, W))
     return (y, bits) if want_bits else y
@@ -274,12 +276,11 @@ def conv_bwd_weight_raw(dy, x, w_shape, into=None):
     KT = _kt(w_shape)
     if (Co, Ci) != (w_shape[0], w_shape[1]):
         raise RuntimeError("conv_bwd_weight: channel mismatch")
-    nbytes = call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT)
-    ws = workspace(nbytes, dy.device)
+    ws = _scratch(call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT), dy.device)
     dw = into if into is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=dy.device)
     timed = _kernel_timer.begin({"op": "wgrad", "Cin": Ci, "Cout": Co, "KT": KT, "bias": False}) if _kernel_timer is not None else None
-    call("hpvg_conv_bwd_weight_f32", ptr(dy), ptr(x), None, None, 0, ptr(dw), 1 if into is not None else 0, ptr(ws),
-         ctypes.c_size_t(ws.numel()), B, Ci, Co, T, H, W, KT, stream())
+    call("hpvg_conv_bwd_weight_f32", ptr(dy), ptr(x), None, None, 0, ptr(dw), 1 if into is not None else 0, *ws, B, Ci, Co, T, H, W, KT,
+         stream())
     if timed is not None:
         _kernel_timer.end(timed, (B, Ci, Co, T, H, W))
     return None if into is not None else dw
@@ -295,11 +296,9 @@ def conv_bwd_weight_bias_raw(dy, x, w_shape, into_w, into_b):
     KT = _kt(w_shape)
     if load().hpvg_conv_bwd_weight_fuses_bias(B, Ci, Co, T, H, W, KT) != 1:
         return False
-    nbytes = call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT)
-    ws = workspace(nbytes, dy.device)
+    ws = _scratch(call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT), dy.device)
     timed = _kernel_timer.begin({"op": "wgrad", "Cin": Ci, "Cout": Co, "KT": KT, "bias": True}) if _kernel_timer is not None else None
-    call("hpvg_conv_bwd_weight_bias_f32", ptr(dy), ptr(x), ptr(into_w), 1, ptr(into_b), 1, ptr(ws), ctypes.c_size_t(ws.numel()),
-         B, Ci, Co, T, H, W, KT, stream())
+    call("hpvg_conv_bwd_weight_bias_f32", ptr(dy), ptr(x), ptr(into_w), 1, ptr(into_b), 1, *ws, B, Ci, Co, T, H, W, KT, stream())
     if timed is not None:
         _kernel_timer.end(timed, (B, Ci, Co, T, H, W))
     return True
@@ -309,9 +308,8 @@ def channel_sum_raw(dy, into=None):
     dy = _c(dy)
     B, C, T, H, W = geom(dy)
     out = into if into is not None else torch.empty(C, dtype=torch.float32, device=dy.device)
-    ws = workspace(call("hpvg_channel_sum_ws_bytes", C), dy.device)
-    call("hpvg_channel_sum_f32", ptr(dy), ptr(out), 1 if into is not None else 0, ptr(ws), ctypes.c_size_t(ws.numel()), B, C,
-         ctypes.c_long(T * H * W), stream())
+    call("hpvg_channel_sum_f32", ptr(dy), ptr(out), 1 if into is not None else 0,
+         *_scratch(call("hpvg_channel_sum_ws_bytes", C), dy.device), B, C, T * H * W, stream())
     return None if into is not None else out
 
 
@@ -328,8 +326,9 @@ def _scalar_out(device):
 
 
 def _reduce_ws(device):
+    """The launch arguments (pointer, size) of the reductions' scratch."""
     n = call("hpvg_reduce_ws_bytes")
-    return workspace(n, device), n
+    return ptr(workspace(n, device)), n
 
 
 class inputs_only:
@@ -355,7 +354,7 @@ class LReLUMaskMul(Function):
     def forward(ctx, dy, h):
         dy = _c(dy)
         out = torch.empty_like(dy)
-        call("hpvg_lrelu_mask_mul_f32", ptr(dy), ptr(h), ptr(out), ctypes.c_long(dy.numel()), stream())
+        call("hpvg_lrelu_mask_mul_f32", ptr(dy), ptr(h), ptr(out), dy.numel(), stream())
         ctx.save_for_backward(h)
         return out
 
@@ -496,12 +495,12 @@ class BNAct(Function):
         assert B % groups == 0
         stats = torch.empty(groups, 4, C, dtype=torch.float32, device=dev)  # per group: mean, invstd, scale, shift
         nws = call("hpvg_bn_ws_bytes", C * groups)
-        ws = workspace(nws, dev)
+        ws = _scratch(nws, dev)
         h = torch.empty_like(r)
         st = stats[0]
         call("hpvg_bn_train_fwd_f32", ptr(r), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
              float(momentum), float(eps), ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]), ptr(h),
-             1 if lrelu else 0, groups, ptr(ws), ctypes.c_size_t(ws.numel()), B, C, ctypes.c_long(S), stream())
+             1 if lrelu else 0, groups, *ws, B, C, S, stream())
         ctx.save_for_backward(r, stats, gamma, beta)
         ctx.lrelu, ctx.groups = lrelu, groups
         return h
@@ -526,11 +525,10 @@ class BNAct(Function):
         direct = sg is not None and sb is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
         dgb = (sg, sb) if direct else torch.empty(2, C, dtype=torch.float32, device=dev)
         nws = call("hpvg_bn_ws_bytes", C * groups)
-        ws = workspace(nws, dev)
+        ws = _scratch(nws, dev)
         st = stats[0]
         call("hpvg_bn_act_bwd_f32", ptr(dh), ptr(r), ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]),
-             1 if ctx.lrelu else 0, groups, ptr(dr), ptr(dgb[0]), ptr(dgb[1]), 1 if direct else 0, ptr(ws),
-             ctypes.c_size_t(ws.numel()), B, C, ctypes.c_long(S), stream())
+             1 if ctx.lrelu else 0, groups, ptr(dr), ptr(dgb[0]), ptr(dgb[1]), 1 if direct else 0, *ws, B, C, S, stream())
         if direct:
             return dr, None, None, None, None, None, None, None, None
         return dr, dgb[0], dgb[1], None, None, None, None, None, None
@@ -548,10 +546,10 @@ class BNActBwd(Function):
         dev = r.device
         dr = torch.empty_like(r)
         dgb = torch.empty(2, C, dtype=torch.float32, device=dev)
-        ws = workspace(call("hpvg_bn_ws_bytes", C), dev)
+        ws = _scratch(call("hpvg_bn_ws_bytes", C), dev)
         st = stats[0]
         call("hpvg_bn_act_bwd_f32", ptr(dh), ptr(r), ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]), 1 if lrelu else 0, 1,
-             ptr(dr), ptr(dgb[0]), ptr(dgb[1]), 0, ptr(ws), ctypes.c_size_t(ws.numel()), B, C, ctypes.c_long(S), stream())
+             ptr(dr), ptr(dgb[0]), ptr(dgb[1]), 0, *ws, B, C, S, stream())
         ctx.save_for_backward(dh, r, gamma, stats)
         ctx.lrelu = lrelu
         dg, db = dgb[0], dgb[1]
@@ -570,11 +568,10 @@ class BNActBwd(Function):
         g_r = torch.empty_like(r) if ctx.needs_input_grad[1] else None
         slot = grad_slot(gamma) if ctx.needs_input_grad[2] else None
         g_gamma = slot if slot is not None else (torch.empty(C, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None)
-        ws = workspace(call("hpvg_bn_bwd2_ws_bytes", C), dev)
+        ws = _scratch(call("hpvg_bn_bwd2_ws_bytes", C), dev)
         st = stats[0]
         call("hpvg_bn_act_bwd2_f32", ptr(dh), ptr(g), ptr(r), ptr(st[0]), ptr(st[1]), ptr(st[2]), ptr(st[3]), 1 if ctx.lrelu else 0,
-             ptr(g_dh), ptr(g_r), ptr(g_gamma), 1 if slot is not None else 0, ptr(ws), ctypes.c_size_t(ws.numel()), B, C,
-             ctypes.c_long(S), stream())
+             ptr(g_dh), ptr(g_r), ptr(g_gamma), 1 if slot is not None else 0, *ws, B, C, S, stream())
         return g_dh, g_r, (None if slot is not None else g_gamma), None, None
 
 
@@ -594,7 +591,7 @@ def concat_batch(parts, like=None):
     for p in parts:
         n = p if isinstance(p, int) else p.shape[0]
         src = None if isinstance(p, int) else ptr(_c(p.detach()))
-        call("hpvg_copy_f32", src, ptr(out[o:o + n]), ctypes.c_long(n * per), stream())
+        call("hpvg_copy_f32", src, ptr(out[o:o + n]), n * per, stream())
         o += n
     return out
 
@@ -645,18 +642,17 @@ class BNActSync(Function):
         B, C, T, H, W = geom(r)
         S = T * H * W
         dev = r.device
-        ws = workspace(call("hpvg_bn_ws_bytes", C), dev)
+        ws = _scratch(call("hpvg_bn_ws_bytes", C), dev)
         sums = torch.empty(C, 2, dtype=torch.float64, device=dev)
-        call("hpvg_bn_sums_f32", ptr(r), ptr(sums), ptr(ws), ctypes.c_size_t(ws.numel()), B, C, ctypes.c_long(S), stream())
+        call("hpvg_bn_sums_f32", ptr(r), ptr(sums), *ws, B, C, S, stream())
         allreduce(sums)
         # elements per channel behind the statistics: `total` when the ranks hold unequal shares (row slabs)
         count = float(total) if total is not None else float(B) * float(S) * float(nranks)
         stats = torch.empty(4, C, dtype=torch.float32, device=dev)  # mean, invstd, scale, shift
-        call("hpvg_bn_finalize_f32", ptr(sums), ctypes.c_double(count), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+        call("hpvg_bn_finalize_f32", ptr(sums), count, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
              float(momentum), float(eps), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), C, stream())
         h = torch.empty_like(r)
-        call("hpvg_affine_act_f32", ptr(r), ptr(stats[2]), ptr(stats[3]), ptr(h), 1 if lrelu else 0, B, C, ctypes.c_long(S),
-             stream())
+        call("hpvg_affine_act_f32", ptr(r), ptr(stats[2]), ptr(stats[3]), ptr(h), 1 if lrelu else 0, B, C, S, stream())
         ctx.save_for_backward(r, stats)
         ctx.lrelu, ctx.allreduce, ctx.count = lrelu, allreduce, count
         return h
@@ -669,16 +665,16 @@ class BNActSync(Function):
         B, C, T, H, W = geom(r)
         S = T * H * W
         dev = r.device
-        ws = workspace(call("hpvg_bn_ws_bytes", C), dev)
+        ws = _scratch(call("hpvg_bn_ws_bytes", C), dev)
         local = torch.empty(C, 2, dtype=torch.float64, device=dev)  # (sum dz, sum dz*xhat) of this rank's samples
         call("hpvg_bn_act_bwd_sums_f32", ptr(dh), ptr(r), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
-             1 if ctx.lrelu else 0, ptr(local), ptr(ws), ctypes.c_size_t(ws.numel()), B, C, ctypes.c_long(S), stream())
+             1 if ctx.lrelu else 0, ptr(local), *ws, B, C, S, stream())
         glob = local.clone()
         ctx.allreduce(glob)
         gsum = glob.to(torch.float32).contiguous()
         dr = torch.empty_like(r)
         call("hpvg_bn_act_bwd_apply_f32", ptr(dh), ptr(r), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]),
-             1 if ctx.lrelu else 0, ptr(gsum), float(1.0 / ctx.count), ptr(dr), B, C, ctypes.c_long(S), stream())
+             1 if ctx.lrelu else 0, ptr(gsum), float(1.0 / ctx.count), ptr(dr), B, C, S, stream())
         loc32 = local.to(torch.float32)
         return dr, loc32[:, 1].contiguous(), loc32[:, 0].contiguous(), None, None, None, None, None, None, None, None
 
@@ -691,8 +687,7 @@ class AffineAct(Function):
         r = _c(r)
         B, C, T, H, W = geom(r)
         h = torch.empty_like(r)
-        call("hpvg_affine_act_f32", ptr(r), ptr(_c(scale)), ptr(_c(shift)), ptr(h), 1 if lrelu else 0, B, C,
-             ctypes.c_long(T * H * W), stream())
+        call("hpvg_affine_act_f32", ptr(r), ptr(_c(scale)), ptr(_c(shift)), ptr(h), 1 if lrelu else 0, B, C, T * H * W, stream())
         return h
 
     @staticmethod
@@ -712,14 +707,14 @@ class SpectralNormWeight(Function):
         K = w_orig.numel() // Co
         dev = w_orig.device
         sig = torch.empty(2, dtype=torch.float32, device=dev)  # sigma, 1/sigma
-        ws = workspace(Co * 4, dev)
+        ws = _scratch(Co * 4, dev)
         # later forwards overwrite the u/v buffers before this call's backward runs: the kernel also writes the (u, v) its
         # sigma belongs to into `uv` (torch clones them for the same reason); [0, Co) = u, [Co, Co + K) = v
         uv = torch.empty(Co + K, dtype=torch.float32, device=dev) if w_orig.requires_grad else None
         call("hpvg_sn_power_iter_f32", ptr(w_orig), ptr(u), ptr(v), ptr(sig[0:1]), ptr(sig[1:2]), ptr(uv), Co, K,
-             1 if do_iter else 0, float(eps), ptr(ws), ctypes.c_size_t(ws.numel()), stream())
+             1 if do_iter else 0, float(eps), *ws, stream())
         w = torch.empty_like(w_orig)
-        call("hpvg_div_scalar_f32", ptr(w_orig), ptr(sig[0:1]), ptr(w), ctypes.c_long(w.numel()), stream())
+        call("hpvg_div_scalar_f32", ptr(w_orig), ptr(sig[0:1]), ptr(w), w.numel(), stream())
         ctx.save_for_backward(w_orig, uv, sig)
         return w
 
@@ -732,13 +727,10 @@ class SpectralNormWeight(Function):
         K = w_orig.numel() // Co
         slot = grad_slot(w_orig)
         out = slot if slot is not None else torch.empty_like(w_orig)
-        ws = workspace(call("hpvg_sn_bwd_ws_bytes", Co, K), dw.device)
+        ws = _scratch(call("hpvg_sn_bwd_ws_bytes", Co, K), dw.device)
         call("hpvg_sn_bwd_f32", ptr(dw), ptr(w_orig), ptr(uv[:Co]), ptr(uv[Co:]), ptr(sig[0:1]), ptr(out),
-             1 if slot is not None else 0, ptr(ws), ctypes.c_size_t(ws.numel()), Co, K, stream())
+             1 if slot is not None else 0, *ws, Co, K, stream())
         return (None if slot is not None else out), None, None, None, None
-
-
-SN_BATCH_MAX = 8
 
 
 class SpectralNormWeightBatch(Function):
@@ -762,11 +754,11 @@ class SpectralNormWeightBatch(Function):
         need = [w.requires_grad for w in ws_orig]
         uvs = [torch.empty(Cos[i] + Ks[i], dtype=torch.float32, device=dev) if need[i] else None for i in range(n)]
         outs = [torch.empty_like(w) for w in ws_orig]
-        ws = workspace(4 * sum(Cos), dev)
+        ws = _scratch(4 * sum(Cos), dev)
         PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
         call("hpvg_sn_power_iter_batch_f32", n, PA(*[ptr(w) for w in ws_orig]), PA(*[ptr(u) for u in us]), PA(*[ptr(v) for v in vs]),
              PA(*[ptr(sig[i]) for i in range(n)]), PA(*[ptr(t) for t in uvs]), PA(*[ptr(o) for o in outs]), IA(*Cos), IA(*Ks),
-             1 if do_iter else 0, float(eps), ptr(ws), ctypes.c_size_t(ws.numel()), stream())
+             1 if do_iter else 0, float(eps), *ws, stream())
         ctx.n = n
         ctx.save_for_backward(sig, *ws_orig, *uvs)
         return tuple(outs)
@@ -788,11 +780,11 @@ class SpectralNormWeightBatch(Function):
             outs = [sl if sl is not None else torch.empty_like(ws_orig[i]) for sl, i in zip(slots, live)]
             Cos = [ws_orig[i].shape[0] for i in live]
             Ks = [ws_orig[i].numel() // ws_orig[i].shape[0] for i in live]
-            ws = workspace(sum(call("hpvg_sn_bwd_ws_bytes", c, k) for c, k in zip(Cos, Ks)), dev)
+            ws = _scratch(sum(call("hpvg_sn_bwd_ws_bytes", c, k) for c, k in zip(Cos, Ks)), dev)
             PA, IA = ctypes.c_void_p * m, ctypes.c_int * m
             call("hpvg_sn_bwd_batch_f32", m, PA(*[ptr(t) for t in dwc]), PA(*[ptr(ws_orig[i]) for i in live]),
                  PA(*[ptr(uvs[i]) for i in live]), PA(*[ptr(sig[i, 0:1]) for i in live]), PA(*[ptr(o) for o in outs]),
-                 IA(*[1 if sl is not None else 0 for sl in slots]), IA(*Cos), IA(*Ks), ptr(ws), ctypes.c_size_t(ws.numel()), stream())
+                 IA(*[1 if sl is not None else 0 for sl in slots]), IA(*Cos), IA(*Ks), *ws, stream())
             for i, sl, o in zip(live, slots, outs):
                 res[i] = None if sl is not None else o
         for i in range(n):
@@ -810,7 +802,7 @@ class TanhRes(Function):
         if res is not None:
             res = _c(res)
         y = torch.empty_like(x)
-        call("hpvg_tanh_fwd_f32", ptr(x), ptr(res), ptr(y), ctypes.c_long(x.numel()), stream())
+        call("hpvg_tanh_fwd_f32", ptr(x), ptr(res), ptr(y), x.numel(), stream())
         ctx.save_for_backward(y)
         ctx.has_res = res is not None
         return y
@@ -821,7 +813,7 @@ class TanhRes(Function):
         (y,) = ctx.saved_tensors
         dy = _c(dy)
         dx = torch.empty_like(y)
-        call("hpvg_tanh_bwd_f32", ptr(dy), ptr(y), ptr(dx), ctypes.c_long(y.numel()), stream())
+        call("hpvg_tanh_bwd_f32", ptr(dy), ptr(y), ptr(dx), y.numel(), stream())
         return dx, (dx if ctx.has_res else None)
 
 
@@ -834,7 +826,7 @@ class Add(Function):
         if a.shape != b.shape:
             raise RuntimeError("add: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
         out = torch.empty_like(a)
-        call("hpvg_add_f32", ptr(a), ptr(b), ptr(out), ctypes.c_long(a.numel()), stream())
+        call("hpvg_add_f32", ptr(a), ptr(b), ptr(out), a.numel(), stream())
         return out
 
     @staticmethod
@@ -852,7 +844,7 @@ def _box_copy(src, grow):
     if min(dT, dH, dW) < 1:
         raise RuntimeError("crop of %d from %s leaves nothing" % (-grow, tuple(src.shape)))
     out = src.new_empty((B, C, dT, dH, dW) if src.dim() == 5 else (B, C, dH, dW))
-    call("hpvg_box_copy_f32", ptr(src), ptr(out), ctypes.c_long(B * C), T, H, W, dT, dH, dW, oT, grow, grow, stream())
+    call("hpvg_box_copy_f32", ptr(src), ptr(out), B * C, T, H, W, dT, dH, dW, oT, grow, grow, stream())
     return out
 
 
@@ -885,6 +877,16 @@ class CropBorder(Function):
         return ZeroPad.apply(g, ctx.c), None
 
 
+def _resize_out(ctx, x, size):
+    """The empty output of a resize of x to `size`, and the kernels' (B * C, Ti, Hi, Wi, To, Ho, Wo), which ctx keeps with
+    the input's shape for UpsampleAC.backward."""
+    B, C, Ti, Hi, Wi = geom(x)
+    To, Ho, Wo = size if x.dim() == 5 else (1,) + tuple(size)
+    ctx.in_shape = x.shape
+    ctx.dims = (B * C, Ti, Hi, Wi, To, Ho, Wo)
+    return torch.empty((B, C) + tuple(size), dtype=torch.float32, device=x.device), ctx.dims
+
+
 class UpsampleAC(Function):
     """Tri/bi-linear resize with align_corners=True to `size`; with `noise`, also returns up + amp*noise
     (utils/images.py:83-105 + networks_3d.py:395-400)."""
@@ -892,25 +894,14 @@ class UpsampleAC(Function):
     @staticmethod
     def forward(ctx, x, size, noise, amp):
         x = _c(x)
-        B, C, Ti, Hi, Wi = geom(x)
-        if x.dim() == 5:
-            To, Ho, Wo = size
-            oshape = (B, C, To, Ho, Wo)
-        else:
-            Ho, Wo = size
-            To = 1
-            oshape = (B, C, Ho, Wo)
-        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        y, dims = _resize_out(ctx, x, size)
         yn = None
         if noise is not None:
             noise = _c(noise)
-            if tuple(noise.shape) != tuple(oshape):
-                raise RuntimeError("noise shape %s != upsampled shape %s" % (tuple(noise.shape), oshape))
+            if noise.shape != y.shape:
+                raise RuntimeError("noise shape %s != upsampled shape %s" % (tuple(noise.shape), tuple(y.shape)))
             yn = torch.empty_like(y)
-        call("hpvg_upsample_linear_ac_f32", ptr(x), ptr(y), ptr(noise), float(amp), ptr(yn), ctypes.c_long(B * C), Ti, Hi,
-             Wi, To, Ho, Wo, stream())
-        ctx.in_shape = x.shape
-        ctx.dims = (B * C, Ti, Hi, Wi, To, Ho, Wo)
+        call("hpvg_upsample_linear_ac_f32", ptr(x), ptr(y), ptr(noise), float(amp), ptr(yn), *dims, stream())
         if yn is None:
             return y
         return y, yn
@@ -924,7 +915,7 @@ class UpsampleAC(Function):
         g2 = _c(g2) if g2 is not None else None
         BC, Ti, Hi, Wi, To, Ho, Wo = ctx.dims
         dx = torch.empty(ctx.in_shape, dtype=torch.float32, device=g.device)
-        call("hpvg_upsample_linear_ac_bwd_f32", ptr(g), ptr(g2), ptr(dx), ctypes.c_long(BC), Ti, Hi, Wi, To, Ho, Wo, stream())
+        call("hpvg_upsample_linear_ac_bwd_f32", ptr(g), ptr(g2), ptr(dx), BC, Ti, Hi, Wi, To, Ho, Wo, stream())
         return dx, None, None, None
 
 
@@ -960,22 +951,26 @@ def rng_next_iteration(device):
 
 
 def _seed():
-    return ctypes.c_ulonglong(torch.initial_seed() & 0xFFFFFFFFFFFFFFFF)   # follows torch.manual_seed
+    return torch.initial_seed() & 0xFFFFFFFFFFFFFFFF   # follows torch.manual_seed
+
+
+def _philox_call(name, device, *args):
+    """Launch a kernel whose arguments end in the Philox triple (seed, call index, iteration pointer) and the stream: the next
+    draw of `device`'s noise stream."""
+    st = _rng(device)
+    call(name, *args, _seed(), st.call & 0xFFFFFFFF, ptr(st.iter_dev), stream())
+    st.call += 1
 
 
 def normal_(out):
     """out <- N(0, 1) (utils/images.py:49, networks_3d.py:32) with the Philox kernel of libhpvg; returns out."""
-    st = _rng(out.device)
-    call("hpvg_normal_f32", ptr(out), ctypes.c_long(out.numel()), _seed(), ctypes.c_uint(st.call & 0xFFFFFFFF), ptr(st.iter_dev), stream())
-    st.call += 1
+    _philox_call("hpvg_normal_f32", out.device, ptr(out), out.numel())
     return out
 
 
 def uniform_(out):
     """out <- U[0, 1) from the library's Philox stream (reparameterize_bern's eps, networks_3d.py:40)."""
-    st = _rng(out.device)
-    call("hpvg_uniform_f32", ptr(out), ctypes.c_long(out.numel()), _seed(), ctypes.c_uint(st.call & 0xFFFFFFFF), ptr(st.iter_dev), stream())
-    st.call += 1
+    _philox_call("hpvg_uniform_f32", out.device, ptr(out), out.numel())
     return out
 
 
@@ -997,7 +992,7 @@ class Gate(Function):
         B, C, S = _bcs(f)
         out = torch.empty_like(f)
         bern = torch.empty_like(logit)
-        call("hpvg_gate_fwd_f32", ptr(f), ptr(logit), ptr(out), ptr(bern), B, C, ctypes.c_long(S), stream())
+        call("hpvg_gate_fwd_f32", ptr(f), ptr(logit), ptr(out), ptr(bern), B, C, S, stream())
         ctx.save_for_backward(f, bern)
         return out, bern
 
@@ -1010,7 +1005,7 @@ class Gate(Function):
         dbern = _c(dbern) if dbern is not None else None
         df = torch.empty_like(f) if (ctx.needs_input_grad[0] and dout is not None) else None
         dlogit = torch.empty_like(bern) if ctx.needs_input_grad[1] else None
-        call("hpvg_gate_bwd_f32", ptr(dout), ptr(f), ptr(bern), ptr(dbern), ptr(df), ptr(dlogit), B, C, ctypes.c_long(S), stream())
+        call("hpvg_gate_bwd_f32", ptr(dout), ptr(f), ptr(bern), ptr(dbern), ptr(df), ptr(dlogit), B, C, S, stream())
         return df, dlogit
 
 
@@ -1022,7 +1017,7 @@ class GlobalAvgPool(Function):
         x = _c(x)
         B, C, S = _bcs(x)
         out = torch.empty((B, C) + (1,) * (x.dim() - 2), dtype=torch.float32, device=x.device)
-        call("hpvg_rowsum_f32", ptr(x), None, ptr(out), float(1.0 / S), B, C, ctypes.c_long(S), stream())
+        call("hpvg_rowsum_f32", ptr(x), None, ptr(out), float(1.0 / S), B, C, S, stream())
         ctx.shape = x.shape
         return out
 
@@ -1032,7 +1027,7 @@ class GlobalAvgPool(Function):
         g = _c(g)
         B, C, S = _bcs(torch.empty(ctx.shape, device="meta"))
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        call("hpvg_outer_f32", ptr(g), None, ptr(dx), float(1.0 / S), B, C, ctypes.c_long(S), stream())
+        call("hpvg_outer_f32", ptr(g), None, ptr(dx), float(1.0 / S), B, C, S, stream())
         return dx
 
 
@@ -1047,7 +1042,7 @@ class CodeTimesMap(Function):
         if code.numel() != B * C or zmap.shape[1] != 1:
             raise RuntimeError("CodeTimesMap: expected a [B,C,1,..] code and a [B,1,...] map, got %s, %s" % (tuple(code.shape), tuple(zmap.shape)))
         out = torch.empty((B, C) + tuple(zmap.shape[2:]), dtype=torch.float32, device=code.device)
-        call("hpvg_outer_f32", ptr(code), ptr(zmap), ptr(out), 1.0, B, C, ctypes.c_long(S), stream())
+        call("hpvg_outer_f32", ptr(code), ptr(zmap), ptr(out), 1.0, B, C, S, stream())
         ctx.save_for_backward(code, zmap)
         return out
 
@@ -1061,10 +1056,10 @@ class CodeTimesMap(Function):
         dcode = dmap = None
         if ctx.needs_input_grad[0]:
             dcode = torch.empty_like(code)
-            call("hpvg_rowsum_f32", ptr(dz), ptr(zmap), ptr(dcode), 1.0, B, C, ctypes.c_long(S), stream())
+            call("hpvg_rowsum_f32", ptr(dz), ptr(zmap), ptr(dcode), 1.0, B, C, S, stream())
         if ctx.needs_input_grad[1]:
             dmap = torch.empty_like(zmap)
-            call("hpvg_colsum_f32", ptr(dz), ptr(code), ptr(dmap), B, C, ctypes.c_long(S), stream())
+            call("hpvg_colsum_f32", ptr(dz), ptr(code), ptr(dmap), B, C, S, stream())
         return dcode, dmap
 
 
@@ -1075,7 +1070,7 @@ class ReparamBern(Function):
     def forward(ctx, x, eps):
         x, eps = _c(x), _c(eps)
         z = torch.empty_like(x)
-        call("hpvg_reparam_bern_fwd_f32", ptr(x), ptr(eps), ptr(z), ctypes.c_long(x.numel()), stream())
+        call("hpvg_reparam_bern_fwd_f32", ptr(x), ptr(eps), ptr(z), x.numel(), stream())
         ctx.save_for_backward(x)
         return z
 
@@ -1084,7 +1079,7 @@ class ReparamBern(Function):
     def backward(ctx, dz):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        call("hpvg_reparam_bern_bwd_f32", ptr(_c(dz)), ptr(x), ptr(dx), ctypes.c_long(x.numel()), stream())
+        call("hpvg_reparam_bern_bwd_f32", ptr(_c(dz)), ptr(x), ptr(dx), x.numel(), stream())
         return dx, None
 
 
@@ -1095,8 +1090,7 @@ class KLBern(Function):
     def forward(ctx, x):
         x = _c(x)
         out = _scalar_out(x.device)
-        ws, n = _reduce_ws(x.device)
-        call("hpvg_kl_bern_fwd_f32", ptr(x), ptr(out), ptr(ws), ctypes.c_size_t(n), ctypes.c_long(x.numel()), stream())
+        call("hpvg_kl_bern_fwd_f32", ptr(x), ptr(out), *_reduce_ws(x.device), x.numel(), stream())
         ctx.save_for_backward(x)
         return out.view(())
 
@@ -1105,7 +1099,7 @@ class KLBern(Function):
     def backward(ctx, g):
         (x,) = ctx.saved_tensors
         dx = torch.empty_like(x)
-        call("hpvg_kl_bern_bwd_f32", ptr(_c(g).view(1)), ptr(x), ptr(dx), ctypes.c_long(x.numel()), stream())
+        call("hpvg_kl_bern_bwd_f32", ptr(_c(g).view(1)), ptr(x), ptr(dx), x.numel(), stream())
         return dx
 
 
@@ -1117,34 +1111,13 @@ class UpsampleACNoise(Function):
     @staticmethod
     def forward(ctx, x, size, amp, first_noisy):
         x = _c(x)
-        B, C, Ti, Hi, Wi = geom(x)
-        if x.dim() == 5:
-            To, Ho, Wo = size
-            oshape = (B, C, To, Ho, Wo)
-        else:
-            Ho, Wo = size
-            To = 1
-            oshape = (B, C, Ho, Wo)
-        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        y, dims = _resize_out(ctx, x, size)
         yn = torch.empty_like(y)
-        st = _rng(x.device)
-        call("hpvg_upsample_linear_ac_noise_f32", ptr(x), ptr(y), ptr(yn), float(amp), ctypes.c_long(B * C), C, int(first_noisy), Ti,
-             Hi, Wi, To, Ho, Wo, _seed(), ctypes.c_uint(st.call & 0xFFFFFFFF), ptr(st.iter_dev), stream())
-        st.call += 1
-        ctx.in_shape = x.shape
-        ctx.dims = (B * C, Ti, Hi, Wi, To, Ho, Wo)
+        _philox_call("hpvg_upsample_linear_ac_noise_f32", x.device, ptr(x), ptr(y), ptr(yn), float(amp), dims[0], x.shape[1],
+                     int(first_noisy), *dims[1:])
         return y, yn
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy, dyn):
-        g, g2 = (dy, dyn) if dy is not None else (dyn, None)
-        g = _c(g)
-        g2 = _c(g2) if g2 is not None else None
-        BC, Ti, Hi, Wi, To, Ho, Wo = ctx.dims
-        dx = torch.empty(ctx.in_shape, dtype=torch.float32, device=g.device)
-        call("hpvg_upsample_linear_ac_bwd_f32", ptr(g), ptr(g2), ptr(dx), ctypes.c_long(BC), Ti, Hi, Wi, To, Ho, Wo, stream())
-        return dx, None, None, None
+    backward = UpsampleAC.backward
 
 
 class Reparam(Function):
@@ -1154,7 +1127,7 @@ class Reparam(Function):
     def forward(ctx, mu, logvar, eps):
         mu, logvar, eps = _c(mu), _c(logvar), _c(eps)
         z = torch.empty_like(mu)
-        call("hpvg_reparam_fwd_f32", ptr(mu), ptr(logvar), ptr(eps), ptr(z), ctypes.c_long(mu.numel()), stream())
+        call("hpvg_reparam_fwd_f32", ptr(mu), ptr(logvar), ptr(eps), ptr(z), mu.numel(), stream())
         ctx.save_for_backward(logvar, eps)
         return z
 
@@ -1164,7 +1137,7 @@ class Reparam(Function):
         logvar, eps = ctx.saved_tensors
         dz = _c(dz)
         dlv = torch.empty_like(dz)
-        call("hpvg_reparam_bwd_f32", ptr(dz), ptr(logvar), ptr(eps), ptr(dlv), ctypes.c_long(dz.numel()), stream())
+        call("hpvg_reparam_bwd_f32", ptr(dz), ptr(logvar), ptr(eps), ptr(dlv), dz.numel(), stream())
         return dz, dlv, None
 
 
@@ -1176,8 +1149,7 @@ class KL(Function):
     def forward(ctx, mu, logvar):
         mu, logvar = _c(mu), _c(logvar)
         out = _scalar_out(mu.device)
-        ws, n = _reduce_ws(mu.device)
-        call("hpvg_kl_fwd_f32", ptr(mu), ptr(logvar), ptr(out), ptr(ws), ctypes.c_size_t(n), ctypes.c_long(mu.numel()), stream())
+        call("hpvg_kl_fwd_f32", ptr(mu), ptr(logvar), ptr(out), *_reduce_ws(mu.device), mu.numel(), stream())
         ctx.save_for_backward(mu, logvar)
         return out.view(())
 
@@ -1188,7 +1160,7 @@ class KL(Function):
         g = _c(g).view(1)
         dmu = torch.empty_like(mu)
         dlv = torch.empty_like(mu)
-        call("hpvg_kl_bwd_f32", ptr(g), ptr(mu), ptr(logvar), ptr(dmu), ptr(dlv), ctypes.c_long(mu.numel()), stream())
+        call("hpvg_kl_bwd_f32", ptr(g), ptr(mu), ptr(logvar), ptr(dmu), ptr(dlv), mu.numel(), stream())
         return dmu, dlv
 
 
@@ -1201,8 +1173,7 @@ class MSE(Function):
         if a.shape != b.shape:
             raise RuntimeError("mse: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
         out = _scalar_out(a.device)
-        ws, n = _reduce_ws(a.device)
-        call("hpvg_mse_fwd_f32", ptr(a), ptr(b), ptr(out), ptr(ws), ctypes.c_size_t(n), ctypes.c_long(a.numel()), stream())
+        call("hpvg_mse_fwd_f32", ptr(a), ptr(b), ptr(out), *_reduce_ws(a.device), a.numel(), stream())
         ctx.save_for_backward(a, b)
         return out.view(())
 
@@ -1214,10 +1185,10 @@ class MSE(Function):
         da = db = None
         if ctx.needs_input_grad[0]:
             da = torch.empty_like(a)
-            call("hpvg_mse_bwd_f32", ptr(g), ptr(a), ptr(b), ptr(da), ctypes.c_long(a.numel()), stream())
+            call("hpvg_mse_bwd_f32", ptr(g), ptr(a), ptr(b), ptr(da), a.numel(), stream())
         if ctx.needs_input_grad[1]:
             db = torch.empty_like(a)
-            call("hpvg_mse_bwd_f32", ptr(g), ptr(b), ptr(a), ptr(db), ctypes.c_long(a.numel()), stream())
+            call("hpvg_mse_bwd_f32", ptr(g), ptr(b), ptr(a), ptr(db), a.numel(), stream())
         return da, db
 
 
@@ -1228,9 +1199,7 @@ class MeanScaled(Function):
     def forward(ctx, x, sign):
         x = _c(x)
         out = _scalar_out(x.device)
-        ws, n = _reduce_ws(x.device)
-        call("hpvg_sum_scaled_f32", ptr(x), ptr(out), ctypes.c_double(sign / x.numel()), ptr(ws), ctypes.c_size_t(n),
-             ctypes.c_long(x.numel()), stream())
+        call("hpvg_sum_scaled_f32", ptr(x), ptr(out), sign / x.numel(), *_reduce_ws(x.device), x.numel(), stream())
         ctx.shape = x.shape
         ctx.coef = sign / x.numel()
         return out.view(())
@@ -1240,7 +1209,7 @@ class MeanScaled(Function):
     def backward(ctx, g):
         g = _c(g).view(1)
         dx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        call("hpvg_fill_scaled_f32", ptr(g), float(ctx.coef), ptr(dx), ctypes.c_long(dx.numel()), stream())
+        call("hpvg_fill_scaled_f32", ptr(g), float(ctx.coef), ptr(dx), dx.numel(), stream())
         return dx, None
 
 
@@ -1252,9 +1221,7 @@ class GradPenalty(Function):
         g = _c(g)
         B, C, T, H, W = geom(g)
         out = _scalar_out(g.device)
-        ws, n = _reduce_ws(g.device)
-        call("hpvg_gp_fwd_f32", ptr(g), ptr(out), float(lam), ptr(ws), ctypes.c_size_t(n), B, C, ctypes.c_long(T * H * W),
-             stream())
+        call("hpvg_gp_fwd_f32", ptr(g), ptr(out), float(lam), *_reduce_ws(g.device), B, C, T * H * W, stream())
         ctx.save_for_backward(g)
         ctx.lam = lam
         return out.view(())
@@ -1266,7 +1233,7 @@ class GradPenalty(Function):
         gout = _c(gout).view(1)
         B, C, T, H, W = geom(g)
         dg = torch.empty_like(g)
-        call("hpvg_gp_bwd_f32", ptr(gout), ptr(g), ptr(dg), float(ctx.lam), B, C, ctypes.c_long(T * H * W), stream())
+        call("hpvg_gp_bwd_f32", ptr(gout), ptr(g), ptr(dg), float(ctx.lam), B, C, T * H * W, stream())
         return dg, None
 
 
@@ -1293,26 +1260,25 @@ def lerp(a, b, alpha):
     """alpha*a + (1-alpha)*b with a device scalar alpha (no autograd: the result becomes a leaf, modules/utils.py:9-10)."""
     a, b = _c(a.detach()), _c(b.detach())
     out = torch.empty_like(a)
-    call("hpvg_lerp_f32", ptr(a), ptr(b), ptr(alpha), ptr(out), ctypes.c_long(a.numel()), stream())
+    call("hpvg_lerp_f32", ptr(a), ptr(b), ptr(alpha), ptr(out), a.numel(), stream())
     return out
 
 
 # ------------------------------------------------------------------------------------------ optimizer primitives
 def sqsum(flat):
     out = _scalar_out(flat.device)
-    ws, n = _reduce_ws(flat.device)
-    call("hpvg_sqsum_f32", ptr(flat), ptr(out), ptr(ws), ctypes.c_size_t(n), ctypes.c_long(flat.numel()), stream())
+    call("hpvg_sqsum_f32", ptr(flat), ptr(out), *_reduce_ws(flat.device), flat.numel(), stream())
     return out
 
 
 def clip_scale_(flat_grad, sq, max_norm, coef_out=None):
-    call("hpvg_clip_scale_f32", ptr(flat_grad), ctypes.c_long(flat_grad.numel()), ptr(sq), float(max_norm), ptr(coef_out),
+    call("hpvg_clip_scale_f32", ptr(flat_grad), flat_grad.numel(), ptr(sq), float(max_norm), ptr(coef_out),
          stream())
 
 
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step, step_dev=None):
     weights_changed()
-    call("hpvg_adam_step_f32", ptr(p), ptr(g), ptr(m), ptr(v), ctypes.c_long(p.numel()), float(lr), float(beta1), float(beta2),
+    call("hpvg_adam_step_f32", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(beta1), float(beta2),
          float(eps), int(step), ptr(step_dev), stream())
 
 
@@ -1356,34 +1322,6 @@ def patch_nn_counts(qshape, rshape, patch, qstride=(1, 1, 1), rstride=(1, 1, 1))
     return out[0], out[1], out[2]
 
 
-def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
-    """Exact patch nearest neighbours (hpvg_patchnn_u8, i8 matrix cores): query / ref are uint8 device tensors [T,H,W,3] or
-    [H,W,3]; for every patch of the query's strided grid, d2 = the smallest squared distance to a patch of ref's grid and nn =
-    the smallest index (raster order of ref's grid) that attains it.  Both int32, shaped as the query's patch grid."""
-    vols = []
-    for name, t in (("query", query_u8), ("ref", ref_u8)):
-        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
-            raise RuntimeError("patch_nn: %s must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (name, t.dtype, tuple(t.shape)))
-        vols.append(_c(t if t.dim() == 4 else t[None]))
-    q, r = vols
-    if query_u8.dim() != ref_u8.dim():
-        raise RuntimeError("patch_nn: query and ref must both be volumes or both be images")
-    if q.device != r.device:
-        raise RuntimeError("patch_nn: query on %s, ref on %s" % (q.device, r.device))
-    pa, qs, rs = _triple(patch, "patch"), _triple(qstride, "qstride"), _triple(rstride, "rstride")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, (ctypes.c_int * 3)())   # refuses bad arguments by name
-    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
-    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
-    ws = workspace(nbytes, q.device)
-    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
-    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patchnn_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(d2), ptr(nn), ptr(ws), ws.numel(), stream())
-    if query_u8.dim() == 3:
-        d2, nn = d2[0], nn[0]
-    return d2, nn
-
-
 def _patch_volumes(op, pairs):
     """The uint8 [T,H,W,3] views of volumes or images (all of one rank, on one device), and whether they are images."""
     vols = []
@@ -1396,6 +1334,25 @@ def _patch_volumes(op, pairs):
             raise RuntimeError("%s: %s on %s, %s on %s" % (op, pairs[0][0], pairs[0][1].device, name, t.device))
         vols.append(_c(t if t.dim() == 4 else t[None]))
     return vols, pairs[0][1].dim() == 3
+
+
+def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """Exact patch nearest neighbours (hpvg_patchnn_u8, i8 matrix cores): query / ref are uint8 device tensors [T,H,W,3] or
+    [H,W,3]; for every patch of the query's strided grid, d2 = the smallest squared distance to a patch of ref's grid and nn =
+    the smallest index (raster order of ref's grid) that attains it.  Both int32, shaped as the query's patch grid."""
+    (q, r), image = _patch_volumes("patch_nn", (("query", query_u8), ("ref", ref_u8)))
+    pa, qs, rs = _triple(patch, "patch"), _triple(qstride, "qstride"), _triple(rstride, "rstride")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, (ctypes.c_int * 3)())   # refuses bad arguments by name
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
+    ws = _scratch(nbytes, q.device)
+    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
+    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
+    call("hpvg_patchnn_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(d2), ptr(nn), *ws, stream())
+    if image:
+        d2, nn = d2[0], nn[0]
+    return d2, nn
 
 
 def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
@@ -1422,10 +1379,10 @@ def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rs
         raise RuntimeError("patch_nn_weighted: every ref_weight must be finite and > 0")
     grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
     nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
-    ws = workspace(nbytes, q.device)
+    ws = _scratch(nbytes, q.device)
     score = torch.empty(grid, dtype=torch.float32, device=q.device)
     nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patchnn_weighted_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(w), ptr(score), ptr(nn), ptr(ws), ws.numel(), stream())
+    call("hpvg_patchnn_weighted_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(w), ptr(score), ptr(nn), *ws, stream())
     if image:
         score, nn = score[0], nn[0]
     return score, nn
@@ -1509,8 +1466,8 @@ def patch_proj_hist(vol_u8, patch, dirs_i8, stride=(1, 1, 1)):
     for p0 in range(0, P, chunk):
         n = min(chunk, P - p0)
         nbytes = call("hpvg_patchproj_ws_bytes", *g, pa, st, n)
-        ws = workspace(nbytes, v.device)
-        call("hpvg_patchproj_hist_u8", ptr(v), *g, pa, st, ptr(dirs[p0:p0 + n]), n, ptr(hist[p0:p0 + n]), ptr(ws), ws.numel(), stream())
+        ws = _scratch(nbytes, v.device)
+        call("hpvg_patchproj_hist_u8", ptr(v), *g, pa, st, ptr(dirs[p0:p0 + n]), n, ptr(hist[p0:p0 + n]), *ws, stream())
     return hist
 
 

@@ -26,7 +26,7 @@ def graph_node_census(graph):
     import ctypes
     from .lib import call
     counts = (ctypes.c_int * len(_NODE_TYPES))()
-    call("hpvg_graph_node_census", ctypes.c_void_p(graph.raw_cuda_graph()), counts, len(_NODE_TYPES))
+    call("hpvg_graph_node_census", graph.raw_cuda_graph(), counts, len(_NODE_TYPES))
     return {name: int(c) for name, c in zip(_NODE_TYPES, counts)}
 
 

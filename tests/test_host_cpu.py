@@ -4,6 +4,7 @@ the reference's state_dicts, Adam parameter groups follow train_video.py:57-86, 
 import ctypes
 import json
 import os
+import re
 
 import pytest
 import torch
@@ -23,6 +24,68 @@ def test_library_loads_and_exports_header_symbols():
     lib = ctypes.CDLL(hplib.LIB_PATH)
     for s in declared:
         assert hasattr(lib, s), s
+
+
+def test_header_signatures_frozen():
+    """Declarations that between them use every C type of include/hpvg.h, as the parser must bind them."""
+    c = ctypes
+    P, I, L, F, D, Z = c.c_void_p, c.c_int, c.c_long, c.c_float, c.c_double, c.c_size_t
+    want = {
+        "hpvg_bn_finalize_f32": ([P, D, P, P, P, P, F, F, P, P, P, P, I, P], I),
+        "hpvg_normal_f32": ([P, L, c.c_ulonglong, c.c_uint, P, P], I),
+        "hpvg_scalar_log_append_f32": ([hplib.ScalarPtrs, I, P, I, P, P], I),
+        "hpvg_hist_w1_i32": ([P, L, P, L, I, L, P, P], I),
+        "hpvg_sn_power_iter_batch_f32": ([I] + [P] * 8 + [I, F, P, Z, P], I),    # pointer-to-pointer parameters
+        "hpvg_clip_scale_f32": ([P, L, P, F, P, P], I),                          # a comment inside the parameter list
+        "hpvg_reduce_ws_bytes": ([], Z),
+        "hpvg_patchproj_bins": ([P], Z),
+        "hpvg_conv_wino_config": ([I, L], I),
+    }
+    with open(hplib.HEADER_PATH) as f:
+        sigs, _ = hplib.parse_header(f.read())
+    for name, (args, ret) in want.items():
+        assert sigs[name] == (ret, args), name
+
+
+def test_every_declaration_is_parsed_and_bound():
+    with open(hplib.HEADER_PATH) as f:
+        text = f.read()
+    sigs, _ = hplib.parse_header(text)
+    names = set(re.findall(r"\b(hpvg_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
+    assert names == set(sigs) and sorted(names) == hplib.check_symbols()
+    lib = hplib.load()
+    for name, (ret, args) in sigs.items():
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == args and fn.restype is ret, name
+        assert ret in (ctypes.c_int, ctypes.c_size_t), name
+
+
+@pytest.mark.parametrize("decl", [
+    "int hpvg_x(const float* a, short n, void* stream);",            # a scalar type outside the known set
+    "int hpvg_x(void (*cb)(int), void* stream);",                    # a function-pointer parameter
+    "float hpvg_x(const float* a);",                                 # an unknown return type
+    "const char* hpvg_x(int code);",
+    "int hpvg_x(int);",                                              # no parameter name: the type cannot be told from it
+])
+def test_header_parser_refuses_what_it_does_not_understand(decl):
+    ok = "#define HPVG_N 4\n/* int hpvg_hidden(short n); */\nsize_t hpvg_ok(int n, /* why */ unsigned long long seed);\n"
+    sigs, consts = hplib.parse_header(ok)
+    assert sigs == {"hpvg_ok": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_ulonglong])} and consts == {"HPVG_N": 4}
+    with pytest.raises(ImportError, match="hpvg_x"):
+        hplib.parse_header(ok + decl + "\n")
+
+
+def test_header_constants():
+    from hp_vae_gan_amd import ops
+    assert (ops.PACK_BATCH_MAX, hplib.LOG_MAX_K, ops.SN_BATCH_MAX) == (16, 16, 8)
+    assert ctypes.sizeof(hplib.ScalarPtrs) == 16 * ctypes.sizeof(ctypes.c_void_p)
+    with open(hplib.HEADER_PATH) as f:
+        consts = hplib.parse_header(f.read())[1]
+    assert consts["HPVG_PACK_BATCH_MAX"] == 16 and consts["HPVG_LOG_MAX_K"] == 16 and consts["HPVG_SN_BATCH_MAX"] == 8
+    assert {k: v for k, v in consts.items() if k.startswith("HPVG_ERR_")} == \
+        {"HPVG_ERR_ARG": -1, "HPVG_ERR_WORKSPACE": -2, "HPVG_ERR_UNSUPPORTED": -3, "HPVG_ERR_LAUNCH": -4}
+    with pytest.raises(RuntimeError, match="hpvg_conv_fwd_plan failed: HPVG_ERR_ARG"):    # call() prints the header's name of the code
+        hplib.call("hpvg_conv_fwd_plan", 1, 1, 1, 1, 1, 1, 2, (ctypes.c_int * 10)())
 
 
 def test_size_queries_and_plans_run_without_gpu():

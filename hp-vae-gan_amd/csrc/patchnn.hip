@@ -16,6 +16,17 @@
 //      bits, so the result is independent of the launch geometry and of timing, and ties resolve to the smallest index.
 //   3. patchnn_unpack_kernel: key -> d2, nn.
 //
+// Subset search (the patch inpainting of generate_patchnn --mask: only the patches that overlap the hole are queries, only the
+// patches that avoid it are keys): either side may bring an ascending int32 list of grid indices.  The pack gathers only the
+// listed patches (row i of the matrix is grid patch sel[i], clamped into the grid, so nothing outside a volume is ever read),
+// kernel 2 runs unchanged on the compacted matrices, whose sizes - and the workspace - follow the lists' lengths, and
+// patchnn_unpack_subset_kernel scatters row i's key to d2 / nn [qsel[i]] with the winner translated back through rsel, after
+// patchnn_fill_kernel has written -1 to every entry of the full-grid outputs.  Compacted rows keep the lists' order, so the
+// smallest compacted index among equals is the smallest grid index.
+//
+// Mask count: patch_mask_count_kernel, one thread per patch of a strided grid, counts the nonzero bytes of a uint8 [T][H][W]
+// mask under the patch (which patches overlap a hole, which avoid it).
+//
 // Weighted search (the patch nearest-neighbour generator's completeness normalisation, GPNN): score = float32(d2) * w_j with a
 // per-reference-patch weight.  patchnn_min_kernel<true> is the same tile with another epilogue: |q_i|^2 is no longer constant
 // along a row of scores, so the epilogue forms the whole d2 = |q_i|^2 + |r_j|^2 - 2 acc in int32 (the row norms of the tile
@@ -73,6 +84,8 @@ struct PnnGeom {
   PnnSide q, r;
   int pt, ph, pw;
   int D, Dp;
+  long mq, mr;        // rows of the two packed matrices: the grids' patches, or the lengths of the subset search's lists
+  long mqpad, mrpad;  // padded to PNN_TILE
   size_t off_qmat, off_rmat, off_qn, off_rn, off_keys, bytes;
 };
 
@@ -99,6 +112,23 @@ inline bool pnn_patch_ok(const int* patch) {
   return d * 65025.0 < 2147483648.0;
 }
 
+// the workspace of a search over mq query rows and mr reference rows
+inline void pnn_layout(PnnGeom& g, long mq, long mr) {
+  g.mq = mq; g.mr = mr;
+  g.mqpad = (mq + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
+  g.mrpad = (mr + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
+  size_t o = 0;
+  g.off_qmat = o; o = pnn_align(o + (size_t)g.mqpad * g.Dp);
+  g.off_rmat = o; o = pnn_align(o + (size_t)g.mrpad * g.Dp);
+  g.off_qn = o; o = pnn_align(o + (size_t)g.mqpad * 4);
+  g.off_rn = o; o = pnn_align(o + (size_t)g.mrpad * 4);
+  g.off_keys = o; o = pnn_align(o + (size_t)g.mqpad * 8);
+  g.bytes = o;
+}
+
+// a list's length for the layout: the grid's count for a null list (given == false), 0 for a length the call refuses
+inline long pnn_sel_rows(bool given, long n, long N) { return !given ? N : (n < 1 || n > N ? 0 : n); }
+
 inline bool pnn_geom(PnnGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
                      const int* rstride) {
   if (!pnn_patch_ok(patch)) return false;
@@ -106,13 +136,7 @@ inline bool pnn_geom(PnnGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr,
   g.pt = patch[0]; g.ph = patch[1]; g.pw = patch[2];
   g.D = 3 * g.pt * g.ph * g.pw;
   g.Dp = (g.D + PNN_BK - 1) / PNN_BK * PNN_BK;
-  size_t o = 0;
-  g.off_qmat = o; o = pnn_align(o + (size_t)g.q.Npad * g.Dp);
-  g.off_rmat = o; o = pnn_align(o + (size_t)g.r.Npad * g.Dp);
-  g.off_qn = o; o = pnn_align(o + (size_t)g.q.Npad * 4);
-  g.off_rn = o; o = pnn_align(o + (size_t)g.r.Npad * 4);
-  g.off_keys = o; o = pnn_align(o + (size_t)g.q.Npad * 8);
-  g.bytes = o;
+  pnn_layout(g, g.q.N, g.r.N);
   return true;
 }
 
@@ -141,20 +165,27 @@ inline bool ppj_geom(PpjGeom& g, int T, int H, int W, const int* patch, const in
 }
 
 // One wave per patch row: lane l writes the 4-byte words l, l + 64, ... of the row (zeros past D) and the wave sums the
-// squares.  Rows past N (tile padding) are all zeros.
+// squares.  Rows past `rows` (tile padding) are all zeros.  sel == nullptr: row i is patch i of the grid (rows = s.N).  Otherwise
+// row i is patch sel[i] (the gather of the subset search; rows = the list's length), clamped into [0, s.N).
 __global__ __launch_bounds__(256) void patchnn_pack_kernel(const unsigned char* __restrict__ vol, signed char* __restrict__ mat,
                                                             int* __restrict__ norms, unsigned long long* __restrict__ keys,
-                                                            PnnSide s, int ph, int pw, int D, int Dp) {
+                                                            PnnSide s, const int* __restrict__ sel, long rows, long rows_pad, int ph,
+                                                            int pw, int D, int Dp) {
   const int lane = threadIdx.x & 63;
   const int run = pw * 3;  // contiguous bytes of one patch line
   const long wave0 = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  for (long row = wave0; row < s.Npad; row += (long)gridDim.x * 4) {
+  for (long row = wave0; row < rows_pad; row += (long)gridDim.x * 4) {
     unsigned* out = (unsigned*)(mat + row * Dp);
     int sq = 0;
-    if (row < s.N) {
-      const int gx = (int)(row % s.nX);
-      const int gy = (int)((row / s.nX) % s.nY);
-      const int gt = (int)(row / ((long)s.nX * s.nY));
+    if (row < rows) {
+      long p = row;
+      if (sel) {
+        p = sel[row];
+        p = p < 0 ? 0 : (p >= s.N ? s.N - 1 : p);
+      }
+      const int gx = (int)(p % s.nX);
+      const int gy = (int)((p / s.nX) % s.nY);
+      const int gt = (int)(p / ((long)s.nX * s.nY));
       const unsigned char* base = vol + (((long)gt * s.st * s.H + (long)gy * s.sy) * s.W + (long)gx * s.sx) * 3;
       for (int w = lane; w < Dp / 4; w += 64) {
         unsigned word = 0;
@@ -389,6 +420,58 @@ __global__ __launch_bounds__(256) void patchnn_unpack_weighted_kernel(const unsi
   }
 }
 
+// every entry of the subset search's full-grid outputs starts as "not selected"
+__global__ __launch_bounds__(256) void patchnn_fill_kernel(int* __restrict__ d2, int* __restrict__ nn, long N) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    d2[i] = -1;
+    nn[i] = -1;
+  }
+}
+
+// key of compacted row i -> d2, nn at grid patch qsel[i] (i itself for a null list), the winner's compacted index translated to
+// its grid index rsel[j].  Both lists are clamped as the pack clamped them, so no write leaves the outputs and nn names the
+// patch that was compared.  A key nobody lowered (no such row while mr >= 1) gives -1, -1.
+__global__ __launch_bounds__(256) void patchnn_unpack_subset_kernel(const unsigned long long* __restrict__ keys,
+                                                                     const int* __restrict__ qsel, const int* __restrict__ rsel,
+                                                                     int* __restrict__ d2, int* __restrict__ nn, long mq, long Nq, long mr,
+                                                                     long Nr) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < mq; i += (long)gridDim.x * 256) {
+    const unsigned long long k = keys[i];
+    long o = i;
+    if (qsel) {
+      o = qsel[i];
+      o = o < 0 ? 0 : (o >= Nq ? Nq - 1 : o);
+    }
+    long j = (long)(unsigned)(k & 0xffffffffull);
+    const bool none = k == ~0ull || j >= mr;
+    if (!none && rsel) {
+      j = rsel[j];
+      j = j < 0 ? 0 : (j >= Nr ? Nr - 1 : j);
+    }
+    d2[o] = none ? -1 : (int)(unsigned)(k >> 32);
+    nn[o] = none ? -1 : (int)j;
+  }
+}
+
+// One thread per patch of the strided grid: the nonzero bytes of mask [T][H][W] under it.  Neighbouring threads read
+// neighbouring bytes, and every byte is read from the cache by the up to pt * ph * pw patches that cover it.
+__global__ __launch_bounds__(256) void patch_mask_count_kernel(const unsigned char* __restrict__ mask, int* __restrict__ count, PnnSide s,
+                                                                int pt, int ph, int pw) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < s.N; i += (long)gridDim.x * 256) {
+    const int gx = (int)(i % s.nX);
+    const int gy = (int)((i / s.nX) % s.nY);
+    const int gt = (int)(i / ((long)s.nX * s.nY));
+    const unsigned char* base = mask + ((long)gt * s.st * s.H + (long)gy * s.sy) * s.W + (long)gx * s.sx;
+    int c = 0;
+    for (int dt = 0; dt < pt; ++dt)
+      for (int dy = 0; dy < ph; ++dy) {
+        const unsigned char* line = base + ((long)dt * s.H + dy) * s.W;
+        for (int dx = 0; dx < pw; ++dx) c += line[dx] != 0;
+      }
+    count[i] = c;
+  }
+}
+
 // One thread per output voxel (3 channels).  Along each axis the query-grid patches that cover coordinate c are
 // g in [ceil((c - p + 1) / s), floor(c / s)] clipped to the grid, at offset d = c - g s inside the patch.
 __global__ __launch_bounds__(256) void patch_vote_kernel(const unsigned char* __restrict__ v, const int* __restrict__ nn,
@@ -603,8 +686,9 @@ size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, con
 namespace {
 
 // pack both sides, the min kernel, unpack.  rweight == nullptr: d2 / nn into out0 (int); otherwise score / nn, out0 (float).
-int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r, const float* rweight, void* out0, int* nn, void* ws,
-               void* stream) {
+// qsel / rsel (unweighted only): the subset search's lists, g laid out for their lengths; both null is the whole-grid search.
+int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r, const int* qsel, const int* rsel, const float* rweight,
+               void* out0, int* nn, void* ws, void* stream) {
   char* w = (char*)ws;
   signed char* qmat = (signed char*)(w + g.off_qmat);
   signed char* rmat = (signed char*)(w + g.off_rmat);
@@ -612,12 +696,13 @@ int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r,
   int* rn = (int*)(w + g.off_rn);
   unsigned long long* keys = (unsigned long long*)(w + g.off_keys);
   hipStream_t st = (hipStream_t)stream;
-  const long qblocks = g.q.Npad / 4 < 16384 ? g.q.Npad / 4 : 16384;
-  const long rblocks = g.r.Npad / 4 < 16384 ? g.r.Npad / 4 : 16384;
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)qblocks), dim3(256), 0, st, q, qmat, qn, keys, g.q, g.ph, g.pw, g.D, g.Dp);
+  const long qblocks = g.mqpad / 4 < 16384 ? g.mqpad / 4 : 16384;
+  const long rblocks = g.mrpad / 4 < 16384 ? g.mrpad / 4 : 16384;
+  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)qblocks), dim3(256), 0, st, q, qmat, qn, keys, g.q, qsel, g.mq, g.mqpad, g.ph,
+                     g.pw, g.D, g.Dp);
   hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)rblocks), dim3(256), 0, st, r, rmat, rn, (unsigned long long*)nullptr, g.r,
-                     g.ph, g.pw, g.D, g.Dp);
-  const long nrt = g.q.Npad / PNN_TILE, nct = g.r.Npad / PNN_TILE;
+                     rsel, g.mr, g.mrpad, g.ph, g.pw, g.D, g.Dp);
+  const long nrt = g.mqpad / PNN_TILE, nct = g.mrpad / PNN_TILE;
   long splits = (PNN_TARGET_WGS + nrt - 1) / nrt;
   if (splits > nct) splits = nct;
   if (splits < 1) splits = 1;
@@ -627,8 +712,16 @@ int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r,
   if (ub > 4096) ub = 4096;
   if (!rweight) {
     hipLaunchKernelGGL(patchnn_min_kernel<false>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
-                       (const float*)nullptr, keys, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
-    hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (int*)out0, nn, g.q.N);
+                       (const float*)nullptr, keys, g.mq, g.mr, g.Dp, (int)nct, (int)per);
+    if (!qsel && !rsel) {
+      hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (int*)out0, nn, g.q.N);
+    } else {
+      if (qsel) hipLaunchKernelGGL(patchnn_fill_kernel, dim3((unsigned)ub), dim3(256), 0, st, (int*)out0, nn, g.q.N);
+      long sb = (g.mq + 255) / 256;
+      if (sb > 4096) sb = 4096;
+      hipLaunchKernelGGL(patchnn_unpack_subset_kernel, dim3((unsigned)sb), dim3(256), 0, st, keys, qsel, rsel, (int*)out0, nn, g.mq,
+                         g.q.N, g.mr, g.r.N);
+    }
   } else {
     hipLaunchKernelGGL(patchnn_min_kernel<true>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
                        rweight, keys, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
@@ -646,7 +739,7 @@ int hpvg_patchnn_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsign
   PnnGeom g;
   if (!q || !r || !d2 || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
   if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
-  return pnn_launch(g, q, r, nullptr, d2, nn, ws, stream);
+  return pnn_launch(g, q, r, nullptr, nullptr, nullptr, d2, nn, ws, stream);
 }
 
 int hpvg_patchnn_weighted_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
@@ -655,7 +748,40 @@ int hpvg_patchnn_weighted_u8(const unsigned char* q, int Tq, int Hq, int Wq, con
   PnnGeom g;
   if (!q || !r || !rweight || !score || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
   if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
-  return pnn_launch(g, q, r, rweight, score, nn, ws, stream);
+  return pnn_launch(g, q, r, nullptr, nullptr, rweight, score, nn, ws, stream);
+}
+
+size_t hpvg_patchnn_subset_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                                    const int* rstride, long nqsel, long nrsel) {
+  PnnGeom g;
+  if (!pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return 0;
+  const long mq = pnn_sel_rows(nqsel >= 0, nqsel, g.q.N), mr = pnn_sel_rows(nrsel >= 0, nrsel, g.r.N);
+  if (!mq || !mr) return 0;
+  pnn_layout(g, mq, mr);
+  return g.bytes;
+}
+
+int hpvg_patchnn_subset_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                           const int* patch, const int* qstride, const int* rstride, const int* qsel, long nqsel, const int* rsel,
+                           long nrsel, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream) {
+  PnnGeom g;
+  if (!q || !r || !d2 || !nn || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
+  const long mq = pnn_sel_rows(qsel != nullptr, nqsel, g.q.N), mr = pnn_sel_rows(rsel != nullptr, nrsel, g.r.N);
+  if (!mq || !mr) return HPVG_ERR_ARG;
+  pnn_layout(g, mq, mr);
+  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+  return pnn_launch(g, q, r, qsel, rsel, nullptr, d2, nn, ws, stream);
+}
+
+int hpvg_patch_mask_count_u8(const unsigned char* mask, int T, int H, int W, const int* patch, const int* stride, int* count,
+                             void* stream) {
+  PnnSide s;
+  if (!mask || !count || !pnn_patch_ok(patch) || !pnn_side(s, T, H, W, patch, stride)) return HPVG_ERR_ARG;
+  long blocks = (s.N + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(patch_mask_count_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mask, count, s, patch[0],
+                     patch[1], patch[2]);
+  return hpvg_launch_status();
 }
 
 int hpvg_patch_vote_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
@@ -710,7 +836,7 @@ int hpvg_patchproj_hist_u8(const unsigned char* vol, int T, int H, int W, const 
   hipStream_t st = (hipStream_t)stream;
   const long pblocks = g.s.Npad / 4 < 16384 ? g.s.Npad / 4 : 16384;
   hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)pblocks), dim3(256), 0, st, vol, mat, (int*)nullptr,
-                     (unsigned long long*)nullptr, g.s, g.ph, g.pw, g.D, g.Dp);
+                     (unsigned long long*)nullptr, g.s, (const int*)nullptr, g.s.N, g.s.Npad, g.ph, g.pw, g.D, g.Dp);
   long dblocks = (g.Ppad * (g.Dp / 4) + 255) / 256;
   if (dblocks > 4096) dblocks = 4096;
   hipLaunchKernelGGL(patchproj_pack_dirs_kernel, dim3((unsigned)dblocks), dim3(256), 0, st, dirs, dmat, P, g.Ppad, g.D, g.Dp);

@@ -1,6 +1,7 @@
 """`python -m hp_vae_gan_amd.generate_patchnn --exp-dir run/<clip>/<checkname>/experiment_<n>` (or `--video-path clip.npy --out
 dir`, `--image-path img.png --out dir`): training-free samples of the clip by coarse-to-fine patch nearest neighbours (GPNN /
-VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json."""
+VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json.  With `--mask hole.npy` the samples are completions of
+the masked region of the clip (patch inpainting) and every other voxel stays as it is."""
 import argparse
 import json
 import math
@@ -12,6 +13,7 @@ import torch
 
 from . import ops
 from . import utils as hp_utils
+from . import datasets
 from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume, write_samples
 
 
@@ -47,6 +49,10 @@ def generate_patchnn_parser():
                    'volume\'s; another size retargets)')
     p.add_argument('--save-levels', action='store_true', help='also write levels.npz: the real pyramid (level_<l>) and the blurred '
                    'keys of every level above the coarsest (keys_<l>)')
+    p.add_argument('--mask', default=None, help='fill a hole instead of sampling the whole volume: a mask of the real volume\'s '
+                   '(T, H, W) (.npy [T,H,W] / [H,W] bool or uint8, or [...,3], an image file or a frame directory; nonzero = hole). '
+                   'Only patches that overlap the hole are searched, only patches that avoid it answer, and voxels outside the '
+                   'hole are kept; the search is the plain nearest neighbour (--alpha is not used)')
     return p
 
 
@@ -156,15 +162,188 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
     return (q[0] if image else q), score
 
 
+# Patch inpainting (the hole-filling application of GPNN, after Wexler et al.'s space-time completion): the same coarse-to-fine
+# steps, but at every level only the patches that overlap the hole are queries, only the patches that avoid it are keys
+# (ops.patch_nn_subset: the contraction shrinks to |queries| x |keys|), and only the hole's voxels take the vote.
+def patchnn_mask_resize(mask, size):
+    """A bool mask [T,H,W] (torch tensor on any device, or numpy array) at another (T, H, W) with the same T, in exact integer
+    arithmetic and separable: along an axis of S source and O output positions, output o is connected to source i iff
+    |i (O - 1) - o (S - 1)| < max(O - 1, S - 1) (every pair when O or S is 1), and an output voxel is set iff some connected
+    source voxel - connected along both axes - is set.  Equal sizes give the mask itself; the connected set holds floor and
+    ceil of the align-corners source coordinate o (S - 1) / (O - 1), i.e. every voxel the linear resize of the volume reads
+    for that output; and when downsizing every source is connected to some output, so a set voxel never vanishes."""
+    if isinstance(mask, np.ndarray):
+        return patchnn_mask_resize(torch.from_numpy(np.ascontiguousarray(mask)), size).numpy()
+    size = tuple(int(e) for e in size)
+    if mask.dim() != 3 or mask.dtype != torch.bool or len(size) != 3 or size[0] != mask.shape[0] or min(size) < 1:
+        raise ValueError("patchnn_mask_resize: a bool [T,H,W] mask and a (T, H, W) with the same T, got %s %s -> %s"
+                         % (mask.dtype, tuple(mask.shape), size))
+    out = mask
+    for axis in (1, 2):
+        S, O = int(out.shape[axis]), size[axis]
+        if S == O:
+            continue
+        i, o = np.arange(S, dtype=np.int64)[None, :], np.arange(O, dtype=np.int64)[:, None]
+        conn = np.abs(i * (O - 1) - o * (S - 1)) < max(O - 1, S - 1) if min(O, S) > 1 else np.ones((O, S), bool)
+        lo, hi = conn.argmax(1), S - conn[:, ::-1].argmax(1)      # the connected sources of o are the run [lo, hi)
+        assert (conn.sum(1) == hi - lo).all() and (hi > lo).all()
+        pre = torch.zeros([e + (a == axis) for a, e in enumerate(out.shape)], dtype=torch.int32, device=out.device)
+        pre.narrow(axis, 1, S).copy_(torch.cumsum(out.to(torch.int32), axis))
+        hi_t = torch.from_numpy(hi).to(out.device)
+        lo_t = torch.from_numpy(lo).to(out.device)
+        out = (pre.index_select(axis, hi_t) - pre.index_select(axis, lo_t)) > 0
+    return out.contiguous()
+
+
+def _flat_i32(cond):
+    return torch.nonzero(cond.reshape(-1)).reshape(-1).to(torch.int32)
+
+
+def patchnn_inpaint_plan(mask, sizes, patch):
+    """What the levels of patchnn_inpaint need of the mask [T,H,W] (bool, on the device), one dict per level: `mask` = M_l, the
+    mask at sizes[l] (patchnn_mask_resize of the full mask; the finest is the mask itself); `qsel` = the patches that overlap
+    M_l, the queries; `rsel` = the patches that avoid it, the keys of an ordinary step; `rsel_first` (l > 0) = the patches
+    that avoid B_l = M_l | resize(M_{l-1}), the keys of the level's first step, whose key volume is real level l-1 resized: a
+    voxel of it is clean only where every voxel that resize read was known.  All three are ascending flat int32 grid
+    indices.  An empty key set raises ValueError."""
+    plan = []
+    for l, size in enumerate(sizes):
+        M = patchnn_mask_resize(mask, size)
+        c = ops.patch_mask_count(M.to(torch.uint8), patch).reshape(-1)
+        lv = {"mask": M, "qsel": _flat_i32(c > 0), "rsel": _flat_i32(c == 0)}
+        if l > 0:
+            B = M | patchnn_mask_resize(plan[-1]["mask"], size)
+            lv["rsel_first"] = _flat_i32(ops.patch_mask_count(B.to(torch.uint8), patch) == 0)
+        if any(lv[k].numel() == 0 for k in lv if k.startswith("rsel")):
+            raise ValueError("patchnn_inpaint: the hole leaves no whole patch at level %d %s" % (l, tuple(size)))
+        if lv["qsel"].numel() == 0:
+            raise ValueError("patchnn_inpaint: the mask is empty")
+        plan.append(lv)
+    return plan
+
+
+def patchnn_inpaint_step(query, keys, values, mask, patch, qsel, rsel, return_score=False):
+    """One inpainting step on uint8 volumes [T,H,W,3]: nn = for the query patches qsel (those that overlap the hole) the nearest
+    of the key patches rsel (those that avoid it), voted = the vote of the value patches nn with the query as fallback, and the
+    result takes voted inside the bool mask [T,H,W] and the query elsewhere.  return_score: also the mean d2 of the queries."""
+    d2, nn = ops.patch_nn_subset(query, keys, patch, qsel, rsel)
+    voted = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query)
+    out = torch.where(mask[..., None], voted, query)
+    if return_score:
+        return out, float(d2.reshape(-1)[qsel.long()].to(torch.float64).mean())
+    return out
+
+
+def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, seed=0, index=0, pyramid=None,
+                    return_levels=False):
+    """One completion of the hole `mask` (bool [T,H,W], images [H,W]; True = hole) of the uint8 device volume `real` ([T,H,W,3];
+    images [H,W,3]) -> (sample, mean d2 of the last step's queries[, every level's result]).  Sizes, real levels and blurred
+    keys are patchnn_synthesize's.  The coarsest guess is real level 0 with the hole set to the per-channel mean of the known
+    voxels ((2 sum + n) // (2 n)) plus noise * 255 * N(0, 1), rounded and clamped; the noise is drawn for the whole volume
+    under torch.manual_seed(seed + index) as patchnn_synthesize draws it.  Every step is patchnn_inpaint_step with the level's
+    lists (patchnn_inpaint_plan): the plain nearest neighbour - a completeness term would pull every key of the clip into the
+    hole.  Between levels the hole is the previous result resized and everything else real level l.  pyramid: a
+    (sizes, levels, keys) or (sizes, levels, keys, plan) tuple to reuse between samples."""
+    image = real.dim() == 3
+    vol = real[None] if image else real
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != tuple(real.shape[:-1]) or \
+            mask.device != real.device:
+        raise ValueError("patchnn_inpaint: mask must be bool %s on %s, got %s %s on %s"
+                         % (tuple(real.shape[:-1]), real.device, getattr(mask, "dtype", type(mask)), tuple(getattr(mask, "shape", ())),
+                            getattr(mask, "device", None)))
+    mask = mask[None] if image else mask
+    patch = tuple(patch) if patch else default_patch(not image)
+    if pyramid is None:
+        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
+        pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+    sizes, levels, keys = pyramid[:3]
+    plan = pyramid[3] if len(pyramid) > 3 else patchnn_inpaint_plan(mask, sizes, patch)
+    iters = max(int(iters), 1)
+    M = plan[0]["mask"][..., None]
+    known = (~M).to(torch.int64)
+    n = known.sum()
+    mean = (2 * (levels[0].to(torch.int64) * known).sum((0, 1, 2)) + n) // (2 * n)
+    fill = mean.to(torch.float32).expand(levels[0].shape)
+    if noise:
+        torch.manual_seed(int(seed) + int(index))
+        with ops.noise_stream(vol.device):
+            z = ops.normal_(torch.empty(levels[0].shape, dtype=torch.float32, device=vol.device))
+        fill = fill + (float(noise) * 255.0) * z
+    q = torch.where(M, torch.round(fill).clamp_(0, 255).to(torch.uint8), levels[0])
+    score, results = None, []
+    for l, lv in enumerate(plan):
+        if l > 0:
+            q = torch.where(lv["mask"][..., None], _resize_u8(q, sizes[l]), levels[l])
+        for it in range(iters):
+            first = l > 0 and it == 0
+            last = l == len(plan) - 1 and it == iters - 1
+            q = patchnn_inpaint_step(q, keys[l] if first else levels[l], levels[l], lv["mask"], patch, lv["qsel"],
+                                     lv["rsel_first"] if first else lv["rsel"], return_score=last)
+            if last:
+                q, score = q
+        results.append(q[0] if image else q)
+    if return_levels:
+        return results[-1], score, results
+    return results[-1], score
+
+
+def mask_forms(path):
+    """Every [T,H,W] bool reading of a mask input, as host arrays: a .npy [T,H,W] or [H,W] (bool or uint8) as it is, and an
+    input with a last axis of 3 ([...,3] .npy, an image file, a frame directory) with any nonzero channel as hole.  An array
+    [H,W,3] has both readings; the real volume's shape decides between them (pick_mask).  Another dtype or rank ends the
+    program."""
+    ra = datasets.load_frames(path)
+    if ra.dtype not in (np.bool_, np.uint8):
+        raise SystemExit("generate_patchnn: --mask must be bool or uint8, got {} {}".format(ra.dtype, ra.shape))
+    forms = ([ra] if ra.ndim in (2, 3) else []) + ([ra.any(-1)] if ra.ndim in (3, 4) and ra.shape[-1] == 3 else [])
+    if not forms:
+        raise SystemExit("generate_patchnn: --mask must be [T,H,W], [H,W] or either with a last axis of 3, got {}".format(ra.shape))
+    return [np.ascontiguousarray((m[None] if m.ndim == 2 else m) != 0) for m in forms]
+
+
+def pick_mask(forms, shape):
+    """The reading of mask_forms with the real volume's (T, H, W) = shape; none ends the program."""
+    for m in forms:
+        if tuple(m.shape) == tuple(shape):
+            return m
+    raise SystemExit("generate_patchnn: --mask must have the real volume's shape {}, got {}".format(
+        tuple(shape), " or ".join(str(tuple(m.shape)) for m in forms)))
+
+
+def load_mask(path, shape):
+    """The hole mask at `path` of a volume of (T, H, W) = shape as a host bool array [T,H,W] (mask_forms, pick_mask)."""
+    return pick_mask(mask_forms(path), shape)
+
+
+def _refuse_trivial_mask(forms):
+    if all(not m.any() for m in forms) or all(m.all() for m in forms):
+        raise SystemExit("generate_patchnn: --mask is {}".format("empty" if not forms[0].any() else "all hole"))
+
+
 def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
-                     min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False):
+                     min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None):
     """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
-    patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample)."""
+    patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample).  mask: the
+    path of a hole mask of the real volume; the samples are then completions of the hole (patchnn_inpaint), land in
+    <exp-dir>/eval/samples_patchinpaint by default, and patchnn.json also records the mask, its voxels and per level the query
+    and key patches."""
     given = [a for a in (exp_dir, video_path, image_path) if a is not None]
     if len(given) != 1:
         raise SystemExit("generate_patchnn: give exactly one of --exp-dir, --video-path and --image-path")
     if exp_dir is None and out is None:
         raise SystemExit("generate_patchnn: --video-path / --image-path need --out")
+    hole = forms = None
+    if mask is not None:
+        # what the mask alone decides, before the device is touched.  The mask has the real volume's shape (checked below, once
+        # that is known), so a --size that no reading of the mask has cannot be the real size; and a mask is refused as empty
+        # or all hole here only when every reading that can still be the real volume's is.
+        forms = mask_forms(mask)
+        if size is not None:
+            forms = [m for m in forms if tuple(m.shape) == tuple(size)]
+            if not forms:
+                raise SystemExit("generate_patchnn: --mask fills a hole of the real volume: --size {} is not the mask's {}".format(
+                    tuple(size), " or ".join(str(tuple(m.shape)) for m in mask_forms(mask))))
+        _refuse_trivial_mask(forms)
     device = gpu_device()
     fps = 10
     if exp_dir is not None:
@@ -172,7 +351,7 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         real = real_volume(opt, None, device)
         if opt.dims == 3:
             fps = hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[0]
-        out = out or os.path.join(exp_dir, 'eval', 'samples_patchnn')
+        out = out or os.path.join(exp_dir, 'eval', 'samples_patchinpaint' if mask is not None else 'samples_patchnn')
     else:
         real = load_u8_frames(video_path or image_path, device, image_path is not None,
                               "generate_patchnn: the input must be uint8 [N,H,W,3] or [H,W,3]", ranks=(3, 4))
@@ -189,6 +368,14 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
     if image and size[0] != 1:
         raise SystemExit("generate_patchnn: an image's --size has T = 1")
     pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+    if mask is not None:
+        hole = pick_mask(forms, vol.shape[:3])
+        _refuse_trivial_mask([hole])
+        hole = torch.from_numpy(hole).to(device)
+        try:
+            pyramid = pyramid + (patchnn_inpaint_plan(hole, sizes, patch),)
+        except ValueError as e:
+            raise SystemExit("generate_patchnn: {}".format(e))
     os.makedirs(out, exist_ok=True)
     if save_levels:
         np.savez(os.path.join(out, 'levels.npz'), **{"level_%d" % l: v.cpu().numpy() for l, v in enumerate(pyramid[1])},
@@ -198,7 +385,10 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
     for i in range(num_samples):
         e0.record()
         try:
-            smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid)
+            if mask is not None:
+                smp, score = patchnn_inpaint(vol, hole, patch, ratio, min_size, iters, noise, seed, i, pyramid)
+            else:
+                smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
         e1.record()
@@ -214,6 +404,10 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
             "level_sizes": [list(s) for s in sizes], "seconds_per_sample": seconds, "final_score_per_sample": scores,
             "final_score": "mean over the sample's patches of the last step's minimum: d2 / (alpha D 255^2 + the key's distance "
                            "to its nearest sample patch); plain d2 for alpha = inf"}
+    if mask is not None:
+        info.update({"mask": os.path.abspath(mask), "hole_voxels": int(hole.sum()), "alpha": "inf",
+                     "active_patches": [int(lv["qsel"].numel()) for lv in pyramid[3]],
+                     "valid_keys": [int(lv["rsel"].numel()) for lv in pyramid[3]]})
     with open(os.path.join(out, 'patchnn.json'), 'w') as f:
         json.dump(info, f, indent=1, sort_keys=True)
     print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
@@ -224,7 +418,7 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
 def main(argv=None):
     a = generate_patchnn_parser().parse_args(argv)
     generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
-                     a.alpha, a.noise, a.size, a.save_levels)
+                     a.alpha, a.noise, a.size, a.save_levels, a.mask)
     return 0
 
 

@@ -1388,6 +1388,66 @@ def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rs
     return score, nn
 
 
+def _patch_sel(sel, name, N, device):
+    """A subset search's list as launch arguments (pointer, count, the tensor kept alive); None is the whole grid.  Checked on
+    the device with one reduction: int32, 1-D, non-empty, strictly ascending, within [0, N)."""
+    if sel is None:
+        return None, 0, None
+    if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < 1 or sel.device != device:
+        raise RuntimeError("patch_nn_subset: %s must be a non-empty 1-D int32 tensor on %s, got %s %s on %s"
+                           % (name, device, getattr(sel, "dtype", type(sel)), tuple(getattr(sel, "shape", ())),
+                              getattr(sel, "device", None)))
+    sel = _c(sel)
+    if not bool((sel[0] >= 0) & (sel[-1] < N) & (sel[1:] > sel[:-1]).all()):
+        raise RuntimeError("patch_nn_subset: %s must be strictly ascending with every entry in [0, %d)" % (name, N))
+    return ptr(sel), sel.numel(), sel
+
+
+def patch_nn_subset(query_u8, ref_u8, patch, qsel=None, rsel=None, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """patch_nn over selected patches of both grids (hpvg_patchnn_subset_u8, i8 matrix cores; the search of patch inpainting):
+    qsel / rsel are 1-D int32 device tensors of flat grid indices (raster order), strictly ascending; None is the whole grid.
+    Only the selected patches are packed and compared.  Returns (d2, nn), int32, shaped as the query's patch grid: for a
+    selected query patch the smallest squared distance to a selected patch of ref and the smallest index IN REF'S GRID that
+    attains it; -1, -1 for every other patch (patch_vote skips those)."""
+    (q, r), image = _patch_volumes("patch_nn_subset", (("query", query_u8), ("ref", ref_u8)))
+    pa, qs, rs = _triple(patch, "patch", "patch_nn_subset"), _triple(qstride, "qstride", "patch_nn_subset"), \
+        _triple(rstride, "rstride", "patch_nn_subset")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
+    qp, nq, qkeep = _patch_sel(qsel, "qsel", counts[0], q.device)
+    rp, nr, rkeep = _patch_sel(rsel, "rsel", counts[1], q.device)
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    # the workspace query has no list pointers to tell a null list by: there a negative count stands for one (the search itself
+    # takes the null pointer and ignores the count)
+    nbytes = call("hpvg_patchnn_subset_ws_bytes", *qg, *rg, pa, qs, rs, nq if qsel is not None else -1, nr if rsel is not None else -1)
+    ws = _scratch(nbytes, q.device)
+    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
+    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
+    call("hpvg_patchnn_subset_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, qp, nq, rp, nr, ptr(d2), ptr(nn), *ws, stream())
+    if image:
+        d2, nn = d2[0], nn[0]
+    return d2, nn
+
+
+def patch_mask_count(mask_u8, patch, stride=(1, 1, 1)):
+    """For every patch of the strided grid of a uint8 device mask [T,H,W] (or [H,W]; nonzero = hole) the number of hole voxels
+    under it (hpvg_patch_mask_count_u8): int32, shaped as the patch grid, 0 for a patch that avoids the hole."""
+    m = mask_u8
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.uint8 or m.dim() not in (2, 3):
+        raise RuntimeError("patch_mask_count: mask must be uint8 [T,H,W] or [H,W], got %s %s"
+                           % (getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ()))))
+    image = m.dim() == 2
+    m = _c(m[None] if image else m)
+    pa, st = _triple(patch, "patch", "patch_mask_count"), _triple(stride, "stride", "patch_mask_count")
+    g = tuple(m.shape)
+    call("hpvg_patchnn_counts", *g, *g, pa, st, st, (ctypes.c_int * 3)())   # refuses bad arguments by name
+    grid = tuple((g[a] - pa[a]) // st[a] + 1 for a in range(3))
+    count = torch.empty(grid, dtype=torch.int32, device=m.device)
+    call("hpvg_patch_mask_count_u8", ptr(m), *g, pa, st, ptr(count), stream())
+    return count[0] if image else count
+
+
 def patch_vote_counts(out_shape, values_shape, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
     """(Nq, Nr, uncovered) of a patch_vote call: the patches of the output's grid, those of the values volume's grid, and the
     output voxels no patch of the output's grid covers, which take the fallback (hpvg_patch_vote_counts; host only)."""

@@ -288,6 +288,26 @@ int hpvg_patch_vote_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int
 /* host only: out3 = Nq, Nr, the number of output voxels that no patch of the query grid covers */
 int hpvg_patch_vote_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride, const int* rstride,
                            long* out3);
+/* The search over selected patches of both grids (patch inpainting, generate_patchnn --mask: the patches that overlap the hole
+ * against the patches that avoid it).  qsel / rsel: int32 lists of grid indices on the device, STRICTLY ASCENDING, nqsel /
+ * nrsel entries (host values).  A null list is the whole grid and its count is ignored; a non-null list with a count < 1 or
+ * > N is HPVG_ERR_ARG.  Only the listed patches are packed and compared, so the work and the workspace follow the counts.
+ * d2 / nn: int32 [Nq], the FULL query grid.  For a listed query patch d2 = the exact minimum over the listed reference patches
+ * and nn = the index IN r's GRID of the smallest listed patch that attains it; every other entry gets d2 = -1, nn = -1,
+ * written by the call, so hpvg_patch_vote_u8 skips it.  Independent of launch geometry and timing; both lists null: bit for
+ * bit hpvg_patchnn_u8.  Ascending and in-range entries are the caller's contract: an index is clamped into [0, N), so
+ * nothing outside a volume or an output is touched, and the result for such a list is unspecified. */
+/* host only: bytes of workspace for lists of nqsel / nrsel entries; a NEGATIVE count stands for a null list (then the result
+ * is hpvg_patchnn_ws_bytes()'s); 0 for a geometry hpvg_patchnn_u8 refuses and for a count of 0 or > N */
+size_t hpvg_patchnn_subset_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                                    const int* rstride, long nqsel, long nrsel);
+int hpvg_patchnn_subset_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                           const int* patch, const int* qstride, const int* rstride, const int* qsel, long nqsel, const int* rsel,
+                           long nrsel, int* d2, int* nn, void* ws, size_t ws_bytes, void* stream);
+/* count[i] = the nonzero bytes of mask [T][H][W] (uint8, on the device) under patch i of the strided grid, int32 [N], exact:
+ * 0 for a patch that avoids the hole.  Geometry refusals as for hpvg_patchnn_u8; no workspace. */
+int hpvg_patch_mask_count_u8(const unsigned char* mask, int T, int H, int W, const int* patch, const int* stride, int* count,
+                             void* stream);
 
 /* ---- evaluation: exact sliced Wasserstein distance between the patch distributions of two uint8 volumes (the SWD of PGGAN /
  * GPNN / GPDM with integer directions).  Patches, patch and stride as above.  dirs: int8 [P][D] on the device, entries in

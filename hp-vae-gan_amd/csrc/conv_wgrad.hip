@@ -1043,10 +1043,86 @@ struct WPlan {
   int g16; // conv_wgradw_kernel's 16-byte staging form (RS = the X row stride Tw + 8, QK = Th * Tw)
 };
 
-WPlan plan_wgrad_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+// ------------------------------------------------------------------------------------------------------------------ knobs
+// Every knob of the weight-gradient host path, read from the environment once, on first use.  The fields below the line are
+// what is in force: hpvg_conv_bwd_weight_wino_config rewrites them at run time (tests and A/B tools) from the env_* copies.
+struct WKnobs {
+  int wgrad3;          // HPVG_WGRAD3: 0 = never conv_wgrad3_kernel, 2 = always (tests), default = by size (wgrad3_wanted)
+  bool narrow2_off;    // HPVG_WGRAD_NARROW2=0: the first-generation narrow kernel for every head and tail
+  bool balance;        // HPVG_WGRAD_BALANCE=0: conv_wgrad_kernel's three time taps get the same number of slots (wgrad_slots)
+  int wch;             // HPVG_WGRADW_WCH=0: conv_wgradw_kernel's 4-byte form never stages whole channel rows per wave
+  // HPVG_WG2_ORDER: conv_wgradw2_kernel's walk over the tiles, 0 time-major, default 1 plane-major: same time, 1.9 instead of
+  // 3.4 GB of HBM traffic per stage-9 launch (profiles/r03_ab_wgrad2_order.txt)
+  int order;
+  int force16, force2; // development: HPVG_WG16_FORCE / HPVG_WG2_FORCE = "Th,Tw" restrict that search to the tile (Th * 1000 + Tw)
+  long min_tiles;      // HPVG_WGRADW2_MIN_TILES: wgradw2_wanted's threshold (< 0: its defaults)
+  int env_w2, env_g16, env_w8;   // as the process started: HPVG_WGRADW2 (default 0), HPVG_WGRADW_G16 (1), HPVG_WGRADW_W8 (1)
+  // ---- in force
+  // HPVG_WGRAD_WINO at start: 0 = never the Winograd weight gradient (the direct kernels: conv_wgrad_kernel / conv_wgrad3_kernel),
+  // anything else = EVERY wide layer (Cin > 4 and Cout > 4).  There is no size rule at this level: the one-axis kernel with the
+  // slot-grouped reduce wins at every pyramid stage, 2-D and 3-D (profiles/r02_perf_wgrad_wino.txt); what IS chosen by size is
+  // which Winograd kernel runs (wgradw2_wanted below).
+  int wino;
+  int w2;              // the two-axis kernel: 0 = by size, 1 = never, 2 = wherever it can run
+  int g16;             // conv_wgradw_kernel's 16-byte staging form where the width allows it
+  int w8;              // ... on eight waves (0: four)
+  bool four_byte_only, four_waves;   // modes 3 / 4 of hpvg_conv_bwd_weight_wino_config are in force
+  int gen;             // bumped when g16 changes: what the planner may pick has changed, the plan memo drops its entries
+};
+WKnobs& wknobs() {
+  static WKnobs knobs = [] {
+    auto num = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
+    auto tile = [](const char* name) { const char* e = getenv(name); int a = 0, b = 0; return e && sscanf(e, "%d,%d", &a, &b) == 2 ? a * 1000 + b : 0; };
+    WKnobs k{};
+    k.wgrad3 = (int)num("HPVG_WGRAD3", 1);
+    k.narrow2_off = num("HPVG_WGRAD_NARROW2", 1) == 0;
+    k.balance = num("HPVG_WGRAD_BALANCE", 1) != 0;
+    k.wch = (int)num("HPVG_WGRADW_WCH", 1);
+    k.order = (int)num("HPVG_WG2_ORDER", 1);
+    k.force16 = tile("HPVG_WG16_FORCE");
+    k.force2 = tile("HPVG_WG2_FORCE");
+    k.min_tiles = num("HPVG_WGRADW2_MIN_TILES", -1);
+    k.wino = (int)num("HPVG_WGRAD_WINO", 1);
+    k.w2 = k.env_w2 = (int)num("HPVG_WGRADW2", 0);
+    k.g16 = k.env_g16 = (int)num("HPVG_WGRADW_G16", 1);
+    k.w8 = k.env_w8 = (int)num("HPVG_WGRADW_W8", 1);
+    return k;
+  }();
+  return knobs;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- planners
+// Persistent slots of a plan, one workgroup per CU.  KT: the time taps that have workgroups of their own (conv_wgrad_kernel,
+// conv_wgradw_kernel, conv_wgradw2_kernel; 1 for conv_wgrad3_kernel, whose workgroups own all taps).  With `balance`, the 3 * S
+// workgroups of a block pair are split so that tiles-with-work per workgroup are equal: centre tap: ntiles / S1, outer taps:
+// ntiles * (T-1)/T / S0
+void wgrad_slots(WPlan& p, int B, int T, int KT, bool balance) {
+  if (!p.Th) return;
+  const long ntiles = (long)B * T * p.nth * p.ntw;
+  long cap = (long)HPVG_NUM_CU / ((long)KT * p.nob * p.ncb);
+  if (cap < 1) cap = 1;
+  p.S = (int)(ntiles < cap ? ntiles : cap);
+  p.S0 = p.S;
+  if (balance && KT == 3 && T >= 2 && p.S >= 2) {
+    const long Stot = 3L * p.S;
+    long S1 = (Stot * T + (3L * T - 2) / 2) / (3L * T - 2);
+    if (S1 > ntiles) S1 = ntiles;
+    long S0 = (Stot - S1) / 2;
+    if (S0 < 1) S0 = 1;
+    if (S0 > S1) S0 = S1;
+    p.S = (int)S1;
+    p.S0 = (int)S0;
+  }
+}
+
+// Tile plan of the direct kernels.  conv_wgrad_kernel: one time tap of a 64 x 64 channel-block pair per workgroup, two tile
+// buffers.  all_taps: conv_wgrad3_kernel, the same tile family under its own LDS budget (two dY tiles, four 32-channel X planes,
+// one row of zeros); S persistent workgroups per (64 output, 32 input channel) block pair.
+WPlan plan_direct_search(const WKnobs& k, int B, int Cin, int Cout, int T, int H, int W, int KT, bool all_taps) {
   WPlan best{};
   double best_cost = 1e300;
-  const int nob = hpvg_cdiv(Cout, 64), ncb = hpvg_cdiv(Cin, 64);
+  const int nob = hpvg_cdiv(Cout, 64), ncb = hpvg_cdiv(Cin, all_taps ? 32 : 64);
+  const int row_max = all_taps ? 256 : 512;              // (all_taps: one 256-lane DMA round per row)
   for (int Tw = 1; Tw <= W; ++Tw) {
     const int ntw = hpvg_cdiv(W, Tw);
     if (Tw != hpvg_cdiv(W, ntw)) continue;
@@ -1059,87 +1135,25 @@ WPlan plan_wgrad_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
       int XS = QK + 2 * RS + 4;                          // X row: reads reach QK-1 + 2*RS + 2
       if (XS < (Th + 2) * RS + 1) XS = (Th + 2) * RS + 1;
       XS |= 1;
-      if (DS > 512 || XS > 512) break;
-      const size_t lds = (size_t)2 * 64 * (DS + XS) * sizeof(float);  // two tile buffers
-      if (lds > 156 * 1024) break;
+      if (DS > row_max || XS > row_max) break;
+      const size_t lds = (all_taps ? (size_t)2 * 64 * DS + (size_t)4 * 32 * XS + XS : (size_t)2 * 64 * (DS + XS)) * sizeof(float);
+      if (lds > (all_taps ? 158 : 156) * 1024) break;
       const long ntiles = (long)B * T * nth * ntw;
-      // useful fraction of the K loop and per-tile fixed cost (barrier + pipeline segments)
-      const double work = (double)ntiles * (QK * 0.5 * 9.0 + 40.0);
+      // MFMAs of the K loop (its useful fraction) + per-tile fixed cost (barrier + pipeline segments)
+      const double work = (double)ntiles * (all_taps ? QK * 0.5 * 27.0 + 80.0 : QK * 0.5 * 9.0 + 40.0);
       if (work < best_cost) {
         best_cost = work;
         best = WPlan{Th, Tw, RS, DS, XS, QK, nth, ntw, 0, nob, ncb, lds};
       }
     }
   }
-  if (best.Th) {
-    const long ntiles = (long)B * T * best.nth * best.ntw;
-    long cap = (long)HPVG_NUM_CU / ((long)KT * nob * ncb);  // one persistent workgroup per CU
-    if (cap < 1) cap = 1;
-    best.S = (int)(ntiles < cap ? ntiles : cap);
-    best.S0 = best.S;
-    static const bool balance = [] { const char* e = getenv("HPVG_WGRAD_BALANCE"); return !e || atoi(e) != 0; }();
-    if (balance && KT == 3 && T >= 2 && best.S >= 2) {
-      // split the 3*S workgroups of a channel-block pair so that tiles-with-work per workgroup are equal:
-      // centre tap: ntiles / S1, outer taps: ntiles * (T-1)/T / S0
-      const long Stot = 3L * best.S;
-      long S1 = (Stot * T + (3L * T - 2) / 2) / (3L * T - 2);
-      if (S1 > ntiles) S1 = ntiles;
-      long S0 = (Stot - S1) / 2;
-      if (S0 < 1) S0 = 1;
-      if (S0 > S1) S0 = S1;
-      best.S = (int)S1;
-      best.S0 = (int)S0;
-    }
-  }
+  wgrad_slots(best, B, T, all_taps ? 1 : KT, !all_taps && k.balance);
   return best;
-}
-
-WPlan plan_wgrad(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  struct Key { int B, Cin, Cout, T, H, W, KT; };
-  struct Entry { Key k; WPlan p; bool used; };
-  constexpr int NSLOT = 2048;
-  static thread_local Entry cache[NSLOT];
-  static thread_local int filled = 0;
-  unsigned h = 2166136261u;
-  for (int v : {B, Cin, Cout, T, H, W, KT}) h = (h ^ (unsigned)v) * 16777619u;
-  for (int probe = 0; probe < NSLOT; ++probe) {
-    Entry& e = cache[(h + probe) & (NSLOT - 1)];
-    if (!e.used) {
-      const WPlan p = plan_wgrad_search(B, Cin, Cout, T, H, W, KT);
-      if (filled < NSLOT / 2) {
-        e.k = Key{B, Cin, Cout, T, H, W, KT}; e.p = p; e.used = true;
-        ++filled;
-      }
-      return p;
-    }
-    const Key& c = e.k;
-    if (c.B == B && c.Cin == Cin && c.Cout == Cout && c.T == T && c.H == H && c.W == W && c.KT == KT) return e.p;
-  }
-  return plan_wgrad_search(B, Cin, Cout, T, H, W, KT);
 }
 
 // Tile plan of conv_wgradw_kernel (Winograd along W): the tile family of conv_wgrad_kernel with an EVEN band width and row
 // stride, channel strides of 2 (mod 4) and the Winograd K loop's cost (12 MFMAs per 4 positions instead of 18).
-// persistent slots of a conv_wgradw_kernel plan
-void wgradw_slots(WPlan& best, int B, int T, int KT) {
-  if (!best.Th) return;
-  const long ntiles = (long)B * T * best.nth * best.ntw;
-  long cap = (long)HPVG_NUM_CU / ((long)KT * best.nob * best.ncb);  // one persistent workgroup per CU
-  if (cap < 1) cap = 1;
-  best.S = (int)(ntiles < cap ? ntiles : cap);
-  best.S0 = best.S;
-  if (KT == 3 && T >= 2 && best.S >= 2) {   // tiles-with-work per workgroup equal over the three time taps (plan_wgrad_search)
-    const long Stot = 3L * best.S;
-    long S1 = (Stot * T + (3L * T - 2) / 2) / (3L * T - 2);
-    if (S1 > ntiles) S1 = ntiles;
-    long S0 = (Stot - S1) / 2;
-    if (S0 < 1) S0 = 1;
-    if (S0 > S1) S0 = S1;
-    best.S = (int)S1;
-    best.S0 = (int)S0;
-  }
-}
-WPlan plan_wgradw_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+WPlan plan_wgradw4_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
   WPlan best{};
   double best_cost = 1e300;
   const int nob = hpvg_cdiv(Cout, 64), ncb = hpvg_cdiv(Cin, 64);
@@ -1169,23 +1183,14 @@ WPlan plan_wgradw_search(int B, int Cin, int Cout, int T, int H, int W, int KT) 
       }
     }
   }
-  wgradw_slots(best, B, T, KT);
+  wgrad_slots(best, B, T, KT, true);
   return best;
 }
 // the 16-byte staging form (conv_wgradw_kernel<.., G16>): W a multiple of 4, bands of a multiple of 4 columns, dY rows of Tw
 // floats, X rows of Tw + 8 from column w0 - 4; at most two 64-lane pieces per channel row and operand
-int g_wgradw_g16 = -1;
-int g_wgradw_w8 = -1;   // eight-wave form of the 16-byte kernel (HPVG_WGRADW_W8, hpvg_conv_bwd_weight_wino_config mode 4 = off)
-int g_wgradw_gen = 0;   // bumped when hpvg_conv_bwd_weight_wino_config changes what the planner may pick: drops the plan caches
-WPlan plan_wgradw16_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+WPlan plan_wgradw16_search(const WKnobs& k, int B, int Cin, int Cout, int T, int H, int W, int KT) {
   WPlan best{};
-  if (g_wgradw_g16 < 0) {
-    const char* e = getenv("HPVG_WGRADW_G16");
-    g_wgradw_g16 = e ? atoi(e) : 1;
-    const char* e8 = getenv("HPVG_WGRADW_W8");
-    g_wgradw_w8 = e8 ? atoi(e8) : 1;
-  }
-  if (W % 4 != 0 || !g_wgradw_g16) return best;
+  if (W % 4 != 0 || !k.g16) return best;
   double best_cost = 1e300;
   const int nob = hpvg_cdiv(Cout, 64), ncb = hpvg_cdiv(Cin, 64);
   int prev_tw = 0;
@@ -1203,65 +1208,26 @@ WPlan plan_wgradw16_search(int B, int Cin, int Cout, int T, int H, int W, int KT
       const size_t lds = (size_t)2 * 64 * (DS + XS) * sizeof(float);
       if (lds > 156 * 1024) break;
       const long ntiles = (long)B * T * nth * ntw;
-      double work = (double)ntiles * (QK * 0.25 * 12.0 + 40.0);
-      // development: HPVG_WG16_FORCE="Th,Tw" restricts the search to that tile
-      static const int force = [] { const char* e = getenv("HPVG_WG16_FORCE"); int a = 0, b = 0; return e && sscanf(e, "%d,%d", &a, &b) == 2 ? a * 1000 + b : 0; }();
-      if (force && force != Th * 1000 + Tw) continue;
+      const double work = (double)ntiles * (QK * 0.25 * 12.0 + 40.0);
+      if (k.force16 && k.force16 != Th * 1000 + Tw) continue;
       if (work < best_cost) {
         best_cost = work;
         best = WPlan{Th, Tw, RSx, DS, XS, QK, nth, ntw, 0, nob, ncb, lds, 0, 1};
       }
     }
   }
-  wgradw_slots(best, B, T, KT);
+  wgrad_slots(best, B, T, KT, true);
   return best;
-}
-WPlan plan_wgradw(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  struct Key { int B, Cin, Cout, T, H, W, KT; };
-  struct Entry { Key k; WPlan p; };
-  constexpr int NE = 256;
-  static thread_local Entry cache[NE];
-  static thread_local int filled = 0;
-  static thread_local int gen = 0;
-  if (gen != g_wgradw_gen) {
-    gen = g_wgradw_gen;
-    filled = 0;
-  }
-  for (int i = 0; i < filled; ++i) {
-    const Key& c = cache[i].k;
-    if (c.B == B && c.Cin == Cin && c.Cout == Cout && c.T == T && c.H == H && c.W == W && c.KT == KT) return cache[i].p;
-  }
-  WPlan p = plan_wgradw16_search(B, Cin, Cout, T, H, W, KT);
-  if (!p.Th) p = plan_wgradw_search(B, Cin, Cout, T, H, W, KT);
-  if (filled < NE) cache[filled++] = Entry{Key{B, Cin, Cout, T, H, W, KT}, p};
-  return p;
-}
-inline size_t wgradw_slab_bytes(const WPlan& p, int KT) { return (size_t)p.S * KT * p.nob * p.ncb * 12 * 4096 * sizeof(float); }
-// (+ the per-slot bias partials [S][nob][64] behind the slabs)
-inline size_t wgradw_ws_bytes(const WPlan& p, int KT) { return 256 + wgradw_slab_bytes(p, KT) + (size_t)p.S * p.nob * 64 * sizeof(float); }
-// HPVG_WGRAD_WINO (read once; hpvg_conv_bwd_weight_wino_config changes it at run time): 0 = never the Winograd weight
-// gradient (the direct kernels: conv_wgrad_kernel / conv_wgrad3_kernel), anything else = EVERY wide layer (Cin > 4 and Cout > 4).
-// There is no size rule at this level: the one-axis kernel with the slot-grouped reduce wins at every pyramid stage, 2-D and
-// 3-D (profiles/r02_perf_wgrad_wino.txt); what IS chosen by size is which Winograd kernel runs (wgradw2_wanted below).
-int g_wgradw_mode = -1;
-inline bool wgradw_wanted(const WPlan& p, int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (g_wgradw_mode < 0) {
-    const char* e = getenv("HPVG_WGRAD_WINO");
-    g_wgradw_mode = e ? atoi(e) : 1;
-  }
-  return g_wgradw_mode != 0 && p.Th != 0 && Cin > 4 && Cout > 4;
 }
 
 // Tile plan of conv_wgradw2_kernel (Winograd over H and W): the 16-byte staging form with an EVEN tile height (rows of quads)
 // and its K loop's cost (16 MFMAs per two quads = 8 positions).  Any W (W % 4 != 0: the kernel patches the one group per row
 // that straddles the right border).
-WPlan plan_wgradw2_search(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+WPlan plan_wgradw2_search(const WKnobs& k, int B, int Cin, int Cout, int T, int H, int W, int KT) {
   WPlan best{};
   double best_cost = 1e300;
   const int nob = hpvg_cdiv(Cout, 64), ncb = hpvg_cdiv(Cin, 64);
   int prev_tw = 0;
-  // development: HPVG_WG2_FORCE="Th,Tw" restricts the search to that tile
-  static const int force = [] { const char* e = getenv("HPVG_WG2_FORCE"); int a = 0, b = 0; return e && sscanf(e, "%d,%d", &a, &b) == 2 ? a * 1000 + b : 0; }();
   for (int ntw = hpvg_cdiv(W, 4); ntw >= 1; --ntw) {
     const int Tw = 4 * hpvg_cdiv(hpvg_cdiv(W, ntw), 4);
     if (Tw == prev_tw || (long)(ntw - 1) * Tw >= W) continue;
@@ -1269,7 +1235,7 @@ WPlan plan_wgradw2_search(int B, int Cin, int Cout, int T, int H, int W, int KT)
     const int RSx = Tw + 8;
     // bands of 4 / 8 columns stage twice their width in halo and lose to wider ones although they pad least (measured at
     // 5 x 57 x 102: the 10 x 8 tile the area rule picked 0.128 ms, 6 x 16 0.115, 4 x 24 0.105): only where nothing wider fits
-    if (Tw < 12 && W >= 24 && !force) continue;
+    if (Tw < 12 && W >= 24 && !k.force2) continue;
     for (int Th = 2; Th <= H + 3; Th += 2) {
       const int nth = hpvg_cdiv(H, Th);
       const int thb = 2 * hpvg_cdiv(hpvg_cdiv(H, nth), 2);       // balanced, even
@@ -1282,117 +1248,17 @@ WPlan plan_wgradw2_search(int B, int Cin, int Cout, int T, int H, int W, int KT)
       if (QK % 16 != 0) continue;                        // an even number of K steps (the kernel's loop body holds two)
       const long ntiles = (long)B * T * nth * ntw;
       const double work = (double)ntiles * (QK * 0.125 * 16.0 + 40.0);
-      if (force && force != Th * 1000 + Tw) continue;
+      if (k.force2 && k.force2 != Th * 1000 + Tw) continue;
       if (work < best_cost) {
         best_cost = work;
         best = WPlan{Th, Tw, RSx, DS, XS, QK, nth, ntw, 0, nob, ncb, lds, 0, 2};
       }
     }
   }
-  wgradw_slots(best, B, T, KT);
+  wgrad_slots(best, B, T, KT, true);
   return best;
 }
-WPlan plan_wgradw2(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  struct Key { int B, Cin, Cout, T, H, W, KT; };
-  struct Entry { Key k; WPlan p; };
-  constexpr int NE = 256;
-  static thread_local Entry cache[NE];
-  static thread_local int filled = 0;
-  for (int i = 0; i < filled; ++i) {
-    const Key& c = cache[i].k;
-    if (c.B == B && c.Cin == Cin && c.Cout == Cout && c.T == T && c.H == H && c.W == W && c.KT == KT) return cache[i].p;
-  }
-  const WPlan p = plan_wgradw2_search(B, Cin, Cout, T, H, W, KT);
-  if (filled < NE) cache[filled++] = Entry{Key{B, Cin, Cout, T, H, W, KT}, p};
-  return p;
-}
-inline size_t wgradw2_slab_bytes(const WPlan& p, int KT) { return (size_t)p.S * KT * p.nob * p.ncb * 16 * 4096 * sizeof(float); }
-inline size_t wgradw2_ws_bytes(const WPlan& p, int KT) { return 256 + wgradw2_slab_bytes(p, KT) + (size_t)p.S * p.nob * 64 * sizeof(float); }
-// Where the two-axis kernel is taken.  g_wgradw2: 0 = by size, 1 = never, 2 = wherever it can run (HPVG_WGRADW2 at start;
-// hpvg_conv_bwd_weight_wino_config modes 5 / 6 set 2 / 1).  By size: a workgroup must walk enough tiles to amortise its larger
-// slab (16 instead of 12 point tiles per block) and reduce.  Measured on MI355X against the one-axis kernel (tools/ab_wgrad2_sizes.sh,
-// profiles/r03_ab_wgrad2_sizes.txt; 64 -> 64, tiles per persistent workgroup of the centre tap): 3x3x3: 1.4 tiles x0.99, 2.8
-// x1.06, 4.1 x1.14, 13 x1.31, 53 x1.38, 117 x1.42; 3x3 (three times the workgroups per launch, a third of the work each):
-// 2 x0.89, 4 x1.02, 5.3 x1.01, 6 x1.08, 8 x1.17.  HPVG_WGRADW2_MIN_TILES overrides both thresholds.
-int g_wgradw2 = -1;
-long g_wgradw2_min_tiles = -1;    // tiles per persistent workgroup from which the two-axis kernel is taken (default: 2 / 5 for 3-D / 2-D)
-inline bool wgradw2_wanted(const WPlan& p2, int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (g_wgradw2 < 0) {
-    const char* e = getenv("HPVG_WGRADW2");
-    g_wgradw2 = e ? atoi(e) : 0;
-    const char* m = getenv("HPVG_WGRADW2_MIN_TILES");
-    if (m) g_wgradw2_min_tiles = atol(m);
-  }
-  if (g_wgradw2 == 1 || p2.Th == 0 || Cin <= 4 || Cout <= 4) return false;
-  if (!wgradw_wanted(p2, B, Cin, Cout, T, H, W, KT)) return false;     // (the Winograd weight gradient switched off altogether)
-  if (g_wgradw2 == 2) return true;
-  const long ntiles = (long)B * T * p2.nth * p2.ntw;
-  const long mt = g_wgradw2_min_tiles >= 0 ? g_wgradw2_min_tiles : (KT == 3 ? 2 : 5);
-  return ntiles >= mt * (long)p2.S;
-}
 
-// tile plan of conv_wgrad3_kernel: the same tile family as conv_wgrad_kernel under its own LDS budget (two dY tiles, four
-// 32-channel X planes, one row of zeros); S persistent workgroups per (64 output, 32 input channel) block pair
-struct W3Plan { int Th, Tw, RS, DS, XS, QK, nth, ntw, S, nob, ncb; size_t lds; long ntiles; bool ok; };
-W3Plan plan_wgrad3(int B, int Cin, int Cout, int T, int H, int W) {
-  struct Key { int B, Cin, Cout, T, H, W; };
-  struct Entry { Key k; W3Plan p; };
-  constexpr int NE = 256;
-  static thread_local Entry cache[NE];
-  static thread_local int filled = 0;
-  for (int i = 0; i < filled; ++i) {
-    const Key& c = cache[i].k;
-    if (c.B == B && c.Cin == Cin && c.Cout == Cout && c.T == T && c.H == H && c.W == W) return cache[i].p;
-  }
-  W3Plan best{};
-  double best_cost = 1e300;
-  for (int Tw = 1; Tw <= W; ++Tw) {
-    const int ntw = hpvg_cdiv(W, Tw);
-    if (Tw != hpvg_cdiv(W, ntw)) continue;
-    const int RS = Tw + 2;
-    for (int Th = 1; Th <= H; ++Th) {
-      const int nth = hpvg_cdiv(H, Th);
-      if (Th != hpvg_cdiv(H, nth)) continue;
-      const int QK = (Th * RS + 3) & ~3;                 // K positions, padded to the 4-position loop step
-      const int DS = (QK + 1) | 1;                       // dY row stride: >= QK, odd (bank spread)
-      int XS = QK + 2 * RS + 4;                          // X row: reads reach QK-1 + 2*RS + 2
-      if (XS < (Th + 2) * RS + 1) XS = (Th + 2) * RS + 1;
-      XS |= 1;
-      if (DS > 256 || XS > 256) break;                   // one 256-lane DMA round per row
-      const size_t lds = ((size_t)2 * 64 * DS + (size_t)4 * 32 * XS + XS) * sizeof(float);
-      if (lds > 158 * 1024) break;
-      const long nsp = (long)B * nth * ntw;
-      const double work = (double)nsp * T * (QK * 0.5 * 27.0 + 80.0);   // MFMAs of the K loop + per-tile fixed cost
-      if (work < best_cost) {
-        best_cost = work;
-        best = W3Plan{Th, Tw, RS, DS, XS, QK, nth, ntw, 0, hpvg_cdiv(Cout, 64), hpvg_cdiv(Cin, 32), lds, nsp * T, true};
-      }
-    }
-  }
-  if (best.ok) {
-    long cap = (long)HPVG_NUM_CU / ((long)best.nob * best.ncb);  // one persistent workgroup per CU
-    if (cap < 1) cap = 1;
-    best.S = (int)(best.ntiles < cap ? best.ntiles : cap);
-  }
-  if (filled < NE) cache[filled++] = Entry{Key{B, Cin, Cout, T, H, W}, best};
-  return best;
-}
-inline size_t wgrad3_ws_bytes(const W3Plan& q) { return 256 + (size_t)q.S * q.nob * q.ncb * 28 * 2048 * sizeof(float); }
-// conv_wgrad3_kernel pays off where a workgroup walks many tiles (its tiles carry three times the work, its slab is 1.5x
-// the size): measured on MI355X (tools/perf_conv.py, 64 -> 64) it wins 3-4 % at 78 and 156 tiles per workgroup (stage 9,
-// B = 2 / 4) and loses 2-5 % at 50 and below (stages <= 8).  HPVG_WGRAD3: 0 = never, 2 = always (tests), default = by size.
-static const int g_wgrad3_mode = [] { const char* e = getenv("HPVG_WGRAD3"); return e ? atoi(e) : 1; }();
-inline bool wgrad3_wanted(const W3Plan& q) {
-  if (!q.ok || g_wgrad3_mode == 0) return false;
-  return g_wgrad3_mode == 2 || q.ntiles >= 64L * q.S;
-}
-
-// narrow path selection: 0 = head (Cin <= 4), 1 = tail (Cout <= 4), -1 = full kernel
-inline int narrow_mode(int Cin, int Cout) {
-  if (Cin <= 4 && Cout > 4) return 0;
-  if (Cout <= 4 && Cin > 4) return 1;
-  return -1;
-}
 // tile plan of conv_wgrad_narrow2_kernel: Th image rows per tile such that the halo'd narrow tile (CN*KT planes) fits 60 KB
 struct N2Plan { int Th, nth, RS, XPL, S; long ntiles; size_t lds; bool ok; };
 inline N2Plan plan_narrow2w(int B, int CW, int CN, int T, int H, int W, int KT) {
@@ -1421,9 +1287,64 @@ inline N2Plan plan_narrow2w(int B, int CW, int CN, int T, int H, int W, int KT) 
   q.ok = true;
   return q;
 }
-static const bool g_narrow2w_off = [] { const char* e = getenv("HPVG_WGRAD_NARROW2"); return e && atoi(e) == 0; }();
 
-inline size_t narrow_ws_bytes(const WPlan& p, int CW, int CN, int KT, long ntiles) {
+// --------------------------------------------------------------------------------------------------------------- plan memo
+// One memo, thread-local, keyed by the seven integers of a launch: open addressing over NSLOT slots of which at most half are
+// filled (past that a value is searched per call and handed out from `spill`).  An entry is valid while its generation is
+// the caller's: a new generation drops every entry at once without touching the table.
+template <class Value, class Search>
+const Value& memo_lookup(int gen, int B, int Cin, int Cout, int T, int H, int W, int KT, Search search) {
+  struct Entry { int k[7]; int gen; Value v; };
+  constexpr int NSLOT = 2048;
+  static thread_local Entry cache[NSLOT];
+  static thread_local Value spill;
+  static thread_local int filled = 0, cur = 0;
+  if (cur != gen + 1) {       // (0: an entry never written)
+    cur = gen + 1;
+    filled = 0;
+  }
+  unsigned h = 2166136261u;
+  for (int v : {B, Cin, Cout, T, H, W, KT}) h = (h ^ (unsigned)v) * 16777619u;
+  for (int probe = 0; probe < NSLOT; ++probe) {
+    Entry& e = cache[(h + probe) & (NSLOT - 1)];
+    if (e.gen != cur) {
+      if (filled >= NSLOT / 2) break;
+      e = Entry{{B, Cin, Cout, T, H, W, KT}, cur, search()};
+      ++filled;
+      return e.v;
+    }
+    const int* c = e.k;
+    if (c[0] == B && c[1] == Cin && c[2] == Cout && c[3] == T && c[4] == H && c[5] == W && c[6] == KT) return e.v;
+  }
+  spill = search();
+  return spill;
+}
+
+// every tile plan of one launch shape.  wino: the 16-byte form where the width and the knobs allow it, else the 4-byte one -
+// hpvg_conv_bwd_weight_wino_config mode 3 switches the former off and on, and bumps WKnobs::gen with it
+struct WPlans { WPlan tap, wino, wino2, all; };   // all: conv_wgrad3_kernel (KT == 3)
+const WPlans& wgrad_plans(const WKnobs& k, int B, int Cin, int Cout, int T, int H, int W, int KT) {
+  return memo_lookup<WPlans>(k.gen, B, Cin, Cout, T, H, W, KT, [&] {
+    WPlans pl{};
+    pl.tap = plan_direct_search(k, B, Cin, Cout, T, H, W, KT, false);
+    pl.wino = plan_wgradw16_search(k, B, Cin, Cout, T, H, W, KT);
+    if (!pl.wino.Th) pl.wino = plan_wgradw4_search(B, Cin, Cout, T, H, W, KT);
+    pl.wino2 = plan_wgradw2_search(k, B, Cin, Cout, T, H, W, KT);
+    if (KT == 3) pl.all = plan_direct_search(k, B, Cin, Cout, T, H, W, KT, true);
+    return pl;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------ scratch, per kernel family
+// 256 bytes, then one slab of partial sums per persistent workgroup; the Winograd kernels' per-slot bias partials
+// [S][nob][64] lie behind their slabs
+inline size_t wgrad_ws_bytes(const WPlan& p, int KT) { return 256 + (size_t)p.S * KT * p.nob * p.ncb * 9 * 4096 * sizeof(float); }
+inline size_t wgrad3_ws_bytes(const WPlan& q) { return 256 + (size_t)q.S * q.nob * q.ncb * 28 * 2048 * sizeof(float); }
+inline size_t wgradw_slab_bytes(const WPlan& p, int KT) { return (size_t)p.S * KT * p.nob * p.ncb * 12 * 4096 * sizeof(float); }
+inline size_t wgradw_ws_bytes(const WPlan& p, int KT) { return 256 + wgradw_slab_bytes(p, KT) + (size_t)p.S * p.nob * 64 * sizeof(float); }
+inline size_t wgradw2_slab_bytes(const WPlan& p, int KT) { return (size_t)p.S * KT * p.nob * p.ncb * 16 * 4096 * sizeof(float); }
+inline size_t wgradw2_ws_bytes(const WPlan& p, int KT) { return 256 + wgradw2_slab_bytes(p, KT) + (size_t)p.S * p.nob * 64 * sizeof(float); }
+inline size_t narrow_ws_bytes(int CW, int CN, int KT) {
   const int nwb = hpvg_cdiv(CW, 64);
   const int NT = hpvg_cdiv(CN * KT * 9, 32);
   long S = 2L * HPVG_NUM_CU / nwb;             // the larger of the two generations' grids
@@ -1431,41 +1352,349 @@ inline size_t narrow_ws_bytes(const WPlan& p, int CW, int CN, int KT, long ntile
   return 256 + (size_t)S * 4 * nwb * 2 * NT * 1024 * sizeof(float);
 }
 
+// ------------------------------------------------------------------------------------------------------------ the decision
+inline bool wgradw_wanted(const WKnobs& k, const WPlan& p, int Cin, int Cout) {
+  return k.wino != 0 && p.Th != 0 && Cin > 4 && Cout > 4;
+}
+// Where the two-axis kernel is taken.  By size: a workgroup must walk enough tiles to amortise its larger slab (16 instead of
+// 12 point tiles per block) and reduce.  Measured on MI355X against the one-axis kernel (tools/ab_wgrad2_sizes.sh,
+// profiles/r03_ab_wgrad2_sizes.txt; 64 -> 64, tiles per persistent workgroup of the centre tap): 3x3x3: 1.4 tiles x0.99, 2.8
+// x1.06, 4.1 x1.14, 13 x1.31, 53 x1.38, 117 x1.42; 3x3 (three times the workgroups per launch, a third of the work each):
+// 2 x0.89, 4 x1.02, 5.3 x1.01, 6 x1.08, 8 x1.17.  HPVG_WGRADW2_MIN_TILES overrides both thresholds.
+inline bool wgradw2_wanted(const WKnobs& k, const WPlan& p2, int B, int Cin, int Cout, int T, int KT) {
+  if (k.w2 == 1 || !wgradw_wanted(k, p2, Cin, Cout)) return false;
+  if (k.w2 == 2) return true;
+  const long ntiles = (long)B * T * p2.nth * p2.ntw;
+  const long mt = k.min_tiles >= 0 ? k.min_tiles : (KT == 3 ? 2 : 5);
+  return ntiles >= mt * (long)p2.S;
+}
+// conv_wgrad3_kernel pays off where a workgroup walks many tiles (its tiles carry three times the work, its slab is 1.5x
+// the size): measured on MI355X (tools/perf_conv.py, 64 -> 64) it wins 3-4 % at 78 and 156 tiles per workgroup (stage 9,
+// B = 2 / 4) and loses 2-5 % at 50 and below (stages <= 8).
+inline bool wgrad3_wanted(const WKnobs& k, const WPlan& q, int B, int T) {
+  if (!q.Th || k.wgrad3 == 0) return false;
+  return k.wgrad3 == 2 || (long)B * T * q.nth * q.ntw >= 64L * q.S;
+}
+// narrow path selection: 0 = head (Cin <= 4), 1 = tail (Cout <= 4), -1 = full kernel
+inline int narrow_mode(int Cin, int Cout) {
+  if (Cin <= 4 && Cout > 4) return 0;
+  if (Cout <= 4 && Cin > 4) return 1;
+  return -1;
+}
+
+// Which kernel family runs a launch, on which plan and with how much scratch.  The launcher, the workspace check and the host
+// queries (kernel_kind, fuses_bias, wino2_plan's out[10]) all read this one answer.  The chain: narrow (second generation,
+// then first), two-axis Winograd, one-axis Winograd, all-taps direct, per-tap direct.
+struct WDecision {
+  int kind;           // hpvg_conv_bwd_weight_kernel_kind's numbering: 0 conv_wgrad_kernel (plans->tap), 1 conv_wgrad3_kernel
+                      // (->all), 2 conv_wgradw_kernel (->wino), 3 conv_wgradw2_kernel (->wino2), 4 the narrow kernels
+  int narrow;         // kind 4: narrow_mode, and
+  int narrow_gen;     //         2 = conv_wgrad_narrow2_kernel (n2), 1 = conv_wgrad_narrow_kernel (on plans->tap's tiles)
+  N2Plan n2;
+  const WPlans* plans;
+  size_t ws_bytes;    // the scratch that kernel needs
+};
+inline bool wgrad_dims_ok(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+  return B >= 1 && Cin >= 1 && Cout >= 1 && T >= 1 && H >= 1 && W >= 1 && (KT == 1 || KT == 3);
+}
+WDecision wgrad_decide(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+  const WKnobs& k = wknobs();
+  WDecision d{};
+  const WPlans& pl = wgrad_plans(k, B, Cin, Cout, T, H, W, KT);
+  d.plans = &pl;
+  d.narrow = narrow_mode(Cin, Cout);
+  if (d.narrow >= 0) {
+    const int CW = d.narrow == 0 ? Cout : Cin, CN = d.narrow == 0 ? Cin : Cout;
+    d.kind = 4;
+    d.n2 = plan_narrow2w(B, CW, CN, T, H, W, KT);
+    d.narrow_gen = d.n2.ok && !k.narrow2_off ? 2 : 1;
+    d.ws_bytes = narrow_ws_bytes(CW, CN, KT);
+  } else if (wgradw2_wanted(k, pl.wino2, B, Cin, Cout, T, KT)) {
+    d.kind = 3;
+    d.ws_bytes = wgradw2_ws_bytes(pl.wino2, KT);
+  } else if (wgradw_wanted(k, pl.wino, Cin, Cout)) {
+    d.kind = 2;
+    d.ws_bytes = wgradw_ws_bytes(pl.wino, KT);
+  } else if (KT == 3 && wgrad3_wanted(k, pl.all, B, T)) {
+    d.kind = 1;
+    d.ws_bytes = wgrad3_ws_bytes(pl.all);
+  } else {
+    d.kind = 0;
+    d.ws_bytes = wgrad_ws_bytes(pl.tap, KT);
+  }
+  return d;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- launches
+// one launch with up to 160 KB of dynamic LDS: the attribute is set once per kernel instance
+template <auto Kernel, class Args>
+int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args& a) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      (void)hipGetLastError();
+    attr = true;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, a);
+  return hpvg_launch_status();
+}
+
+// the operands of one hpvg_conv_bwd_weight_* call
+struct WCall {
+  const float* dy; const float* x;
+  float* dw; int accumulate;
+  float* db; int accumulate_db;
+  char* ws;
+  int B, Cin, Cout, T, H, W, KT, in_lrelu;
+  hipStream_t s;
+};
+
+// kernel arguments of the three tap-per-workgroup kernels; bias_at: where in the workspace the bias partials lie (Winograd
+// kernels of a call that asks for db)
+WgradArgs wgrad_args(const WCall& c, const WPlan& p, size_t bias_at) {
+  WgradArgs a;
+  a.dy = c.dy; a.x = c.x; a.in_scale = nullptr; a.in_shift = nullptr;
+  a.part = (float*)(c.ws + 256);
+  a.B = c.B; a.Cin = c.Cin; a.Cout = c.Cout; a.T = c.T; a.H = c.H; a.W = c.W;
+  a.Th = p.Th; a.Tw = p.Tw; a.RS = p.RS; a.DS = p.DS; a.XS = p.XS; a.QK = p.QK; a.nth = p.nth; a.ntw = p.ntw;
+  a.S = p.S; a.S0 = p.S0; a.ncb = p.ncb; a.nob = p.nob; a.in_lrelu = c.in_lrelu;
+  a.bpart = c.db ? (float*)(c.ws + bias_at) : nullptr;
+  a.order = wknobs().order;
+  return a;
+}
+inline dim3 wgrad_grid(const WPlan& p, int KT) { return dim3((KT == 3 ? 2 * p.S0 + p.S : p.S) * p.nob * p.ncb); }
+
+// ---- narrow layer (head / tail): dedicated kernels, the wide operand is streamed once
+template <int KT>
+int launch_narrow2_nt(int NT, dim3 grid, size_t lds, hipStream_t s, const Narrow2WArgs& a) {
+  if (NT == 1) return launch_lds<conv_wgrad_narrow2_kernel<KT, 1>>(grid, dim3(256), lds, s, a);
+  if constexpr (KT == 1) {
+    return launch_lds<conv_wgrad_narrow2_kernel<1, 2>>(grid, dim3(256), lds, s, a);
+  } else {
+    if (NT == 2) return launch_lds<conv_wgrad_narrow2_kernel<3, 2>>(grid, dim3(256), lds, s, a);
+    if (NT == 3) return launch_lds<conv_wgrad_narrow2_kernel<3, 3>>(grid, dim3(256), lds, s, a);
+    return launch_lds<conv_wgrad_narrow2_kernel<3, 4>>(grid, dim3(256), lds, s, a);
+  }
+}
+template <int KT>
+int launch_narrow1_nt(int NT, dim3 grid, size_t lds, hipStream_t s, const NarrowArgs& a) {
+  if (NT == 1) return launch_lds<conv_wgrad_narrow_kernel<KT, 1>>(grid, dim3(256), lds, s, a);
+  if constexpr (KT == 1) {
+    return launch_lds<conv_wgrad_narrow_kernel<1, 2>>(grid, dim3(256), lds, s, a);
+  } else {
+    if (NT == 2) return launch_lds<conv_wgrad_narrow_kernel<3, 2>>(grid, dim3(256), lds, s, a);
+    if (NT == 3) return launch_lds<conv_wgrad_narrow_kernel<3, 3>>(grid, dim3(256), lds, s, a);
+    return launch_lds<conv_wgrad_narrow_kernel<3, 4>>(grid, dim3(256), lds, s, a);
+  }
+}
+int launch_narrow(const WCall& c, const WDecision& d) {
+  const int nm = d.narrow, KT = c.KT;
+  const int CW = nm == 0 ? c.Cout : c.Cin, CN = nm == 0 ? c.Cin : c.Cout;
+  const int nwb = hpvg_cdiv(CW, 64);
+  const int NT = hpvg_cdiv(CN * KT * 9, 32);
+  const float* wide = nm == 0 ? c.dy : c.x;
+  const float* narrow = nm == 0 ? c.x : c.dy;
+  float* part = (float*)(c.ws + 256);
+  int slots, st;
+  if (d.narrow_gen == 2) {
+    // ---- second generation: the wide operand straight from global memory, 16 bytes per lane (conv_wgrad_narrow2_kernel)
+    const N2Plan& q = d.n2;
+    Narrow2WArgs n2;
+    n2.wide = wide; n2.narrow = narrow; n2.part = part;
+    n2.B = c.B; n2.CW = CW; n2.CN = CN; n2.T = c.T; n2.H = c.H; n2.W = c.W;
+    n2.Th = q.Th; n2.nth = q.nth; n2.RS = q.RS; n2.XPL = q.XPL; n2.S = q.S; n2.ntiles = (int)q.ntiles;
+    const dim3 grid((unsigned)q.S, nwb);
+    st = KT == 3 ? launch_narrow2_nt<3>(NT, grid, q.lds, c.s, n2) : launch_narrow2_nt<1>(NT, grid, q.lds, c.s, n2);
+    slots = q.S;
+  } else {
+    const WPlan& p = d.plans->tap;
+    const long ntiles = (long)c.B * c.T * p.nth * p.ntw;
+    long S = HPVG_NUM_CU / nwb;
+    if (S < 1) S = 1;
+    if (ntiles < S) S = ntiles;
+    NarrowArgs na;
+    na.wide = wide; na.narrow = narrow; na.part = part;
+    na.B = c.B; na.CW = CW; na.CN = CN; na.T = c.T; na.H = c.H; na.W = c.W;
+    na.Th = p.Th; na.Tw = p.Tw; na.RS = p.RS; na.DS = p.DS; na.XPL = p.XS; na.QK = p.QK; na.nth = p.nth; na.ntw = p.ntw;
+    na.S = (int)S; na.ntiles = (int)ntiles;
+    const size_t lds = (size_t)2 * (64 * p.DS + CN * KT * p.XS) * sizeof(float);
+    const dim3 grid((unsigned)S, nwb);
+    st = KT == 3 ? launch_narrow1_nt<3>(NT, grid, lds, c.s, na) : launch_narrow1_nt<1>(NT, grid, lds, c.s, na);
+    slots = (int)S * 4;
+  }
+  if (st != HPVG_OK) return st;
+  const int total = CW * CN * KT * 9;
+  hipLaunchKernelGGL(conv_wgrad_narrow_reduce_kernel, dim3(hpvg_cdiv(total, 4)), dim3(256), 0, c.s, (const float*)part, c.dw, slots,
+                     nwb, NT, CW, CN, KT * 9, nm, c.accumulate);
+  return hpvg_launch_status();
+}
+
+// ---- Winograd over H and W (conv_wgradw2_kernel): 16 point accumulators per time tap, transformed by the reduce kernel
+// (the 16-column band - the tile of the large launches - has its row strides as immediates: one address register per operand;
+// ST: W % 4 != 0 runs the instance that patches the straddling groups)
+template <int K, bool ST>
+int launch_wgradw2_tile(const WPlan& p2, dim3 grid, hipStream_t s, const WgradArgs& a) {
+  const int gjd = hpvg_cdiv(p2.Th * (p2.Tw / 4), 64), gjx = hpvg_cdiv((p2.Th + 2) * (p2.Tw / 4 + 2), 64);   // pieces of 64 groups
+  if (gjd == 1 && gjx == 1 && p2.Tw == 16) return launch_lds<conv_wgradw2_kernel<K, 1, 1, 16, ST>>(grid, dim3(256), p2.lds, s, a);
+  if (gjd == 1 && gjx == 1) return launch_lds<conv_wgradw2_kernel<K, 1, 1, 0, ST>>(grid, dim3(256), p2.lds, s, a);
+  if (gjd == 1) return launch_lds<conv_wgradw2_kernel<K, 1, 2, 0, ST>>(grid, dim3(256), p2.lds, s, a);
+  return launch_lds<conv_wgradw2_kernel<K, 2, 2, 0, ST>>(grid, dim3(256), p2.lds, s, a);
+}
+int launch_wgradw2(const WCall& c, const WPlan& p2) {
+  const int KT = c.KT;
+  const WgradArgs a = wgrad_args(c, p2, 256 + wgradw2_slab_bytes(p2, KT));
+  const dim3 grid = wgrad_grid(p2, KT);
+  const int st = (c.W & 3) ? (KT == 3 ? launch_wgradw2_tile<3, true>(p2, grid, c.s, a) : launch_wgradw2_tile<1, true>(p2, grid, c.s, a))
+                           : (KT == 3 ? launch_wgradw2_tile<3, false>(p2, grid, c.s, a) : launch_wgradw2_tile<1, false>(p2, grid, c.s, a));
+  if (st != HPVG_OK) return st;
+  const int nbw2 = KT * p2.nob * p2.ncb * 64;
+  hipLaunchKernelGGL(conv_wgradw2_reduce_kernel, dim3(nbw2 + (c.db ? hpvg_cdiv(c.Cout, 64) : 0)), dim3(64, 16), 0, c.s,
+                     (const float*)a.part, c.dw, p2.S, p2.S0, KT, p2.nob, p2.ncb, c.Cout, c.Cin, c.accumulate, nbw2,
+                     (const float*)a.bpart, c.db, c.accumulate_db);
+  return hpvg_launch_status();
+}
+
+// ---- Winograd along W (conv_wgradw_kernel): 12 tap-point accumulators per time tap, transformed by the reduce kernel
+template <int K, int D, int X, bool WCH, bool G16, bool W8>
+int launch_wgradw_form(const WPlan& pw, dim3 grid, hipStream_t s, const WgradArgs& a) {
+  return launch_lds<conv_wgradw_kernel<K, D, X, WCH, G16, W8>>(grid, dim3(W8 ? 512 : 256), pw.lds, s, a);
+}
+template <int K>
+int launch_wgradw_tile(const WKnobs& k, const WPlan& pw, dim3 grid, hipStream_t s, const WgradArgs& a) {
+  if (pw.g16) {
+    // 16-byte form: pieces of 64 groups; eight waves (two per SIMD, half of the Winograd points each) unless HPVG_WGRADW_W8=0 /
+    // mode 4 keep four
+    const int gjd = hpvg_cdiv(pw.Th * (pw.Tw / 4), 64), gjx = hpvg_cdiv((pw.Th + 2) * (pw.Tw / 4 + 2), 64);
+    if (k.w8) {
+      if (gjd == 1 && gjx == 1) return launch_wgradw_form<K, 1, 1, true, true, true>(pw, grid, s, a);
+      if (gjd == 1) return launch_wgradw_form<K, 1, 2, true, true, true>(pw, grid, s, a);
+      return launch_wgradw_form<K, 2, 2, true, true, true>(pw, grid, s, a);
+    }
+    if (gjd == 1 && gjx == 1) return launch_wgradw_form<K, 1, 1, true, true, false>(pw, grid, s, a);
+    if (gjd == 1) return launch_wgradw_form<K, 1, 2, true, true, false>(pw, grid, s, a);
+    return launch_wgradw_form<K, 2, 2, true, true, false>(pw, grid, s, a);
+  }
+  // whole channel rows per wave (WCH) where an instance exists for the row lengths: pieces of 64 lanes
+  const int wjd = hpvg_cdiv(pw.DS, 64), wjx = hpvg_cdiv(pw.XS, 64);
+  if (k.wch && wjd == 1 && wjx == 2) return launch_wgradw_form<K, 1, 2, true, false, false>(pw, grid, s, a);
+  if (k.wch && wjd == 1 && wjx == 3) return launch_wgradw_form<K, 1, 3, true, false, false>(pw, grid, s, a);
+  if (k.wch && wjd == 2 && wjx == 3) return launch_wgradw_form<K, 2, 3, true, false, false>(pw, grid, s, a);
+  if (k.wch && wjd == 2 && wjx == 4) return launch_wgradw_form<K, 2, 4, true, false, false>(pw, grid, s, a);
+  const int njd = pw.DS > 256 ? 2 : 1, njx = pw.XS > 256 ? 2 : 1;
+  if (njd == 1 && njx == 1) return launch_wgradw_form<K, 1, 1, false, false, false>(pw, grid, s, a);
+  if (njd == 1) return launch_wgradw_form<K, 1, 2, false, false, false>(pw, grid, s, a);
+  return launch_wgradw_form<K, 2, 2, false, false, false>(pw, grid, s, a);
+}
+int launch_wgradw(const WCall& c, const WPlan& pw) {
+  const int KT = c.KT;
+  const WgradArgs a = wgrad_args(c, pw, 256 + wgradw_slab_bytes(pw, KT));
+  const dim3 grid = wgrad_grid(pw, KT);
+  const int st = KT == 3 ? launch_wgradw_tile<3>(wknobs(), pw, grid, c.s, a) : launch_wgradw_tile<1>(wknobs(), pw, grid, c.s, a);
+  if (st != HPVG_OK) return st;
+  const long totw = (long)KT * pw.nob * pw.ncb * 3 * 4096;
+  const int nbw = hpvg_cdiv(totw, 128);
+  hipLaunchKernelGGL(conv_wgradw_reduce_kernel, dim3(nbw + (c.db ? hpvg_cdiv(c.Cout, 128) : 0)), dim3(128, 8), 0, c.s,
+                     (const float*)a.part, c.dw, pw.S, pw.S0, KT, pw.nob, pw.ncb, c.Cout, c.Cin, c.accumulate, nbw,
+                     (const float*)a.bpart, c.db, c.accumulate_db);
+  return hpvg_launch_status();
+}
+
+// ---- all 27 taps in one workgroup (conv_wgrad3_kernel)
+int launch_wgrad3(const WCall& c, const WPlan& q) {
+  Wgrad3Args w3;
+  w3.dy = c.dy; w3.x = c.x; w3.part = (float*)(c.ws + 256);
+  w3.B = c.B; w3.Cin = c.Cin; w3.Cout = c.Cout; w3.T = c.T; w3.H = c.H; w3.W = c.W;
+  w3.Th = q.Th; w3.Tw = q.Tw; w3.RS = q.RS; w3.DS = q.DS; w3.XS = q.XS; w3.QK = q.QK; w3.nth = q.nth; w3.ntw = q.ntw;
+  w3.S = q.S; w3.ncb = q.ncb; w3.nob = q.nob; w3.ntiles = c.B * c.T * q.nth * q.ntw;
+  const int st = launch_lds<conv_wgrad3_kernel>(dim3((unsigned)(q.S * q.nob * q.ncb)), dim3(256), q.lds, c.s, w3);
+  if (st != HPVG_OK) return st;
+  const long total3 = (long)q.nob * q.ncb * 27 * 2048;
+  hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3(hpvg_cdiv(total3, 256)), dim3(256, 4), 0, c.s, (const float*)w3.part, c.dw, q.S,
+                     q.nob, q.ncb, c.Cout, c.Cin, c.accumulate);
+  return hpvg_launch_status();
+}
+
+// ---- one time tap per workgroup (conv_wgrad_kernel)
+template <int K>
+int launch_wgrad_tile(const WPlan& p, dim3 grid, hipStream_t s, const WgradArgs& a) {
+  const int njd = p.DS > 256 ? 2 : 1, njx = p.XS > 256 ? 2 : 1;
+  if (njd == 1 && njx == 1) return launch_lds<conv_wgrad_kernel<K, 1, 1>>(grid, dim3(256), p.lds, s, a);
+  if (njd == 1) return launch_lds<conv_wgrad_kernel<K, 1, 2>>(grid, dim3(256), p.lds, s, a);
+  return launch_lds<conv_wgrad_kernel<K, 2, 2>>(grid, dim3(256), p.lds, s, a);
+}
+int launch_wgrad(const WCall& c, const WPlan& p) {
+  const int KT = c.KT;
+  const WgradArgs a = wgrad_args(c, p, 0);
+  const dim3 grid = wgrad_grid(p, KT);
+  const int st = KT == 3 ? launch_wgrad_tile<3>(p, grid, c.s, a) : launch_wgrad_tile<1>(p, grid, c.s, a);
+  if (st != HPVG_OK) return st;
+  const long per_s = (long)KT * p.nob * p.ncb * 9 * 4096;
+  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(hpvg_cdiv(per_s, 256)), dim3(256), 0, c.s, (const float*)a.part, c.dw, p.S, p.S0, KT,
+                     p.nob, p.ncb, c.Cout, c.Cin, c.accumulate);
+  return hpvg_launch_status();
+}
+
+// dw: natural layout [Cout][Cin][KT][3][3]; accumulate != 0 adds into dw instead of overwriting.
+int bwd_weight_impl(const float* dy, const float* x, const float* in_scale, const float* in_shift, int in_lrelu, float* dw,
+                    int accumulate, float* db, int accumulate_db, void* ws, size_t ws_bytes, int B, int Cin, int Cout, int T, int H,
+                    int W, int KT, void* stream) {
+  if (!dy || !x || !dw || !ws) return HPVG_ERR_ARG;
+  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
+  if (KT != 1 && KT != 3) return HPVG_ERR_UNSUPPORTED;
+  if ((in_scale == nullptr) != (in_shift == nullptr)) return HPVG_ERR_ARG;
+  const WDecision d = wgrad_decide(B, Cin, Cout, T, H, W, KT);
+  if (d.plans->tap.Th == 0) return HPVG_ERR_UNSUPPORTED;
+  if (in_scale) return HPVG_ERR_UNSUPPORTED;  // the fused-producer prologue needs the register-staged variant
+  if (db && d.kind != 2 && d.kind != 3) return HPVG_ERR_UNSUPPORTED;   // (only the Winograd kernels produce the bias gradient)
+  if (ws_bytes < d.ws_bytes) return HPVG_ERR_WORKSPACE;
+  const WCall c{dy, x, dw, accumulate, db, accumulate_db, (char*)ws, B, Cin, Cout, T, H, W, KT, in_lrelu, (hipStream_t)stream};
+  switch (d.kind) {
+    case 4: return launch_narrow(c, d);
+    case 3: return launch_wgradw2(c, d.plans->wino2);
+    case 2: return launch_wgradw(c, d.plans->wino);
+    case 1: return launch_wgrad3(c, d.plans->all);
+    default: return launch_wgrad(c, d.plans->tap);
+  }
+}
+
+// out[0..9] of the three plan queries
+int write_plan(const WPlan& p, int B, int T, int* out) {
+  out[0] = p.Th; out[1] = p.Tw; out[2] = p.nth; out[3] = p.ntw; out[4] = p.QK; out[5] = p.S; out[6] = p.DS; out[7] = p.XS;
+  out[8] = (int)p.lds; out[9] = B * T * p.nth * p.ntw;
+  return HPVG_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+// The scratch of the largest kernel that any run-time mode (hpvg_conv_bwd_weight_wino_config) could pick for this shape: the
+// caller sizes one shared buffer, and the mode may change between the query and the launch.  Each term is the function the
+// launcher's own check reads through wgrad_decide.
 size_t hpvg_conv_bwd_weight_ws_bytes(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  const WPlan p = plan_wgrad(B, Cin, Cout, T, H, W, KT);
+  const WKnobs& k = wknobs();
   const int nm = narrow_mode(Cin, Cout);
-  if (nm >= 0) return narrow_ws_bytes(p, nm == 0 ? Cout : Cin, nm == 0 ? Cin : Cout, KT, (long)B * T * p.nth * p.ntw);
-  size_t need = 256 + (size_t)p.S * KT * p.nob * p.ncb * 9 * 4096 * sizeof(float);
-  if (KT == 3) {
-    const W3Plan q = plan_wgrad3(B, Cin, Cout, T, H, W);
-    if (wgrad3_wanted(q) && wgrad3_ws_bytes(q) > need) need = wgrad3_ws_bytes(q);
-  }
-  const WPlan pw = plan_wgradw(B, Cin, Cout, T, H, W, KT);
-  if (g_wgradw_mode != 0 && pw.Th != 0 && wgradw_ws_bytes(pw, KT) > need) need = wgradw_ws_bytes(pw, KT);  // (any run-time mode)
-  const WPlan p2 = plan_wgradw2(B, Cin, Cout, T, H, W, KT);
-  if (g_wgradw_mode != 0 && p2.Th != 0 && wgradw2_ws_bytes(p2, KT) > need) need = wgradw2_ws_bytes(p2, KT);
+  if (nm >= 0) return narrow_ws_bytes(nm == 0 ? Cout : Cin, nm == 0 ? Cin : Cout, KT);
+  const WPlans& pl = wgrad_plans(k, B, Cin, Cout, T, H, W, KT);
+  size_t need = wgrad_ws_bytes(pl.tap, KT);
+  auto or_more = [&need](size_t n) { if (n > need) need = n; };
+  if (KT == 3 && wgrad3_wanted(k, pl.all, B, T)) or_more(wgrad3_ws_bytes(pl.all));
+  if (k.wino != 0 && pl.wino.Th != 0) or_more(wgradw_ws_bytes(pl.wino, KT));
+  if (k.wino != 0 && pl.wino2.Th != 0) or_more(wgradw2_ws_bytes(pl.wino2, KT));
   return need;
 }
 
-// dw: natural layout [Cout][Cin][KT][3][3]; accumulate != 0 adds into dw instead of overwriting.
-static int bwd_weight_impl(const float* dy, const float* x, const float* in_scale, const float* in_shift, int in_lrelu,
-                           float* dw, int accumulate, float* db, int accumulate_db, void* ws, size_t ws_bytes, int B, int Cin,
-                           int Cout, int T, int H, int W, int KT, void* stream);
 int hpvg_conv_bwd_weight_f32(const float* dy, const float* x, const float* in_scale, const float* in_shift, int in_lrelu,
                              float* dw, int accumulate, void* ws, size_t ws_bytes, int B, int Cin, int Cout, int T, int H,
                              int W, int KT, void* stream) {
   return bwd_weight_impl(dy, x, in_scale, in_shift, in_lrelu, dw, accumulate, nullptr, 0, ws, ws_bytes, B, Cin, Cout, T, H, W, KT,
                          stream);
 }
-// does hpvg_conv_bwd_weight_bias_f32 produce the bias gradient for this layer (the Winograd weight-gradient kernel runs it)?
+// does hpvg_conv_bwd_weight_bias_f32 produce the bias gradient for this layer (a Winograd weight-gradient kernel runs it)?
 int hpvg_conv_bwd_weight_fuses_bias(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1 || (KT != 1 && KT != 3) || narrow_mode(Cin, Cout) >= 0) return 0;
-  if (wgradw2_wanted(plan_wgradw2(B, Cin, Cout, T, H, W, KT), B, Cin, Cout, T, H, W, KT)) return 1;
-  return wgradw_wanted(plan_wgradw(B, Cin, Cout, T, H, W, KT), B, Cin, Cout, T, H, W, KT) ? 1 : 0;
+  if (!wgrad_dims_ok(B, Cin, Cout, T, H, W, KT)) return 0;
+  const int kind = wgrad_decide(B, Cin, Cout, T, H, W, KT).kind;
+  return kind == 2 || kind == 3;
 }
 // the weight gradient AND db[o] (+)= sum over batch and positions of dy - the conv's bias gradient - from the same launch:
 // the centre-tap workgroups of conv_wgradw_kernel hold every dY pair in registers anyway.  HPVG_ERR_UNSUPPORTED where
@@ -1475,283 +1704,6 @@ int hpvg_conv_bwd_weight_bias_f32(const float* dy, const float* x, float* dw, in
   if (!db) return HPVG_ERR_ARG;
   if (!hpvg_conv_bwd_weight_fuses_bias(B, Cin, Cout, T, H, W, KT)) return HPVG_ERR_UNSUPPORTED;
   return bwd_weight_impl(dy, x, nullptr, nullptr, 0, dw, accumulate, db, accumulate_db, ws, ws_bytes, B, Cin, Cout, T, H, W, KT, stream);
-}
-static int bwd_weight_impl(const float* dy, const float* x, const float* in_scale, const float* in_shift, int in_lrelu,
-                           float* dw, int accumulate, float* db, int accumulate_db, void* ws, size_t ws_bytes, int B, int Cin,
-                           int Cout, int T, int H, int W, int KT, void* stream) {
-  if (!dy || !x || !dw || !ws) return HPVG_ERR_ARG;
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
-  if (KT != 1 && KT != 3) return HPVG_ERR_UNSUPPORTED;
-  if ((in_scale == nullptr) != (in_shift == nullptr)) return HPVG_ERR_ARG;
-  const WPlan p = plan_wgrad(B, Cin, Cout, T, H, W, KT);
-  if (p.Th == 0) return HPVG_ERR_UNSUPPORTED;
-  const int nm = narrow_mode(Cin, Cout);
-  if (nm >= 0) {
-    // ---- narrow layer (head / tail): dedicated kernel, the wide operand is streamed once
-    if (in_scale) return HPVG_ERR_UNSUPPORTED;
-    const int CW = nm == 0 ? Cout : Cin, CN = nm == 0 ? Cin : Cout;
-    const long ntiles = (long)B * T * p.nth * p.ntw;
-    if (ws_bytes < narrow_ws_bytes(p, CW, CN, KT, ntiles)) return HPVG_ERR_WORKSPACE;
-    const int nwb = hpvg_cdiv(CW, 64);
-    const int NT = hpvg_cdiv(CN * KT * 9, 32);
-    hipStream_t s = (hipStream_t)stream;
-    const N2Plan q = plan_narrow2w(B, CW, CN, T, H, W, KT);
-    if (q.ok && !g_narrow2w_off) {
-      // ---- second generation: the wide operand straight from global memory, 16 bytes per lane (conv_wgrad_narrow2_kernel)
-      Narrow2WArgs n2;
-      n2.wide = nm == 0 ? dy : x; n2.narrow = nm == 0 ? x : dy; n2.part = (float*)((char*)ws + 256);
-      n2.B = B; n2.CW = CW; n2.CN = CN; n2.T = T; n2.H = H; n2.W = W;
-      n2.Th = q.Th; n2.nth = q.nth; n2.RS = q.RS; n2.XPL = q.XPL; n2.S = q.S; n2.ntiles = (int)q.ntiles;
-      const dim3 grid2((unsigned)q.S, nwb);
-#define HPVG_NW2_LAUNCH(K, N)                                                                                         \
-  {                                                                                                                   \
-    static bool attr = false;                                                                                         \
-    if (!attr) {                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_narrow2_kernel<K, N>),                         \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                  \
-        (void)hipGetLastError();                                                                                      \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((conv_wgrad_narrow2_kernel<K, N>), grid2, dim3(256), q.lds, s, n2);                            \
-  }
-      if (KT == 3) {
-        if (NT == 1) HPVG_NW2_LAUNCH(3, 1) else if (NT == 2) HPVG_NW2_LAUNCH(3, 2) else if (NT == 3) HPVG_NW2_LAUNCH(3, 3) else HPVG_NW2_LAUNCH(3, 4)
-      } else {
-        if (NT == 1) HPVG_NW2_LAUNCH(1, 1) else HPVG_NW2_LAUNCH(1, 2)
-      }
-#undef HPVG_NW2_LAUNCH
-      int st2 = hpvg_launch_status();
-      if (st2 != HPVG_OK) return st2;
-      const int total2 = CW * CN * KT * 9;
-      hipLaunchKernelGGL(conv_wgrad_narrow_reduce_kernel, dim3(hpvg_cdiv(total2, 4)), dim3(256), 0, s, (const float*)n2.part, dw,
-                         q.S, nwb, NT, CW, CN, KT * 9, nm, accumulate);
-      return hpvg_launch_status();
-    }
-    long S = HPVG_NUM_CU / nwb;
-    if (S < 1) S = 1;
-    if (ntiles < S) S = ntiles;
-    NarrowArgs na;
-    na.wide = nm == 0 ? dy : x; na.narrow = nm == 0 ? x : dy; na.part = (float*)((char*)ws + 256);
-    na.B = B; na.CW = CW; na.CN = CN; na.T = T; na.H = H; na.W = W;
-    na.Th = p.Th; na.Tw = p.Tw; na.RS = p.RS; na.DS = p.DS; na.XPL = p.XS; na.QK = p.QK; na.nth = p.nth; na.ntw = p.ntw;
-    na.S = (int)S; na.ntiles = (int)ntiles;
-    const size_t lds = (size_t)2 * (64 * p.DS + CN * KT * p.XS) * sizeof(float);
-    const dim3 grid((unsigned)S, nwb);
-#define HPVG_NW_LAUNCH(K, N)                                                                                          \
-  {                                                                                                                   \
-    static bool attr = false;                                                                                         \
-    if (!attr) {                                                                                                      \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_narrow_kernel<K, N>),                          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                  \
-        (void)hipGetLastError();                                                                                      \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((conv_wgrad_narrow_kernel<K, N>), grid, dim3(256), lds, s, na);                                \
-  }
-    if (KT == 3) {
-      if (NT == 1) HPVG_NW_LAUNCH(3, 1) else if (NT == 2) HPVG_NW_LAUNCH(3, 2) else if (NT == 3) HPVG_NW_LAUNCH(3, 3) else HPVG_NW_LAUNCH(3, 4)
-    } else {
-      if (NT == 1) HPVG_NW_LAUNCH(1, 1) else HPVG_NW_LAUNCH(1, 2)
-    }
-#undef HPVG_NW_LAUNCH
-    int st = hpvg_launch_status();
-    if (st != HPVG_OK) return st;
-    const int total = CW * CN * KT * 9;
-    hipLaunchKernelGGL(conv_wgrad_narrow_reduce_kernel, dim3(hpvg_cdiv(total, 4)), dim3(256), 0, s, (const float*)na.part, dw,
-                       (int)S * 4, nwb, NT, CW, CN, KT * 9, nm, accumulate);
-    return hpvg_launch_status();
-  }
-  if (in_scale) return HPVG_ERR_UNSUPPORTED;  // the fused-producer prologue needs the register-staged variant
-  {
-    const WPlan p2 = plan_wgradw2(B, Cin, Cout, T, H, W, KT);
-    if (wgradw2_wanted(p2, B, Cin, Cout, T, H, W, KT)) {
-      // ---- Winograd over H and W (conv_wgradw2_kernel): 16 point accumulators per time tap, transformed by the reduce kernel
-      if (ws_bytes < wgradw2_ws_bytes(p2, KT)) return HPVG_ERR_WORKSPACE;
-      WgradArgs a;
-      a.dy = dy; a.x = x; a.in_scale = nullptr; a.in_shift = nullptr;
-      a.part = (float*)((char*)ws + 256);
-      a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.H = H; a.W = W;
-      a.Th = p2.Th; a.Tw = p2.Tw; a.RS = p2.RS; a.DS = p2.DS; a.XS = p2.XS; a.QK = p2.QK; a.nth = p2.nth; a.ntw = p2.ntw;
-      a.S = p2.S; a.S0 = p2.S0; a.ncb = p2.ncb; a.nob = p2.nob; a.in_lrelu = 0;
-      a.bpart = db ? (float*)((char*)ws + 256 + wgradw2_slab_bytes(p2, KT)) : nullptr;
-      static const int order_env = [] { const char* e = getenv("HPVG_WG2_ORDER"); return e ? atoi(e) : 1; }();   // plane-major: same time, 1.9 instead of 3.4 GB of HBM traffic per stage-9 launch (profiles/r03_ab_wgrad2_order.txt)
-      a.order = order_env;
-      hipStream_t s = (hipStream_t)stream;
-      const dim3 grid((KT == 3 ? 2 * p2.S0 + p2.S : p2.S) * p2.nob * p2.ncb);
-      const int gjd = hpvg_cdiv(p2.Th * (p2.Tw / 4), 64), gjx = hpvg_cdiv((p2.Th + 2) * (p2.Tw / 4 + 2), 64);
-#define HPVG_W2_LAUNCH(K, D, X, TWC, ST)                                                                               \
-  {                                                                                                                    \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgradw2_kernel<K, D, X, TWC, ST>),                    \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                   \
-        (void)hipGetLastError();                                                                                       \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((conv_wgradw2_kernel<K, D, X, TWC, ST>), grid, dim3(256), p2.lds, s, a);                        \
-  }
-      // (the 16-column band - the tile of the large launches - has its row strides as immediates: one address register per
-      // operand; W % 4 != 0 runs the instance that patches the straddling groups)
-#define HPVG_W2_PICK(K)                                                                                                \
-  if (W & 3) {                                                                                                         \
-    if (gjd == 1 && gjx == 1 && p2.Tw == 16) HPVG_W2_LAUNCH(K, 1, 1, 16, true)                                         \
-    else if (gjd == 1 && gjx == 1) HPVG_W2_LAUNCH(K, 1, 1, 0, true)                                                    \
-    else if (gjd == 1) HPVG_W2_LAUNCH(K, 1, 2, 0, true)                                                                \
-    else HPVG_W2_LAUNCH(K, 2, 2, 0, true)                                                                              \
-  } else {                                                                                                             \
-    if (gjd == 1 && gjx == 1 && p2.Tw == 16) HPVG_W2_LAUNCH(K, 1, 1, 16, false)                                        \
-    else if (gjd == 1 && gjx == 1) HPVG_W2_LAUNCH(K, 1, 1, 0, false)                                                   \
-    else if (gjd == 1) HPVG_W2_LAUNCH(K, 1, 2, 0, false)                                                               \
-    else HPVG_W2_LAUNCH(K, 2, 2, 0, false)                                                                             \
-  }
-      if (KT == 3) {
-        HPVG_W2_PICK(3)
-      } else {
-        HPVG_W2_PICK(1)
-      }
-#undef HPVG_W2_PICK
-#undef HPVG_W2_LAUNCH
-      int st2 = hpvg_launch_status();
-      if (st2 != HPVG_OK) return st2;
-      const int nbw2 = KT * p2.nob * p2.ncb * 64;
-      hipLaunchKernelGGL(conv_wgradw2_reduce_kernel, dim3(nbw2 + (db ? hpvg_cdiv(Cout, 64) : 0)), dim3(64, 16), 0, s,
-                         (const float*)a.part, dw, p2.S, p2.S0, KT, p2.nob, p2.ncb, Cout, Cin, accumulate, nbw2,
-                         (const float*)a.bpart, db, accumulate_db);
-      return hpvg_launch_status();
-    }
-  }
-  {
-    const WPlan pw = plan_wgradw(B, Cin, Cout, T, H, W, KT);
-    if (wgradw_wanted(pw, B, Cin, Cout, T, H, W, KT)) {
-      // ---- Winograd along W (conv_wgradw_kernel): 12 tap-point accumulators per time tap, transformed by the reduce kernel
-      if (ws_bytes < wgradw_ws_bytes(pw, KT)) return HPVG_ERR_WORKSPACE;
-      WgradArgs a;
-      a.dy = dy; a.x = x; a.in_scale = nullptr; a.in_shift = nullptr;
-      a.part = (float*)((char*)ws + 256);
-      a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.H = H; a.W = W;
-      a.Th = pw.Th; a.Tw = pw.Tw; a.RS = pw.RS; a.DS = pw.DS; a.XS = pw.XS; a.QK = pw.QK; a.nth = pw.nth; a.ntw = pw.ntw;
-      a.S = pw.S; a.S0 = pw.S0; a.ncb = pw.ncb; a.nob = pw.nob; a.in_lrelu = 0;
-      a.bpart = db ? (float*)((char*)ws + 256 + wgradw_slab_bytes(pw, KT)) : nullptr;
-      hipStream_t s = (hipStream_t)stream;
-      const dim3 grid((KT == 3 ? 2 * pw.S0 + pw.S : pw.S) * pw.nob * pw.ncb);
-      const int njd = pw.DS > 256 ? 2 : 1, njx = pw.XS > 256 ? 2 : 1;
-      // whole channel rows per wave (WCH) where an instance exists for the row lengths: pieces of 64 lanes
-      const int wjd = hpvg_cdiv(pw.DS, 64), wjx = hpvg_cdiv(pw.XS, 64);
-      // 16-byte form: pieces of 64 groups
-      const int gjd = hpvg_cdiv(pw.Th * (pw.Tw / 4), 64), gjx = hpvg_cdiv((pw.Th + 2) * (pw.Tw / 4 + 2), 64);
-      static const int wch_mode = [] { const char* e = getenv("HPVG_WGRADW_WCH"); return e ? atoi(e) : 1; }();
-#define HPVG_WW_LAUNCH(K, D, X, C, G, E)                                                                               \
-  {                                                                                                                    \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgradw_kernel<K, D, X, C, G, E>),                     \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                   \
-        (void)hipGetLastError();                                                                                       \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((conv_wgradw_kernel<K, D, X, C, G, E>), grid, dim3(E ? 512 : 256), pw.lds, s, a);               \
-  }
-      // eight waves (two per SIMD, half of the Winograd points each) for the whole-row staging forms: HPVG_WGRADW_W8=0 keeps four
-      const int w8_mode = g_wgradw_w8;
-#define HPVG_WW_WCH(K)                                                                                                 \
-  if (pw.g16 && gjd == 1 && gjx == 1 && w8_mode) HPVG_WW_LAUNCH(K, 1, 1, true, true, true)                             \
-  else if (pw.g16 && gjd == 1 && w8_mode) HPVG_WW_LAUNCH(K, 1, 2, true, true, true)                                    \
-  else if (pw.g16 && w8_mode) HPVG_WW_LAUNCH(K, 2, 2, true, true, true)                                                \
-  else if (pw.g16 && gjd == 1 && gjx == 1) HPVG_WW_LAUNCH(K, 1, 1, true, true, false)                                  \
-  else if (pw.g16 && gjd == 1) HPVG_WW_LAUNCH(K, 1, 2, true, true, false)                                              \
-  else if (pw.g16) HPVG_WW_LAUNCH(K, 2, 2, true, true, false)                                                          \
-  else if (wch_mode && wjd == 1 && wjx == 2) HPVG_WW_LAUNCH(K, 1, 2, true, false, false)                               \
-  else if (wch_mode && wjd == 1 && wjx == 3) HPVG_WW_LAUNCH(K, 1, 3, true, false, false)                               \
-  else if (wch_mode && wjd == 2 && wjx == 3) HPVG_WW_LAUNCH(K, 2, 3, true, false, false)                               \
-  else if (wch_mode && wjd == 2 && wjx == 4) HPVG_WW_LAUNCH(K, 2, 4, true, false, false)                               \
-  else if (njd == 1 && njx == 1) HPVG_WW_LAUNCH(K, 1, 1, false, false, false)                                          \
-  else if (njd == 1) HPVG_WW_LAUNCH(K, 1, 2, false, false, false)                                                      \
-  else HPVG_WW_LAUNCH(K, 2, 2, false, false, false)
-      if (KT == 3) {
-        HPVG_WW_WCH(3)
-      } else {
-        HPVG_WW_WCH(1)
-      }
-#undef HPVG_WW_WCH
-#undef HPVG_WW_LAUNCH
-      int stw = hpvg_launch_status();
-      if (stw != HPVG_OK) return stw;
-      const long totw = (long)KT * pw.nob * pw.ncb * 3 * 4096;
-      const int nbw = hpvg_cdiv(totw, 128);
-      hipLaunchKernelGGL(conv_wgradw_reduce_kernel, dim3(nbw + (db ? hpvg_cdiv(Cout, 128) : 0)), dim3(128, 8), 0, s, (const float*)a.part,
-                         dw, pw.S, pw.S0, KT, pw.nob, pw.ncb, Cout, Cin, accumulate, nbw, (const float*)a.bpart, db, accumulate_db);
-      return hpvg_launch_status();
-    }
-  }
-  if (db) return HPVG_ERR_UNSUPPORTED;   // (only the Winograd kernel above produces the bias gradient)
-  if (KT == 3) {
-    const W3Plan q = plan_wgrad3(B, Cin, Cout, T, H, W);
-    if (wgrad3_wanted(q)) {
-      // ---- all 27 taps in one workgroup (conv_wgrad3_kernel)
-      if (ws_bytes < wgrad3_ws_bytes(q)) return HPVG_ERR_WORKSPACE;
-      Wgrad3Args w3;
-      w3.dy = dy; w3.x = x; w3.part = (float*)((char*)ws + 256);
-      w3.B = B; w3.Cin = Cin; w3.Cout = Cout; w3.T = T; w3.H = H; w3.W = W;
-      w3.Th = q.Th; w3.Tw = q.Tw; w3.RS = q.RS; w3.DS = q.DS; w3.XS = q.XS; w3.QK = q.QK; w3.nth = q.nth; w3.ntw = q.ntw;
-      w3.S = q.S; w3.ncb = q.ncb; w3.nob = q.nob; w3.ntiles = (int)q.ntiles;
-      hipStream_t s3 = (hipStream_t)stream;
-      const dim3 grid3((unsigned)(q.S * q.nob * q.ncb));
-      {
-        static bool attr = false;
-        if (!attr) {
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024) != hipSuccess)
-            (void)hipGetLastError();
-          attr = true;
-        }
-        hipLaunchKernelGGL(conv_wgrad3_kernel, grid3, dim3(256), q.lds, s3, w3);
-      }
-      int st3 = hpvg_launch_status();
-      if (st3 != HPVG_OK) return st3;
-      const long total3 = (long)q.nob * q.ncb * 27 * 2048;
-      hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3(hpvg_cdiv(total3, 256)), dim3(256, 4), 0, s3, (const float*)w3.part, dw, q.S,
-                         q.nob, q.ncb, Cout, Cin, accumulate);
-      return hpvg_launch_status();
-    }
-  }
-  const size_t need = 256 + (size_t)p.S * KT * p.nob * p.ncb * 9 * 4096 * sizeof(float);
-  if (ws_bytes < need) return HPVG_ERR_WORKSPACE;
-  WgradArgs a;
-  a.dy = dy; a.x = x; a.in_scale = in_scale; a.in_shift = in_shift;
-  a.part = (float*)((char*)ws + 256);
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.H = H; a.W = W;
-  a.Th = p.Th; a.Tw = p.Tw; a.RS = p.RS; a.DS = p.DS; a.XS = p.XS; a.QK = p.QK; a.nth = p.nth; a.ntw = p.ntw;
-  a.S = p.S; a.S0 = p.S0; a.ncb = p.ncb; a.nob = p.nob; a.in_lrelu = in_lrelu; a.bpart = nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((KT == 3 ? 2 * p.S0 + p.S : p.S) * p.nob * p.ncb);
-  const int njd = p.DS > 256 ? 2 : 1, njx = p.XS > 256 ? 2 : 1;
-#define HPVG_WG_LAUNCH(K, D, X)                                                                                        \
-  {                                                                                                                    \
-    static bool attr = false;                                                                                          \
-    if (!attr) {                                                                                                       \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel<K, D, X>),                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                   \
-        (void)hipGetLastError();                                                                                       \
-      attr = true;                                                                                                     \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((conv_wgrad_kernel<K, D, X>), grid, dim3(256), p.lds, s, a);                                    \
-  }
-  if (KT == 3) {
-    if (njd == 1 && njx == 1) HPVG_WG_LAUNCH(3, 1, 1)
-    else if (njd == 1) HPVG_WG_LAUNCH(3, 1, 2)
-    else HPVG_WG_LAUNCH(3, 2, 2)
-  } else {
-    if (njd == 1 && njx == 1) HPVG_WG_LAUNCH(1, 1, 1)
-    else if (njd == 1) HPVG_WG_LAUNCH(1, 1, 2)
-    else HPVG_WG_LAUNCH(1, 2, 2)
-  }
-#undef HPVG_WG_LAUNCH
-  int st = hpvg_launch_status();
-  if (st != HPVG_OK) return st;
-  const long per_s = (long)KT * p.nob * p.ncb * 9 * 4096;
-  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(hpvg_cdiv(per_s, 256)), dim3(256), 0, s, (const float*)a.part, dw, p.S, p.S0, KT,
-                     p.nob, p.ncb, Cout, Cin, accumulate);
-  return hpvg_launch_status();
 }
 
 // out[c] (+)= sum over batch and all spatial positions of x[b][c][...]  (conv bias gradient); ws: C*64 doubles
@@ -1789,71 +1741,55 @@ int hpvg_channel_sum_f32(const float* x, float* out, int accumulate, void* ws, s
 // kernel (conv_wgradw2_kernel) on every wide layer; 6 = the one-axis kernel only; a negative mode only queries.
 // Returns the mode in force.
 int hpvg_conv_bwd_weight_wino_config(int mode) {
-  (void)wgradw_wanted(WPlan{}, 1, 8, 8, 1, 1, 1, 1);   // settle the defaults
-  (void)wgradw2_wanted(WPlan{}, 1, 8, 8, 1, 1, 1, 1);
-  (void)plan_wgradw16_search(1, 8, 8, 1, 1, 1, 1);
-  static const int env_g16 = g_wgradw_g16, env_w8 = g_wgradw_w8, env_w2 = g_wgradw2;
-  static int four_byte_only = 0, four_waves = 0;
+  WKnobs& k = wknobs();
   if (mode >= 0) {
-    four_byte_only = mode == 3;
-    four_waves = mode == 4;
-    g_wgradw_w8 = four_waves ? 0 : env_w8;
-    g_wgradw_mode = mode > 2 ? 2 : mode;
+    k.four_byte_only = mode == 3;
+    k.four_waves = mode == 4;
+    k.w8 = k.four_waves ? 0 : k.env_w8;
+    k.wino = mode > 2 ? 2 : mode;
     // 5: the two-axis kernel wherever it can run; 2 / 3 / 4 / 6: the one-axis kernel only (2: its default staging forms);
     // 0 / 1: as the process started (HPVG_WGRADW2)
-    g_wgradw2 = mode == 5 ? 2 : (mode == 2 || mode == 3 || mode == 4 || mode == 6 ? 1 : env_w2);
-    const int g16 = mode == 3 ? 0 : env_g16;
-    if (g16 != g_wgradw_g16) {
-      g_wgradw_g16 = g16;
-      ++g_wgradw_gen;
+    k.w2 = mode == 5 ? 2 : (mode == 2 || mode == 3 || mode == 4 || mode == 6 ? 1 : k.env_w2);
+    const int g16 = mode == 3 ? 0 : k.env_g16;
+    if (g16 != k.g16) {
+      k.g16 = g16;
+      ++k.gen;
     }
   }
-  if (g_wgradw_mode == 2 && g_wgradw2 == 2) return 5;
-  if (g_wgradw_mode == 2 && four_byte_only) return 3;
-  if (g_wgradw_mode == 2 && four_waves) return 4;
-  return g_wgradw_mode;
+  if (k.wino == 2 && k.w2 == 2) return 5;
+  if (k.wino == 2 && k.four_byte_only) return 3;
+  if (k.wino == 2 && k.four_waves) return 4;
+  return k.wino;
 }
 
 // host only: which kernel family hpvg_conv_bwd_weight_f32 runs this shape on: 0 = conv_wgrad_kernel (direct, a workgroup per
 // time tap), 1 = conv_wgrad3_kernel (direct, all taps per workgroup), 2 = conv_wgradw_kernel (Winograd along W: 2/3 of the direct
 // matrix-core work), 3 = conv_wgradw2_kernel (Winograd over H and W: 4/9), 4 = the narrow kernels (heads / tails)
 int hpvg_conv_bwd_weight_kernel_kind(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1 || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  if (narrow_mode(Cin, Cout) >= 0) return 4;
-  if (wgradw2_wanted(plan_wgradw2(B, Cin, Cout, T, H, W, KT), B, Cin, Cout, T, H, W, KT)) return 3;
-  if (wgradw_wanted(plan_wgradw(B, Cin, Cout, T, H, W, KT), B, Cin, Cout, T, H, W, KT)) return 2;
-  if (KT == 3 && wgrad3_wanted(plan_wgrad3(B, Cin, Cout, T, H, W))) return 1;
-  return 0;
+  if (!wgrad_dims_ok(B, Cin, Cout, T, H, W, KT)) return HPVG_ERR_ARG;
+  return wgrad_decide(B, Cin, Cout, T, H, W, KT).kind;
 }
 
 // host only: the tile plan of the Winograd weight-gradient kernel: out[0..9] as hpvg_conv_bwd_weight_plan
 int hpvg_conv_bwd_weight_wino_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
-  if (!out || (KT != 1 && KT != 3) || B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
-  const WPlan p = plan_wgradw(B, Cin, Cout, T, H, W, KT);
-  if (p.Th == 0) return HPVG_ERR_UNSUPPORTED;
-  out[0] = p.Th; out[1] = p.Tw; out[2] = p.nth; out[3] = p.ntw; out[4] = p.QK; out[5] = p.S; out[6] = p.DS; out[7] = p.XS;
-  out[8] = (int)p.lds; out[9] = B * T * p.nth * p.ntw;
-  return HPVG_OK;
+  if (!out || !wgrad_dims_ok(B, Cin, Cout, T, H, W, KT)) return HPVG_ERR_ARG;
+  const WPlan& p = wgrad_plans(wknobs(), B, Cin, Cout, T, H, W, KT).wino;
+  return p.Th == 0 ? HPVG_ERR_UNSUPPORTED : write_plan(p, B, T, out);
 }
 
 // host only: the tile plan of the two-axis Winograd weight-gradient kernel (conv_wgradw2_kernel): out[0..9] as
-// hpvg_conv_bwd_weight_plan, out[10] = 1 when this shape runs it by default (the size rule); HPVG_ERR_UNSUPPORTED when no tile fits
+// hpvg_conv_bwd_weight_plan, out[10] = 1 when this shape runs it under the mode in force; HPVG_ERR_UNSUPPORTED when no tile fits
 int hpvg_conv_bwd_weight_wino2_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
-  if (!out || (KT != 1 && KT != 3) || B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
-  const WPlan p = plan_wgradw2(B, Cin, Cout, T, H, W, KT);
-  if (p.Th == 0) return HPVG_ERR_UNSUPPORTED;
-  out[0] = p.Th; out[1] = p.Tw; out[2] = p.nth; out[3] = p.ntw; out[4] = p.QK; out[5] = p.S; out[6] = p.DS; out[7] = p.XS;
-  out[8] = (int)p.lds; out[9] = B * T * p.nth * p.ntw;
-  out[10] = wgradw2_wanted(p, B, Cin, Cout, T, H, W, KT) ? 1 : 0;
-  return HPVG_OK;
+  if (!out || !wgrad_dims_ok(B, Cin, Cout, T, H, W, KT)) return HPVG_ERR_ARG;
+  const WDecision d = wgrad_decide(B, Cin, Cout, T, H, W, KT);
+  if (d.plans->wino2.Th == 0) return HPVG_ERR_UNSUPPORTED;
+  out[10] = d.kind == 3;
+  return write_plan(d.plans->wino2, B, T, out);
 }
 
 int hpvg_conv_bwd_weight_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
   if (!out || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  const WPlan p = plan_wgrad(B, Cin, Cout, T, H, W, KT);
-  out[0] = p.Th; out[1] = p.Tw; out[2] = p.nth; out[3] = p.ntw; out[4] = p.QK; out[5] = p.S; out[6] = p.DS; out[7] = p.XS;
-  out[8] = (int)p.lds; out[9] = B * T * p.nth * p.ntw;
-  return HPVG_OK;
+  return write_plan(wgrad_plans(wknobs(), B, Cin, Cout, T, H, W, KT).tap, B, T, out);
 }
 
 }  // extern "C"

@@ -169,6 +169,10 @@ class StageTrainer:
         # test hook: callable(trainer) run right after the discriminator's optimizer step (the parity tests put the reference's
         # post-step critic in place there, so that the generator step is judged from an identical state: see tests/helpers.py)
         self.after_d_step = None
+        # test hook, read from opt so that train() hands it on: callable(n, device) -> list of n one-element fp32 device
+        # tensors, the gradient penalty's alphas of one iteration (n = 1).  The iteration reads them by address, so a captured
+        # iteration sees on every replay what the caller wrote there before it.  None: alpha is drawn as step() describes
+        self.alpha_source = getattr(opt, "alpha_source", None)
         # telemetry.LossLog with the columns of loss_log_columns(self.is_gan), or None: each iteration then ends with one
         # append of its scalars, which a captured iteration replays (no host synchronisation per iteration)
         self.loss_log = None
@@ -194,7 +198,8 @@ class StageTrainer:
     def enable_graph(self, real, real_zero):
         """Capture one iteration into a hipGraph and replay it from then on (call after >= 1 eager iteration, i.e.
         after the noise-amplitude calibration and once every workspace has its final size).  Inside the graph the GP
-        alpha is drawn from the DEVICE generator (a fresh host->device copy cannot be replayed); Adam reads its step
+        alpha is drawn from the DEVICE generator (a fresh host->device copy cannot be replayed) unless alpha_source
+        supplies it; Adam reads its step
         count from device memory.  Inputs are copied into static buffers before each replay."""
         if self.iteration < 1:
             raise RuntimeError("run one eager iteration first (noise-amplitude calibration is not capturable)")
@@ -220,7 +225,9 @@ class StageTrainer:
         opt, netG = self.opt, self.netG
         if real.is_cuda:
             ops.rng_next_iteration(real.device)   # the library's noise stream: (seed, iteration on the device, call index)
-        if alpha is None and getattr(self, '_graph_alpha', False):
+        if alpha is None and self.alpha_source is not None:
+            alpha = self.alpha_source(1, real.device)[0]
+        elif alpha is None and getattr(self, '_graph_alpha', False):
             alpha = torch.rand(1, device=real.device)
         if noise_init is None:
             noise_init = utils.generate_noise(size=opt.Z_init_size, device=opt.device)
@@ -368,6 +375,7 @@ class BaselineStageTrainer:
         self.optimizerG = hp_optim.FlatAdam(self.arenaG, groups, betas=(opt.beta1, 0.999))
         self.iteration = 0
         self.after_d_step = None   # test hook: callable(trainer, j) after the j-th discriminator update (see StageTrainer)
+        self.alpha_source = getattr(opt, "alpha_source", None)   # test hook (see StageTrainer): n = opt.Dsteps alphas per iteration
         # telemetry.LossLog with the columns of baseline_loss_log_columns(opt.alpha), or None (see StageTrainer.loss_log)
         self.loss_log = None
 
@@ -392,7 +400,9 @@ class BaselineStageTrainer:
         opt, netG, netD = self.opt, self.netG, self.netD
         if real.is_cuda:
             ops.rng_next_iteration(real.device)
-        if alphas is None and getattr(self, '_graph_alpha', False):
+        if alphas is None and self.alpha_source is not None:
+            alphas = self.alpha_source(opt.Dsteps, real.device)
+        elif alphas is None and getattr(self, '_graph_alpha', False):
             alphas = [torch.rand(1, device=real.device) for _ in range(opt.Dsteps)]
         if noise_init is None:
             noise_init = utils.generate_noise(ref=opt.Z_init)

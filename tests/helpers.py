@@ -325,3 +325,149 @@ def compare_step(what, rec, spread, got, rtol=RTOL):
             if _bn_fed_bias(n, names):
                 atol = max(bn_bias_atol(n, rec[key], 1e-7), 0.0)
             assert_close(mine, g, rtol, "%s.%s.%s" % (what, key, n), atol=atol)
+
+
+# ------------------------------------------------------------------------------------------------ eager == hipGraph replay, exactly
+class AlphaFeed:
+    """`alpha_source` of the trainers (train.StageTrainer.alpha_source): views of ONE persistent device buffer of `n` floats.
+    `write(it)` fills the buffer on the current stream with iteration `it`'s alphas, device to device (no host wait, so replays
+    stay back to back), from a table fixed by a seeded CPU generator.  A captured iteration reads the buffer by address, so a
+    replay sees what was written just before it."""
+
+    def __init__(self, n, iters, device, seed=20240607):
+        g = torch.Generator().manual_seed(seed)
+        self.host = torch.rand(iters, n, generator=g)
+        self.table = self.host.to(device)
+        self.buf = torch.zeros(n, dtype=torch.float32, device=device)
+        self.views = [self.buf[j:j + 1] for j in range(n)]
+        self.calls = 0
+
+    def write(self, it):
+        self.buf.copy_(self.table[it])
+
+    def __call__(self, n, device):
+        assert n == len(self.views) and torch.device(device).type == self.buf.device.type, (n, device)
+        self.calls += 1
+        return self.views
+
+
+# the keys of an iteration's `out` in the order the iteration computes them (params_D / params_G: the parameter arenas right
+# after the iteration, loss_log_row: its row of the device loss log); a key that is not listed is compared after these
+STEP_ORDER = ["mu", "logvar", "generated_vae", "generated", "fake", "rec_vae_loss", "kl_loss", "errD_real", "errD_fake",
+              "gradient_penalty", "gradD_flat", "params_D", "rec_loss", "errG", "total_loss", "gradG_flat", "clip_info",
+              "params_G", "loss_log_row"]
+BASELINE_ORDER = ["errD_real", "fake", "errD_fake", "gradient_penalty", "gradD_flat", "params_D", "errG", "generated",
+                  "rec_loss", "gradG_flat", "params_G", "loss_log_row"]
+
+
+def _snapshot(trainer, out):
+    """Device clones of everything in `out` (a replay's outputs are static buffers that the next replay overwrites) plus the
+    two parameter arenas; no host synchronisation."""
+    rec = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in out.items()}
+    if getattr(trainer, "arenaD", None) is not None:
+        rec["params_D"] = trainer.arenaD.flat.clone()
+    rec["params_G"] = trainer.arenaG.flat.clone()
+    return rec
+
+
+def _to_host(x):
+    if torch.is_tensor(x):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return {k: _to_host(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_to_host(v) for v in x)
+    return x
+
+
+def run_iterations(trainer, inputs, feed, graph_after=None, sync=False):
+    """len(inputs) iterations of trainer.step(*inputs[i]), alphas of iteration i written to `feed` (or None) before it.
+    graph_after = k: k eager iterations, then enable_graph(*inputs[k]) - whose warm-up IS iteration k - then replays; None:
+    eager throughout.  sync: a device synchronise after every iteration.  Returns (records, final): per iteration the host copy
+    of _snapshot (with the iteration's loss-log row when the trainer has a log), and the end state - both networks'
+    state_dict, both optimizers' state_dict, clip_info and opt.Noise_Amps."""
+    recs = []
+    for i, args in enumerate(inputs):
+        if feed is not None:
+            feed.write(i)
+        if graph_after is not None and i == graph_after:
+            trainer.enable_graph(*args)
+            out = trainer.warmup_out
+        else:
+            out = trainer.step(*args)
+        recs.append(_snapshot(trainer, out))
+        if sync:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    assert trainer.iteration == len(inputs)
+    recs = [_to_host(r) for r in recs]
+    if trainer.loss_log is not None:
+        idx, rows, lost = trainer.loss_log.drain()
+        assert lost == 0 and idx.tolist() == list(range(len(inputs))), (idx, lost)
+        for r, row in zip(recs, rows):
+            r["loss_log_row"] = torch.from_numpy(row.copy())
+    final = {}
+    for tag in ("D", "G"):
+        net = getattr(trainer, "net" + tag, None)
+        if net is not None:
+            final["net%s.state_dict" % tag] = _to_host(dict(net.state_dict()))
+            final["optimizer%s.state_dict" % tag] = _to_host(getattr(trainer, "optimizer" + tag).state_dict())
+    if hasattr(trainer, "clip_info"):
+        final["clip_info"] = _to_host(trainer.clip_info)
+    final["Noise_Amps"] = list(trainer.opt.Noise_Amps)
+    return recs, final
+
+
+def first_difference(a, b, path=""):
+    """None when a and b (nested dicts / lists of tensors and plain values) are equal - tensors in dtype, shape and every
+    bit, and without NaNs - else a line naming the first entry that differs, in the containers' own order."""
+    if torch.is_tensor(a) or torch.is_tensor(b):
+        if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dtype != b.dtype or a.shape != b.shape:
+            return "%s: %s vs %s" % (path, _describe(a), _describe(b))
+        bits_a, bits_b = (a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)) if a.dtype == torch.float32 else (a, b)
+        if torch.equal(bits_a, bits_b) and torch.equal(a, b):
+            return None
+        bad = (bits_a != bits_b) | (a != b)
+        d = (a.double() - b.double()).abs()
+        return "%s: %d of %d elements differ (or are NaN), first at flat index %d: %r vs %r; max |a - b| = %.3e" % (
+            path, int(bad.sum()), a.numel(), int(bad.reshape(-1).nonzero()[0]), a.reshape(-1)[bad.reshape(-1)][0].item(),
+            b.reshape(-1)[bad.reshape(-1)][0].item(), float(d[~torch.isnan(d)].max()) if (~torch.isnan(d)).any() else float("nan"))
+    if isinstance(a, dict):
+        if not isinstance(b, dict) or list(a.keys()) != list(b.keys()):
+            return "%s: keys %s vs %s" % (path, list(a.keys()), list(b.keys()) if isinstance(b, dict) else type(b))
+        for k in a:
+            d = first_difference(a[k], b[k], "%s[%r]" % (path, k))
+            if d:
+                return d
+        return None
+    if isinstance(a, (list, tuple)):
+        if not isinstance(b, (list, tuple)) or len(a) != len(b):
+            return "%s: %r vs %r" % (path, a, b)
+        for i, (x, y) in enumerate(zip(a, b)):
+            d = first_difference(x, y, "%s[%d]" % (path, i))
+            if d:
+                return d
+        return None
+    return None if (type(a) is type(b) and a == b) else "%s: %r vs %r" % (path, a, b)
+
+
+def _describe(x):
+    return "%s%s" % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else repr(x)
+
+
+def ordered(rec, order):
+    """`rec` with its keys in `order`, unlisted keys after them (sorted): none is dropped."""
+    keys = [k for k in order if k in rec] + sorted(k for k in rec if k not in order)
+    return {k: rec[k] for k in keys}
+
+
+def assert_runs_identical(what, run_a, run_b, order):
+    """run_a, run_b: (records, final) of run_iterations.  Fails with the first iteration and, inside it, the first key in
+    computation order that differs; then the end state, critic first."""
+    (recs_a, final_a), (recs_b, final_b) = run_a, run_b
+    assert len(recs_a) == len(recs_b), what
+    for i, (ra, rb) in enumerate(zip(recs_a, recs_b)):
+        d = first_difference(ordered(ra, order), ordered(rb, order), "out")
+        assert d is None, "%s: first difference at iteration %d (0-based): %s" % (what, i, d)
+    d = first_difference(final_a, final_b, "end state ")
+    assert d is None, "%s: every iteration's outputs agree, but: %s" % (what, d)

@@ -179,10 +179,12 @@ def test_baseline_singan_step_matches_reference(fname, generator, critic):
 
 @pytest.mark.parametrize("fname", ["step3d_gan_s3.pt", "step3d_vae_s1.pt"])
 def test_graph_replay_equals_eager(fname):
-    """hipGraph capture of the iteration (StageTrainer.enable_graph): replays must produce what eager steps produce.
-    Noise is pinned by a cycling noise_source so that both runs see identical draws; alpha is injected in the eager
-    run and pinned in the graph run by seeding the device generator identically."""
-    from helpers import hip_opt
+    """hipGraph capture of the iteration (StageTrainer.enable_graph): replays must produce what eager steps produce, bit for
+    bit.  Noise is pinned by a cycling noise_source and a fixed noise_init, so that both runs see identical draws whatever the
+    library's stream does; the gradient penalty's alphas reach both runs through alpha_source (helpers.AlphaFeed).  The same
+    `real` every iteration.  (tests/test_graph_replay_exact.py: the library's own noise, changing inputs, every output.)"""
+    from helpers import AlphaFeed, first_difference, hip_opt
+    from hp_vae_gan_amd import ops as hp_ops
     from hp_vae_gan_amd import train as hp_train
     from hp_vae_gan_amd.modules import networks_3d
     fx = load_golden(fname)
@@ -191,6 +193,7 @@ def test_graph_replay_equals_eager(fname):
     rec = fx["iters"][0]
 
     def build():
+        hp_ops._rng_states.clear()           # both runs start the library's noise stream at iteration 0 (calibration pass draws)
         opt = hip_opt(fx["opt"], 3, s, dev)
         netG = networks_3d.GeneratorHPVAEGAN(opt)
         for _ in range(s):
@@ -203,6 +206,7 @@ def test_graph_replay_equals_eager(fname):
             netD.load_state_dict(fx["D_init"])
             netD.to(dev)
         opt.Noise_Amps = list(fx["noise_amps_init"])
+        opt.alpha_source = AlphaFeed(1, 8, dev)
         tr = hp_train.StageTrainer(opt, netG, netD)
         noises = {tuple(t.shape): t.to(dev) for t in rec["noises"]}
         netG.noise_source = lambda ref: noises[tuple(ref.shape)]     # the same draw for a given shape, every time
@@ -219,20 +223,21 @@ def test_graph_replay_equals_eager(fname):
         T.utils.generate_noise = lambda ref=None, size=None, type='normal', emb_size=None, device=None: ni if size is not None else orig(ref=ref)
         a_tr, a_G, a_D = build()
         torch.manual_seed(7)
-        a_tr.step(real, rz)
-        for _ in range(7):
-            a_tr._graph_alpha = True
+        for it in range(8):
+            a_tr.alpha_source.write(it)
             a_tr.step(real, rz)
         b_tr, b_G, b_D = build()
         torch.manual_seed(7)
+        b_tr.alpha_source.write(0)
         b_tr.step(real, rz)
+        b_tr.alpha_source.write(1)
         b_tr.enable_graph(real, rz)          # runs one warm-up iteration (eager, side stream) + capture (no execution)
         # the graph bakes in the scratch buffer's address: a later, larger request must not free that buffer
-        from hp_vae_gan_amd import ops as hp_ops
         baked = hp_ops.workspace(1, real.device)
         grown = hp_ops.workspace(baked.numel() + (1 << 20), real.device)
         assert grown is not baked and any(b is baked for b in hp_ops._ws_pinned)
-        for _ in range(6):
+        for it in range(2, 8):
+            b_tr.alpha_source.write(it)
             out = b_tr.step(real, rz)        # replays
             # a device synchronise between replays: this is what exposed hipMemsetAsync nodes being mis-ordered inside a
             # captured graph (upsample backward scattered into a buffer zeroed too late; back-to-back replays hid it)
@@ -240,24 +245,28 @@ def test_graph_replay_equals_eager(fname):
             assert torch.isfinite(out["clip_info"]).all() and float(out["clip_info"][1]) < 1e4, out["clip_info"]
     finally:
         T.utils.generate_noise = orig
-    # a: 1 + 7 eager iterations; b: 1 eager + 1 warm-up + 6 replays = 8 iterations.  alpha draws differ between the
-    # runs (device generator offsets under capture), so GAN-stage parameters agree only to the Adam step scale.
-    lr = fx["opt"]["lr_g"] * 8
-    for (k, va), (_, vb) in zip(a_G.state_dict().items(), b_G.state_dict().items()):
-        assert torch.isfinite(vb.float()).all(), k
-        # VAE stage: identical draws -> equal up to the float-atomic order of upsample_bwd and Adam's amplification of it
-        assert_close(vb.float(), va.float(), 2e-2 if fx["D_init"] is not None else 1e-3, "graph.G." + k, atol=2 * lr if fx["D_init"] is not None else lr)  # conv biases feeding BN drift by +-lr per step
+    # a: 8 eager iterations; b: 1 eager + 1 warm-up + 6 replays = 8 iterations on the same draws, the same alphas, kernels
+    # without float atomics: the same bits
     assert b_tr.iteration == a_tr.iteration == 8
+    for net_a, net_b, tag in ((a_G, b_G, "G"), (a_D, b_D, "D")):
+        if net_a is None:
+            continue
+        sd_a, sd_b = net_a.state_dict(), net_b.state_dict()
+        for k, vb in sd_b.items():
+            assert torch.isfinite(vb.float()).all(), k
+            assert torch.equal(vb, sd_a[k]), first_difference(sd_a[k].cpu(), vb.cpu(), "graph.%s.%s (eager vs replay)" % (tag, k))
+        assert list(sd_a) == list(sd_b)
 
 
 @pytest.mark.parametrize("fname,critic", [("baseline3d_s2.pt", "WDiscriminator3D"), ("baseline3d_dbl_s1.pt", "WDiscriminatorBaselines")])
 def test_baseline_graph_replay_tracks_eager(fname, critic):
     """hipGraph capture of the baselines' iteration (BaselineStageTrainer.enable_graph; Dsteps = 2 in baseline3d_s2, the
     BatchNorm critic and its double backward in baseline3d_dbl_s1): the captured graph holds kernel nodes only (enable_graph
-    refuses anything else), replays stay finite with a device synchronise in between, and after 8 iterations the
-    parameters sit within the Adam step scale of an eager run fed the same noise (the alphas differ: device generator
-    offsets under capture), BatchNorm counters included."""
-    from helpers import hip_opt
+    refuses anything else), replays stay finite with a device synchronise in between, and after 8 iterations both networks -
+    parameters, BatchNorm statistics and counters, spectral-norm u / v - hold the bits of an eager run fed the same noise
+    (a cycling noise_source) and the same alphas (alpha_source)."""
+    from helpers import AlphaFeed, first_difference, hip_opt
+    from hp_vae_gan_amd import ops as hp_ops
     from hp_vae_gan_amd import train as hp_train
     from hp_vae_gan_amd.modules import networks_3d
     fx = load_golden(fname)
@@ -266,6 +275,9 @@ def test_baseline_graph_replay_tracks_eager(fname, critic):
     rec = fx["iters"][0]
 
     def build():
+        # noise_init is the one draw this test leaves to the library's stream (generate_noise(ref=opt.Z_init)): both runs
+        # start that stream at iteration 0, or the second would continue where the first stopped
+        hp_ops._rng_states.clear()
         opt = hip_opt(fx["opt"], 3, s, dev)
         netG = networks_3d.GeneratorSG(opt)
         for _ in range(s):
@@ -277,6 +289,7 @@ def test_baseline_graph_replay_tracks_eager(fname, critic):
         netD.to(dev)
         opt.Noise_Amps = list(fx["noise_amps_init"])
         opt.Z_init = fx["Z_init"].to(dev)
+        opt.alpha_source = AlphaFeed(opt.Dsteps, 8, dev)
         tr = hp_train.BaselineStageTrainer(opt, netG, netD)
         noises = {tuple(t.shape): t.to(dev) for t in rec["noises"]}
         netG.noise_source = lambda ref: noises[tuple(ref.shape)]     # the same draw for a given shape, every time
@@ -285,31 +298,29 @@ def test_baseline_graph_replay_tracks_eager(fname, critic):
     real = fx["real"].to(dev)
     a_tr, a_G, a_D = build()
     torch.manual_seed(7)
-    a_tr.step(real)
-    a_tr._graph_alpha = True
-    for _ in range(7):
+    for it in range(8):
+        a_tr.alpha_source.write(it)
         a_tr.step(real)
     b_tr, b_G, b_D = build()
     torch.manual_seed(7)
+    b_tr.alpha_source.write(0)
     b_tr.step(real)
+    b_tr.alpha_source.write(1)
     b_tr.enable_graph(real)              # one warm-up iteration (eager, side stream) + capture
     assert b_tr.graph_nodes.get("kernel", 0) > 50 and not b_tr.graph_nodes.get("memset", 0) and not b_tr.graph_nodes.get("memcpy", 0)
-    for _ in range(6):
+    for it in range(2, 8):
+        b_tr.alpha_source.write(it)
         out = b_tr.step(real)            # replays
         torch.cuda.synchronize()
         for k in ("errD_real", "errD_fake", "gradient_penalty", "errG", "rec_loss"):
             assert torch.isfinite(out[k]).all(), k
     assert b_tr.iteration == a_tr.iteration == 8
-    lr = fx["opt"]["lr_g"] * 8
     for net_a, net_b, tag in ((a_G, b_G, "G"), (a_D, b_D, "D")):
-        for (k, va), (_, vb) in zip(net_a.state_dict().items(), net_b.state_dict().items()):
+        sd_a, sd_b = net_a.state_dict(), net_b.state_dict()
+        assert list(sd_a) == list(sd_b)
+        for k, vb in sd_b.items():
             assert torch.isfinite(vb.float()).all(), k
-            if k.endswith("num_batches_tracked"):
-                assert int(va) == int(vb), "%s.%s: %d vs %d forward passes counted" % (tag, k, int(va), int(vb))
-            elif not k.endswith(("weight_u", "weight_v", "running_mean", "running_var")):
-                # (bound of two Adam trajectories that see different alphas: 2 lr per optimizer step, Dsteps of them per iteration)
-                steps = fx["opt"]["Dsteps"] if tag == "D" else 1
-                assert_close(vb.float(), va.float(), 2e-2, "baseline.graph.%s.%s" % (tag, k), atol=2 * lr * steps)
+            assert torch.equal(vb, sd_a[k]), first_difference(sd_a[k].cpu(), vb.cpu(), "baseline.graph.%s.%s (eager vs replay)" % (tag, k))
 
 
 @pytest.mark.parametrize("fname,iters", [("step3d_gan_s3.pt", 6), ("step3d_vae_s1.pt", 6)])

@@ -482,6 +482,101 @@ def test_graph_capture_refusal_restores_host_state(monkeypatch):
     assert [(m.pending_batches, d) for m, d in trainer._graph_bn] == [(11, 2), (11, 2)]    # what every replay adds
 
 
+@pytest.mark.parametrize("kind", ["stage", "baseline"])
+def test_alpha_source_seam(kind, monkeypatch):
+    """The gradient penalty's alpha seam of both trainers on stub networks (no device): with alpha_source unset _step_eager
+    takes the paths it always took - alpha None handed to calc_gradient_penalty (which draws torch.rand(1, 1) on the CPU
+    generator), or, with _graph_alpha, torch.rand(1, device=...) per critic step; with it set, the source's own tensors reach
+    calc_gradient_penalty, torch.rand is never called and the CPU generator does not move; an explicit alpha / alphas argument
+    still wins."""
+    import types
+    from hp_vae_gan_amd import train as T
+
+    class G(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.ones(1))
+
+        def forward(self, x, amps, noise_init=None, mode="rand"):
+            return x * self.w
+
+        def forward_pair(self, rz, amps, noise_init):
+            y = rz * self.w
+            return y, y + 1, y, (y, y)
+
+    class D(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.ones(1))
+
+        def forward(self, x):
+            return x * self.w
+
+    seen = []
+
+    def penalty(netD, real, fake, lam, device, alpha=None):
+        seen.append(alpha)
+        return (fake.detach() * netD.w).mean()
+
+    monkeypatch.setattr(T, "calc_gradient_penalty", penalty)
+    monkeypatch.setattr(T, "wgan_mean", lambda x, sign: sign * x.mean())
+    monkeypatch.setattr(T, "mse_loss", lambda a, b: ((a - b) ** 2).mean())
+    rand_calls = []
+    real_rand = torch.rand
+    monkeypatch.setattr(torch, "rand", lambda *a, **k: rand_calls.append((a, k)) or real_rand(*a, **k))
+
+    def arena():
+        return types.SimpleNamespace(zero_grad=lambda: None, clip_grad_norm_=lambda *a: None, grad=None)
+
+    def adam():
+        return types.SimpleNamespace(step=lambda: None)
+
+    Dsteps = 2 if kind == "baseline" else 1
+    opt = types.SimpleNamespace(Noise_Amps=[1], lambda_grad=0.1, device="cpu", Dsteps=Dsteps, Gsteps=1, disc_loss_weight=1.0,
+                                rec_weight=10.0, alpha=10.0, grad_clip=5.0, Z_init=torch.zeros(1, 1, 2, 2, 2), scale_idx=1)
+    cls = T.StageTrainer if kind == "stage" else T.BaselineStageTrainer
+    tr = cls.__new__(cls)
+    tr.__dict__.update(opt=opt, netG=G(), netD=D(), is_gan=True, arenaG=arena(), arenaD=arena(), optimizerG=adam(), optimizerD=adam(),
+                       after_d_step=None, loss_log=None, iteration=1, clip_info=torch.zeros(2), last={},
+                       alpha_source=getattr(opt, "alpha_source", None))
+    real = torch.full((1, 1, 2, 2, 2), 0.5)
+    noise_init = torch.zeros(1, 1, 2, 2, 2)
+
+    def step(**kw):
+        del seen[:], rand_calls[:]
+        before = torch.get_rng_state()
+        if kind == "stage":
+            tr._step_eager(real, real, noise_init, **kw)
+        else:
+            tr._step_eager(real, noise_init, **kw)
+        assert len(seen) == Dsteps
+        return torch.equal(before, torch.get_rng_state())
+
+    # unset: today's paths
+    assert tr.alpha_source is None
+    assert step() and seen == [None] * Dsteps and not rand_calls          # (calc_gradient_penalty itself draws on the CPU generator)
+    tr._graph_alpha = True
+    assert not step() and len(rand_calls) == Dsteps                       # torch.rand(1, device=real.device): one per critic step
+    assert all(a == (1,) and k == {"device": real.device} for a, k in rand_calls)
+    assert all(torch.is_tensor(a) and a.shape == (1,) for a in seen)
+    # set: the source's tensors, nothing drawn - in eager mode and in the mode enable_graph switches on
+    buf = torch.tensor([0.25, 0.75])
+    views = [buf[j:j + 1] for j in range(Dsteps)]
+    asked = []
+    tr.alpha_source = lambda n, device: asked.append((n, device)) or views
+    for graph_alpha in (False, True):
+        tr._graph_alpha = graph_alpha
+        del asked[:]
+        assert step() and not rand_calls
+        assert asked == [(Dsteps, real.device)]
+        assert len(seen) == Dsteps and all(a is v for a, v in zip(seen, views))
+    # an explicit argument wins over the source
+    mine = [torch.tensor([0.5]) for _ in range(Dsteps)]
+    del asked[:]
+    assert step(**({"alpha": mine[0]} if kind == "stage" else {"alphas": mine})) and not asked and not rand_calls
+    assert all(a is m for a, m in zip(seen, mine))
+
+
 def test_two_axis_conv_is_bounded_by_its_zero_plane_and_offsets():
     """conv_wino2r_kernel stages a time plane outside the clip from a device plane of zeros (2^18 floats) and addresses its
     epilogue with 32-bit offsets: the size rule (host only) must hand larger planes / volumes to the one-axis kernel (kind 1)

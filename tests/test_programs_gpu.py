@@ -102,11 +102,17 @@ def _opt(niter):
     return opt
 
 
-def _run_stages(last, niter, with_log):
-    """Stages 0..last on one fixed batch; returns [(trainer, log, recorded rows)]."""
+def _run_stages(last, niter, with_log, hip_graph=True, feed_alphas=False):
+    """Stages 0..last on one fixed batch; returns [(trainer, log, recorded rows)].  hip_graph False: every iteration eager.
+    feed_alphas: the gradient penalty's alphas come through the trainer's alpha_source seam (helpers.AlphaFeed: the first is
+    written before train(), the callback writes the next iteration's), and the callback also makes the programs' preview draw
+    (Program.sample: a no_grad forward under ops.noise_stream) - the one thing between two replays that reads the packed-weight
+    cache."""
+    from helpers import AlphaFeed
     ops._rng_states.clear()
     torch.manual_seed(0)
     opt = _opt(niter)
+    opt.hip_graph = hip_graph
     assert opt.stop_scale == 5
     ds = datasets.SingleVideoDataset(opt)
     netG = networks_3d.GeneratorHPVAEGAN(opt).to(DEV)
@@ -125,10 +131,25 @@ def _run_stages(last, niter, with_log):
         log = telemetry.LossLog(cols, capacity=64, device=DEV) if with_log else None
         rec = []
 
-        def cb(trainer, out):
-            torch.cuda.synchronize()
-            rec.append([float(out[k]) for k in cols[:-1]] + [float(out["clip_info"][1])])
-        tr = hp_train.train(opt, netG, data, netD=netD, loss_log=log, callback=cb if with_log else None)
+        feed = AlphaFeed(1, niter, DEV, seed=100 + s) if feed_alphas else None
+        opt.alpha_source = feed
+        if feed is not None:
+            feed.write(0)
+
+        def cb(trainer, out, feed=feed, rec=rec):
+            if with_log:
+                torch.cuda.synchronize()
+                rec.append([float(out[k]) for k in cols[:-1]] + [float(out["clip_info"][1])])
+            if feed is not None:
+                if trainer.iteration < niter:
+                    feed.write(trainer.iteration)
+                with torch.no_grad(), ops.noise_stream(DEV):
+                    noise_init = hu.generate_noise(size=opt.Z_init_size, device=DEV)
+                    trainer.netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
+        tr = hp_train.train(opt, netG, data, netD=netD, loss_log=log, callback=cb if with_log or feed_alphas else None)
+        if feed is not None and netD is not None:
+            # train() handed opt.alpha_source on: asked once per iteration that passed through python (replays do not)
+            assert feed.calls == (4 if hip_graph else niter), feed.calls
         res.append((tr, log, rec))
     torch.cuda.synchronize()
     return res
@@ -178,6 +199,36 @@ def test_loss_log_under_replay_and_changes_nothing():
     for s in range(3):
         assert _equal_nested(_state(on[s][0]), _state(off[s][0])), s
         assert _equal_nested(_opt_state(on[s][0]), _opt_state(off[s][0])), s
+    print("wall %.1f s" % (time.time() - t0))
+
+
+def test_train_loop_with_replay_equals_eager_loop_bit_for_bit():
+    """train() itself, stages 0..2 (two VAE stages and a GAN stage), opt.hip_graph True against False: the switch to replays
+    after two eager iterations, the warm-up's callback, the re-capture of every stage on pinned workspaces, and each stage
+    starting from the weights a graph-trained stage left.  Exact: network state, optimizer state, the callback's scalars and
+    the drained loss-log rows (tests/test_graph_replay_exact.py has the per-iteration comparison of a single stage)."""
+    from helpers import first_difference
+    t0 = time.time()
+    on = _run_stages(2, 8, True, hip_graph=True, feed_alphas=True)
+    off = _run_stages(2, 8, True, hip_graph=False, feed_alphas=True)
+    for s in range(3):
+        (tr_on, log_on, rec_on), (tr_off, log_off, rec_off) = on[s], off[s]
+        assert tr_on._graph is not None and getattr(tr_off, "_graph", None) is None and tr_on.iteration == tr_off.iteration == 8
+        assert tr_on.optimizerG.steps() == tr_off.optimizerG.steps() == 8
+        idx_on, rows_on, lost_on = log_on.drain()
+        idx_off, rows_off, lost_off = log_off.drain()
+        assert lost_on == lost_off == 0 and idx_on.tolist() == idx_off.tolist() == list(range(8))
+        for i in range(8):
+            assert np.array_equal(rows_on[i].view(np.uint32), rows_off[i].view(np.uint32)), \
+                "stage %d: loss-log row %d (0-based) differs: replay %s, eager %s" % (s, i, rows_on[i], rows_off[i])
+        assert len(rec_on) == len(rec_off) == 8
+        assert np.array_equal(np.array(rec_on, np.float32).view(np.uint32), np.array(rec_off, np.float32).view(np.uint32)), s
+        d = first_difference(_state(tr_on), _state(tr_off), "stage %d state" % s)
+        assert d is None, d
+        assert _equal_nested(_state(tr_on), _state(tr_off)), s
+        d = first_difference(_opt_state(tr_on), _opt_state(tr_off), "stage %d optimizers" % s)
+        assert d is None, d
+        assert _equal_nested(_opt_state(tr_on), _opt_state(tr_off)), s
     print("wall %.1f s" % (time.time() - t0))
 
 

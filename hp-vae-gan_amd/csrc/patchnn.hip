@@ -55,6 +55,14 @@
 //      are associative and commutative, so the histogram is independent of the launch geometry and of timing.
 //   7. hist_w1_kernel: one workgroup per direction walks the NB bins of two histograms in chunks of 1024 with a carried block
 //      prefix sum and accumulates num = sum_b |Nb cA(b) - Na cB(b)| = Na Nb W1 in 64 bits (exact while Na Nb 256 D < 2^63).
+//
+// Copied regions of a nearest-neighbour field (the evaluate program's --chunks): the connected components of the query patch
+// grid under "6-neighbours whose nearest neighbours have the same displacement", by union-find in five launches on one stream
+// (nnf_chunks_*_kernel below).  labels doubles as the parent array; every link points to a smaller index, so a tree's root is
+// its smallest member and the labels are canonical without sorting.  The merge launch talks to other workgroups only through
+// relaxed agent-scope atomics on parent (the XCDs' L2s are not coherent: a plain load may miss another XCD's atomicMin), it
+// waits for nobody, and each of its loops strictly lowers an index per trip; whatever needs the finished forest is a later
+// launch.  Sizes and statistics are integer atomic adds / max, so all outputs are independent of launch geometry and timing.
 #include <limits.h>
 
 #include <type_traits>
@@ -855,6 +863,250 @@ int hpvg_hist_w1_i32(const int* histA, long Na, const int* histB, long Nb, int P
   if ((unsigned __int128)Na * (unsigned __int128)Nb * (unsigned __int128)(NB - 1) >= ((unsigned __int128)1 << 63)) return HPVG_ERR_ARG;
   hipLaunchKernelGGL(hist_w1_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, histA, histB, (long long)Na, (long long)Nb,
                      NB, num);
+  return hpvg_launch_status();
+}
+
+}  // extern "C"
+
+namespace {
+
+struct NnfGeom {
+  int gT, gH, gW;  // query patch grid
+  int kT, kH, kW;  // key patch grid
+  int qst, qsy, qsx;
+  int rst, rsy, rsx;
+  long Nq, Nr;
+};
+
+constexpr int NNF_MAX_BLOCKS = 8192;  // grid-stride past this many workgroups of 256
+
+// Whether patch i = (t, y, x) of the query grid is kept, and its displacement in voxels (b * rstride - a * qstride per axis, in
+// 64 bits: a product of two ints cannot overflow).  nn[i] is only decoded, never used as an address.
+__device__ __forceinline__ bool nnf_disp(const int* __restrict__ nn, const int* __restrict__ d2, int max_d2, const NnfGeom& g, long i,
+                                         int t, int y, int x, long long& dt, long long& dy, long long& dx) {
+  const int j = nn[i];
+  if (j < 0 || j >= g.Nr) return false;
+  if (d2) {
+    const int d = d2[i];
+    if (d < 0 || d > max_d2) return false;
+  }
+  const unsigned kw = (unsigned)g.kW, khw = (unsigned)g.kH * (unsigned)g.kW;  // kH kW <= Nr < 2^31
+  const unsigned bt = (unsigned)j / khw, rem = (unsigned)j - bt * khw;
+  const unsigned by = rem / kw, bx = rem - by * kw;
+  dt = (long long)bt * g.rst - (long long)t * g.qst;
+  dy = (long long)by * g.rsy - (long long)y * g.qsy;
+  dx = (long long)bx * g.rsx - (long long)x * g.qsx;
+  return true;
+}
+
+__device__ __forceinline__ void nnf_coords(const NnfGeom& g, long i, int& t, int& y, int& x) {
+  const unsigned gw = (unsigned)g.gW, ghw = (unsigned)g.gH * (unsigned)g.gW;  // gH gW <= Nq < 2^31
+  const unsigned ut = (unsigned)i / ghw, rem = (unsigned)i - ut * ghw;
+  const unsigned uy = rem / gw;
+  t = (int)ut;
+  y = (int)uy;
+  x = (int)(rem - uy * gw);
+}
+
+__device__ __forceinline__ unsigned long long nnf_wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// launch 1: parent[i] = i for a kept patch and -1 otherwise; sizes and stats are cleared here (no memset node)
+__global__ __launch_bounds__(256) void nnf_chunks_init_kernel(const int* __restrict__ nn, const int* __restrict__ d2, int max_d2,
+                                                               NnfGeom g, int* __restrict__ parent, int* __restrict__ sizes,
+                                                               long long* __restrict__ stats) {
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gid < 6) stats[gid] = 0;
+  for (long i = gid; i < g.Nq; i += (long)gridDim.x * 256) {
+    const int j = nn[i];
+    bool kept = j >= 0 && j < g.Nr;
+    if (kept && d2) {
+      const int d = d2[i];
+      kept = d >= 0 && d <= max_d2;
+    }
+    parent[i] = kept ? (int)i : -1;
+    sizes[i] = 0;
+  }
+}
+
+// The root of x's tree as far as this thread can see it.  Every value ever stored in parent[x] of a kept patch is in [0, x]
+// (launch 1 stores x, the merge only lowers it with atomicMin), so every trip of the loop strictly lowers x: it ends after at
+// most x trips whatever other workgroups do.  The load is a relaxed agent-scope atomic, so it is served past this CU's L1 and
+// sees atomics from the other XCDs; a value that is stale all the same is an earlier parent, i.e. still a member of the tree.
+__device__ __forceinline__ int nnf_find(int* parent, int x) {
+  for (;;) {
+    const int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p >= x || p < 0) return x;  // p == x: a root (the other two cannot happen; they only keep a misused buffer in bounds)
+    x = p;
+  }
+}
+
+// Join the trees of a and b: the larger root is linked under the smaller one with atomicMin.  A trip that does not return
+// has found parent[a] already lowered by somebody else (old < a) and carries on with (old, b): the atomicMin left a under
+// min(old, b), so joining old and b is exactly what is still owed.  Each such trip replaces the larger of the two indices by a
+// strictly smaller one (the finds only lower them too), so a + b strictly decreases and the loop ends whatever other
+// workgroups do; nothing here waits for another thread.
+__device__ __forceinline__ void nnf_unite(int* parent, int a, int b) {
+  for (;;) {
+    a = nnf_find(parent, a);
+    b = nnf_find(parent, b);
+    if (a == b) return;
+    if (a < b) {
+      const int s = a;
+      a = b;
+      b = s;
+    }
+    const int old = __hip_atomic_fetch_min(parent + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == a) return;  // a was still a root and now hangs under b
+    a = old;
+  }
+}
+
+// launch 2: one thread per patch and its three forward pairs; kept, in_place and coherent_pairs are counted on the way and leave
+// as one 64-bit atomic per block and counter.  No path compression: parent is touched only by the loads and atomicMins above.
+__global__ __launch_bounds__(256) void nnf_chunks_merge_kernel(const int* __restrict__ nn, const int* __restrict__ d2, int max_d2,
+                                                                NnfGeom g, int* parent, long long* __restrict__ stats) {
+  __shared__ unsigned long long red[3][4];
+  unsigned long long kept = 0, inplace = 0, coh = 0;
+  const long plane = (long)g.gH * g.gW;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < g.Nq; i += (long)gridDim.x * 256) {
+    int t, y, x;
+    nnf_coords(g, i, t, y, x);
+    long long dt, dy, dx, et, ey, ex;
+    if (!nnf_disp(nn, d2, max_d2, g, i, t, y, x, dt, dy, dx)) continue;
+    ++kept;
+    inplace += (dt | dy | dx) == 0;
+    if (x + 1 < g.gW && nnf_disp(nn, d2, max_d2, g, i + 1, t, y, x + 1, et, ey, ex) && et == dt && ey == dy && ex == dx) {
+      ++coh;
+      nnf_unite(parent, (int)i, (int)(i + 1));
+    }
+    if (y + 1 < g.gH && nnf_disp(nn, d2, max_d2, g, i + g.gW, t, y + 1, x, et, ey, ex) && et == dt && ey == dy && ex == dx) {
+      ++coh;
+      nnf_unite(parent, (int)i, (int)(i + g.gW));
+    }
+    if (t + 1 < g.gT && nnf_disp(nn, d2, max_d2, g, i + plane, t + 1, y, x, et, ey, ex) && et == dt && ey == dy && ex == dx) {
+      ++coh;
+      nnf_unite(parent, (int)i, (int)(i + plane));
+    }
+  }
+  kept = nnf_wave_sum(kept);
+  inplace = nnf_wave_sum(inplace);
+  coh = nnf_wave_sum(coh);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][wave] = kept;
+    red[1][wave] = inplace;
+    red[2][wave] = coh;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const unsigned long long v = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (v) atomicAdd((unsigned long long*)stats + threadIdx.x, v);
+  }
+}
+
+// launch 3: label = root, in place.  The forest is final (launch 2 is over), so a racing reader finds in labels[k] either k's
+// parent or k's root, both on the way to the same root; the loop of nnf_find ends for the reason given there.
+__global__ __launch_bounds__(256) void nnf_chunks_flatten_kernel(int* labels, long N) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    const int p = __hip_atomic_load(labels + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (p < 0 || p == (int)i) continue;
+    const int r = nnf_find(labels, p);
+    if (r != p) __hip_atomic_store(labels + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// launch 4: sizes[label] += 1.  The lanes of a wave that share a label leave as one add: a rigid copy is ONE chunk, and one
+// atomic per patch on one word would serialise the whole grid.  The inner loop clears at least its leader's bit per trip and
+// involves this wave only.
+__global__ __launch_bounds__(256) void nnf_chunks_size_kernel(const int* __restrict__ labels, int* __restrict__ sizes, long N) {
+  const int lane = threadIdx.x & 63;
+  for (long base = (long)blockIdx.x * 256; base < N; base += (long)gridDim.x * 256) {  // uniform trip count per wave
+    const long i = base + threadIdx.x;
+    const int l = i < N ? labels[i] : -1;
+    unsigned long long todo = __ballot(l >= 0 && l < N);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const int ll = __shfl(l, leader, 64);
+      const unsigned long long same = __ballot(l == ll) & todo;
+      if (lane == leader) atomicAdd(sizes + ll, __popcll(same));
+      todo &= ~same;
+    }
+  }
+}
+
+// launch 5: chunks, largest, sum_sq over the roots (labels[i] == i), reduced per block before one 64-bit atomic each
+__global__ __launch_bounds__(256) void nnf_chunks_stats_kernel(const int* __restrict__ labels, const int* __restrict__ sizes, long N,
+                                                                long long* __restrict__ stats) {
+  __shared__ unsigned long long red[3][4];
+  unsigned long long chunks = 0, largest = 0, sumsq = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
+    if (labels[i] != (int)i) continue;
+    const unsigned long long s = (unsigned long long)(unsigned)sizes[i];
+    ++chunks;
+    largest = s > largest ? s : largest;
+    sumsq += s * s;
+  }
+  chunks = nnf_wave_sum(chunks);
+  sumsq = nnf_wave_sum(sumsq);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long v = __shfl_xor(largest, o, 64);
+    largest = v > largest ? v : largest;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][wave] = chunks;
+    red[1][wave] = largest;
+    red[2][wave] = sumsq;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long c = 0, m = 0, q = 0;
+    for (int w = 0; w < 4; ++w) {
+      c += red[0][w];
+      m = red[1][w] > m ? red[1][w] : m;
+      q += red[2][w];
+    }
+    if (c) {
+      atomicAdd((unsigned long long*)stats + 3, c);
+      atomicMax((unsigned long long*)stats + 4, m);
+      atomicAdd((unsigned long long*)stats + 5, q);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpvg_nnf_chunks_i32(const int* nn, const int* d2, int max_d2, const int* qgrid, const int* rgrid, const int* qstride,
+                        const int* rstride, int* labels, int* sizes, long long* stats, void* stream) {
+  if (!nn || !labels || !sizes || !stats || !qgrid || !rgrid || !qstride || !rstride) return HPVG_ERR_ARG;
+  for (int a = 0; a < 3; ++a)
+    if (qgrid[a] < 1 || rgrid[a] < 1 || qstride[a] < 1 || rstride[a] < 1) return HPVG_ERR_ARG;
+  if ((double)qgrid[0] * (double)qgrid[1] * (double)qgrid[2] >= 2147483648.0) return HPVG_ERR_ARG;
+  if ((double)rgrid[0] * (double)rgrid[1] * (double)rgrid[2] >= 2147483648.0) return HPVG_ERR_ARG;
+  if (d2 && max_d2 < 0) return HPVG_ERR_ARG;
+  NnfGeom g;
+  g.gT = qgrid[0]; g.gH = qgrid[1]; g.gW = qgrid[2];
+  g.kT = rgrid[0]; g.kH = rgrid[1]; g.kW = rgrid[2];
+  g.qst = qstride[0]; g.qsy = qstride[1]; g.qsx = qstride[2];
+  g.rst = rstride[0]; g.rsy = rstride[1]; g.rsx = rstride[2];
+  g.Nq = (long)g.gT * g.gH * g.gW;
+  g.Nr = (long)g.kT * g.kH * g.kW;
+  long blocks = (g.Nq + 255) / 256;
+  if (blocks > NNF_MAX_BLOCKS) blocks = NNF_MAX_BLOCKS;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(nnf_chunks_init_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nn, d2, max_d2, g, labels, sizes, stats);
+  hipLaunchKernelGGL(nnf_chunks_merge_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nn, d2, max_d2, g, labels, stats);
+  hipLaunchKernelGGL(nnf_chunks_flatten_kernel, dim3((unsigned)blocks), dim3(256), 0, st, labels, g.Nq);
+  hipLaunchKernelGGL(nnf_chunks_size_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const int*)labels, sizes, g.Nq);
+  hipLaunchKernelGGL(nnf_chunks_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const int*)labels, (const int*)sizes, g.Nq,
+                     stats);
   return hpvg_launch_status();
 }
 

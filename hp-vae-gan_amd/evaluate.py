@@ -1,6 +1,7 @@
 """`python -m hp_vae_gan_amd.evaluate --exp-dir run/<clip>/<checkname>/experiment_<n>` (after `generate`), or
 `--samples S.npy --real R.npy` without an experiment: patch nearest-neighbour coherence / completeness, nn_unique_frac and
-diversity of the samples against the training clip, written to metrics.json."""
+diversity of the samples against the training clip, written to metrics.json; with --chunks also the copied-region statistics of
+the nearest-neighbour field."""
 import argparse
 import json
 import math
@@ -11,7 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume
+from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume, write_frames
 
 
 def evaluate_parser():
@@ -31,7 +32,21 @@ def evaluate_parser():
     p.add_argument('--swd', type=int, default=0, metavar='P', help='also report the exact sliced Wasserstein distance between the '
                    'patch distributions over P random directions with entries in {-1, 0, +1} (default 0: off)')
     p.add_argument('--swd-seed', type=int, default=0, help='seed of the directions')
+    p.add_argument('--chunks', action='store_true', help='also report the copied regions of each sample: the connected components '
+                   'of its patch grid under "neighbours whose nearest neighbours have the same displacement"')
+    p.add_argument('--chunk-tol', type=_nonneg_float, default=None, metavar='X', help='with --chunks (which it implies): only patches '
+                   'whose squared distance is at most floor(X * D * 255^2), X in the unit of coherence, belong to a chunk '
+                   '(default: every patch does)')
+    p.add_argument('--save-chunks', action='store_true', help='with --chunks (which it implies): write chunks.npz (labels, sizes, '
+                   'nn) and one source_XXXX.gif / .png per sample, coloured by where each patch came from')
     return p
+
+
+def _nonneg_float(text):
+    v = float(text)
+    if not (v >= 0.0 and math.isfinite(v)):
+        raise argparse.ArgumentTypeError("must be a finite number >= 0, got %s" % text)
+    return v
 
 
 def patch_score(d2, D):
@@ -94,9 +109,41 @@ def swd_score(num, Na, Nb, dirs):
     return sum((n / scale) / math.sqrt(z) for n, z in zip(num, nnz)) / len(num)   # n / scale: Python's correctly rounded int / int
 
 
-def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0):
+def pair_count(grid):
+    """E: the pairs of 6-neighbours of a patch grid (gT, gH, gW)."""
+    gT, gH, gW = (int(e) for e in grid)
+    return (gT - 1) * gH * gW + gT * (gH - 1) * gW + gT * gH * (gW - 1)
+
+
+def chunk_metrics(stats, Nq, E, kept_frac=False):
+    """The per-sample chunk scores from the integers of ops.nnf_chunks, stats = (kept, in_place, coherent_pairs, chunks, largest,
+    sum of size^2), each one Python int / int division: nnf_coherence = coherent_pairs / E (None for a grid without pairs),
+    chunks, largest_chunk_frac = largest / Nq, chunk_frac = sum_sq / Nq^2 (the expected share of the grid taken up by the chunk
+    of a random patch: 1.0 for a rigid copy, about 1 / Nq for an incoherent field), in_place_frac = in_place / Nq; with
+    kept_frac also chunk_kept_frac = kept / Nq."""
+    kept, in_place, pairs, chunks, largest, sum_sq = (int(v) for v in (stats.tolist() if hasattr(stats, "tolist") else stats))
+    Nq, E = int(Nq), int(E)
+    m = {"nnf_coherence": pairs / E if E > 0 else None, "chunks": chunks, "largest_chunk_frac": largest / Nq,
+         "chunk_frac": sum_sq / (Nq * Nq), "in_place_frac": in_place / Nq}
+    if kept_frac:
+        m["chunk_kept_frac"] = kept / Nq
+    return m
+
+
+def source_colours(nn, ref_grid):
+    """uint8 [..., 3] shaped as nn's patch grid: (R, G, B) = the (x, y, t) key coordinate of each patch's nearest neighbour,
+    coordinate c of an axis of k positions as the byte (2 * 255 * c + (k - 1)) // (2 * (k - 1)), 0 when k == 1."""
+    kT, kH, kW = (int(e) for e in ref_grid)
+    j = nn.to(torch.int64).clamp(0, kT * kH * kW - 1)
+    coords = ((j % kW, kW), ((j // kW) % kH, kH), (j // (kW * kH), kT))
+    return torch.stack([(2 * 255 * c + (k - 1)) // (2 * (k - 1)) if k > 1 else torch.zeros_like(c) for c, k in coords], -1).to(torch.uint8)
+
+
+def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0,
+             chunks=False, chunk_tol=None, save_chunks=False):
     """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
-    `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions."""
+    `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions.
+    chunks (implied by chunk_tol / save_chunks): also the copied-region statistics of the coherence direction's field."""
     if exp_dir is None and (samples is None or real is None):
         raise SystemExit("evaluate: give --exp-dir, or both --samples and --real")
     spath = samples or os.path.join(exp_dir, 'eval', 'samples', 'samples.npy')
@@ -129,6 +176,12 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
     coh_counts = ops.patch_nn_counts(vol(samples_dev[0]), vol(real_dev), patch, qstride=stride)
     com_counts = ops.patch_nn_counts(vol(real_dev), vol(samples_dev[0]), patch, qstride=stride)
     D = coh_counts[2]
+    chunks = bool(chunks or chunk_tol is not None or save_chunks)
+    if chunks:
+        ref_grid = tuple(v - p + 1 for v, p in zip(vol(real_dev), patch))   # the real side is dense
+        max_d2 = None if chunk_tol is None else min(int(math.floor(float(chunk_tol) * (D * 255 * 255))), 2 ** 31 - 1)
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        chunk_seconds, saved = 0.0, []
     per_sample = []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seconds = 0.0
@@ -141,6 +194,17 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         seconds += e0.elapsed_time(e1) / 1e3
         per_sample.append({"coherence": patch_score(d2c, D), "completeness": patch_score(d2r, D),
                            "nn_unique_frac": nn_unique_frac(nnc, coh_counts[1])})
+        if chunks:
+            c0.record()
+            labels, sizes, stats = ops.nnf_chunks(nnc, ref_grid, qstride=stride, d2=None if max_d2 is None else d2c, max_d2=max_d2)
+            c1.record()
+            c1.synchronize()
+            chunk_seconds += c0.elapsed_time(c1) / 1e3
+            grid = tuple(nnc.shape) if video else (1,) + tuple(nnc.shape)
+            per_sample[-1].update(chunk_metrics(stats.cpu(), coh_counts[0], pair_count(grid), max_d2 is not None))
+            if save_chunks:
+                saved.append((labels.cpu().numpy().reshape(grid), sizes.cpu().numpy().reshape(grid), nnc.cpu().numpy().reshape(grid),
+                              source_colours(nnc, ref_grid).cpu().numpy()))
     n = len(per_sample)
     metrics = {"samples": os.path.abspath(spath), "num_samples": n, "patch": list(patch), "stride": list(stride),
                "Nq": coh_counts[0], "Nr": coh_counts[1], "D": D, "Nq_completeness": com_counts[0], "Nr_completeness": com_counts[1],
@@ -163,19 +227,34 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         metrics.update({"swd": sum(p["swd"] for p in per_sample) / n, "swd_directions": int(swd), "swd_seed": int(swd_seed),
                         "swd_seconds": e0.elapsed_time(e1) / 1e3})
         swd_text = " swd {:.6f}".format(metrics["swd"])
+    chunk_text = ""
+    if chunks:
+        for k in ("nnf_coherence", "chunks", "largest_chunk_frac", "chunk_frac", "in_place_frac") + \
+                (("chunk_kept_frac",) if max_d2 is not None else ()):
+            vals = [p[k] for p in per_sample]
+            metrics[k] = None if any(v is None for v in vals) else sum(vals) / n
+        metrics.update({"chunk_tol": None if chunk_tol is None else float(chunk_tol), "chunk_seconds": chunk_seconds})
+        chunk_text = " chunk_frac {:.6f} nnf_coherence {}".format(
+            metrics["chunk_frac"], "n/a" if metrics["nnf_coherence"] is None else "{:.6f}".format(metrics["nnf_coherence"]))
+        if save_chunks:
+            np.savez(os.path.join(out, 'chunks.npz'), labels=np.stack([s[0] for s in saved]), sizes=np.stack([s[1] for s in saved]),
+                     nn=np.stack([s[2] for s in saved]))
+            for i, s in enumerate(saved):
+                write_frames(s[3], os.path.join(out, 'source_{:04d}{}'.format(i, '.gif' if video else '.png')), 10)
     with open(os.path.join(out, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1, sort_keys=True)
-    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{} "
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{} "
           "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
                                                metrics["nn_unique_frac"],
                                                "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
-                                               swd_text, seconds, os.path.join(out, 'metrics.json')))
+                                               swd_text, chunk_text, seconds, os.path.join(out, 'metrics.json')))
     return metrics
 
 
 def main(argv=None):
     a = evaluate_parser().parse_args(argv)
-    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed)
+    evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed, a.chunks, a.chunk_tol,
+             a.save_chunks)
     return 0
 
 

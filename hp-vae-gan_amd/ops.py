@@ -1448,6 +1448,49 @@ def patch_mask_count(mask_u8, patch, stride=(1, 1, 1)):
     return count[0] if image else count
 
 
+def nnf_chunks(nn, ref_grid, qstride=(1, 1, 1), rstride=(1, 1, 1), d2=None, max_d2=None):
+    """The copied regions of a nearest-neighbour field (hpvg_nnf_chunks_i32, a union-find over the patch grid): nn is an int32
+    device tensor shaped as a query patch grid [gT,gH,gW] (or [gH,gW], as patch_nn returns it for images: gT = 1) of indices
+    into the key patch grid ref_grid = (kT, kH, kW).  A patch is kept iff its index is in range and, with d2 (int32, shaped as
+    nn) and max_d2 given, 0 <= d2 <= max_d2; two 6-neighbours are joined iff both are kept and their displacements
+    key coordinate * rstride - grid coordinate * qstride are equal.  Returns (labels, sizes, stats): labels int32 shaped as nn
+    (the smallest flat index of the patch's chunk, -1 where not kept), sizes int32 shaped as nn (the chunk's size at its label,
+    0 elsewhere) and stats int64 [6] = kept, in_place, coherent_pairs, chunks, largest, sum of size^2.  Exact."""
+    if not isinstance(nn, torch.Tensor) or nn.dtype != torch.int32 or nn.dim() not in (2, 3) or nn.numel() < 1:
+        raise RuntimeError("nnf_chunks: nn must be a non-empty int32 patch grid [gT,gH,gW] or [gH,gW], got %s %s"
+                           % (getattr(nn, "dtype", type(nn)), tuple(getattr(nn, "shape", ()))))
+    if not nn.is_cuda:
+        raise RuntimeError("nnf_chunks: nn is on %s; this op runs only on an MI355X device (no CPU fallback)" % nn.device)
+    if (d2 is None) != (max_d2 is None):
+        raise RuntimeError("nnf_chunks: d2 and max_d2 go together, got d2 %s and max_d2 %s"
+                           % ("None" if d2 is None else "given", max_d2))
+    if d2 is not None:
+        if not isinstance(d2, torch.Tensor) or d2.dtype != torch.int32 or d2.shape != nn.shape or d2.device != nn.device:
+            raise RuntimeError("nnf_chunks: d2 must be int32 %s on %s like nn, got %s %s on %s"
+                               % (tuple(nn.shape), nn.device, getattr(d2, "dtype", type(d2)), tuple(getattr(d2, "shape", ())),
+                                  getattr(d2, "device", None)))
+        if int(max_d2) < 0 or int(max_d2) >= 2 ** 31:
+            raise RuntimeError("nnf_chunks: max_d2 must be in [0, 2^31), got %s" % (max_d2,))
+        d2 = _c(d2)
+    image = nn.dim() == 2
+    n = _c(nn[None] if image else nn)
+    qg = _triple(n.shape, "nn's grid", "nnf_chunks")
+    rg, qs, rs = _triple(ref_grid, "ref_grid", "nnf_chunks"), _triple(qstride, "qstride", "nnf_chunks"), \
+        _triple(rstride, "rstride", "nnf_chunks")
+    if min(rg) < 1 or rg[0] * rg[1] * rg[2] >= 2 ** 31:
+        raise RuntimeError("nnf_chunks: ref_grid %s must have entries >= 1 and fewer than 2^31 patches" % (tuple(rg),))
+    if min(qs) < 1 or min(rs) < 1:
+        raise RuntimeError("nnf_chunks: strides must be >= 1, got qstride %s rstride %s" % (tuple(qs), tuple(rs)))
+    labels = torch.empty_like(n)
+    sizes = torch.empty_like(n)
+    stats = torch.empty(6, dtype=torch.int64, device=n.device)
+    call("hpvg_nnf_chunks_i32", ptr(n), ptr(d2), int(max_d2) if d2 is not None else 0, qg, rg, qs, rs, ptr(labels), ptr(sizes),
+         ptr(stats), stream())
+    if image:
+        labels, sizes = labels[0], sizes[0]
+    return labels, sizes, stats
+
+
 def patch_vote_counts(out_shape, values_shape, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
     """(Nq, Nr, uncovered) of a patch_vote call: the patches of the output's grid, those of the values volume's grid, and the
     output voxels no patch of the output's grid covers, which take the fallback (hpvg_patch_vote_counts; host only)."""

@@ -308,6 +308,22 @@ int hpvg_patchnn_subset_u8(const unsigned char* q, int Tq, int Hq, int Wq, const
  * 0 for a patch that avoids the hole.  Geometry refusals as for hpvg_patchnn_u8; no workspace. */
 int hpvg_patch_mask_count_u8(const unsigned char* mask, int T, int H, int W, const int* patch, const int* stride, int* count,
                              void* stream);
+/* The copied regions ("chunks") of a nearest-neighbour field (evaluate --chunks).  nn: int32 [Nq] on the device over the query
+ * patch grid qgrid = (gT, gH, gW), raster order (t, y, x), holding indices into the key patch grid rgrid = (kT, kH, kW),
+ * Nr = kT kH kW; d2: int32 [Nq] or NULL.  qgrid / rgrid / qstride / rstride: host arrays of 3 ints.  Patch i at grid coordinate
+ * a with nn[i] at key coordinate b has the displacement b * rstride - a * qstride (per axis, in voxels).  It is KEPT iff
+ * 0 <= nn[i] < Nr and (d2 == NULL or 0 <= d2[i] <= max_d2), so the -1 entries of hpvg_patchnn_subset_u8 never are.  Two grid
+ * patches that differ by +1 along exactly one axis are a pair (no pair joins the end of a row or plane to the start of the
+ * next); a pair is coherent iff both are kept and their displacements are equal; the chunks are the connected components of
+ * the kept patches under coherent pairs.  labels: int32 [Nq], the smallest flat index of the patch's chunk, -1 where not kept.
+ * sizes: int32 [Nq], the chunk's size where labels[i] == i, 0 elsewhere.  stats: int64 [6] = kept, in_place (kept with
+ * displacement 0), coherent_pairs, chunks, largest size, sum of size^2.  Integer work throughout: exact, a function of the
+ * inputs alone, independent of launch geometry and timing.  nn is only decoded arithmetically - nothing is read through it.
+ * sizes and stats are cleared by the call itself; no workspace (labels holds the union-find forest meanwhile), no host
+ * synchronisation.  HPVG_ERR_ARG, before any device work: a null nn / labels / sizes / stats or geometry array, a grid entry
+ * < 1, a stride < 1, Nq or Nr >= 2^31, max_d2 < 0 with a non-null d2. */
+int hpvg_nnf_chunks_i32(const int* nn, const int* d2 /*nullable*/, int max_d2, const int* qgrid, const int* rgrid,
+                        const int* qstride, const int* rstride, int* labels, int* sizes, long long* stats, void* stream);
 
 /* ---- evaluation: exact sliced Wasserstein distance between the patch distributions of two uint8 volumes (the SWD of PGGAN /
  * GPNN / GPDM with integer directions).  Patches, patch and stride as above.  dirs: int8 [P][D] on the device, entries in

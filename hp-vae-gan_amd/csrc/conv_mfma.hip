@@ -23,6 +23,7 @@
 // (tap, m-tile); all workgroups read the same 442 KB so it stays L2 resident.
 // Accumulation is exact fp32 (v_mfma_f32_32x32x2_f32 == chain of fmaf).
 #include "hpvg_common.h"
+#include "hpvg_host.h"
 #include "hpvg.h"
 #include <stdlib.h>
 
@@ -858,88 +859,6 @@ __global__ __launch_bounds__(256, 2) void conv_narrow2_kernel(const ConvFwdArgs 
   }
 }
 
-// tile plan of conv_narrow2_kernel; returns false when the shape does not fit (then conv_narrow_kernel runs)
-bool plan_narrow2(int B, int Cin, int Cout, int T, int H, int W, int KT, Narrow2Geom* out, long* ntiles) {
-  if ((Cin & 1) || W < 4) return false;
-  const int NT = hpvg_cdiv(9 * Cout, 32);
-  const int JB = NT == 1 ? 4 : 2;
-  const int GP = 32 * JB;
-  double best = 1e300;
-  bool found = false;
-  // bands of a window width RS: band 0 = window [0, RS), outputs columns 0 .. RS-2 (all W of them when RS == W); a middle
-  // band outputs RS-2 columns from the window that starts one column before its first output; a band whose remaining
-  // columns number <= RS-1 is the last: its window is pulled back to end at W (the right image border needs no neighbour)
-  auto bands = [&](int RS, Narrow2Geom* q) -> int {
-    int nb = 0, o = 0;
-    while (o < W) {
-      if (nb == 16) return 0;
-      int n, ws;
-      if (nb == 0) { n = (RS == W) ? W : RS - 1; ws = 0; }
-      else if (W - o <= RS - 1) { n = W - o; ws = W - RS; }
-      else { n = RS - 2; ws = o - 1; }
-      if (n < 1) return 0;
-      if (q) { q->ws[nb] = ws; q->ob[nb] = o; q->on[nb] = n; }
-      o += n;
-      ++nb;
-    }
-    return nb;
-  };
-  for (int RS = 4; RS <= 256 && RS <= W; RS += 4) {
-    const int nb = bands(RS, nullptr);
-    if (nb == 0) continue;
-    for (int Th = 1; Th <= H; ++Th) {
-      const int nth = hpvg_cdiv(H, Th);
-      if (Th != hpvg_cdiv(H, nth)) continue;
-      const int npos = (Th + 2) * RS;
-      const int G = hpvg_cdiv(npos, GP);
-      if (G > 16) break;
-      const int pitch = (G * GP) | 1;
-      if ((size_t)(9 * Cout) * pitch * sizeof(float) > 76 * 1024) break;
-      const long nt = (long)B * T * nth * nb;
-      const double rounds = hpvg_cdiv(G, 4);
-      const double waves = nt <= 2L * HPVG_NUM_CU ? 1.0 : (double)nt / (2.0 * HPVG_NUM_CU);
-      const double cost = waves * (rounds * GP + 30.0);     // MFMA work of the slowest wave + a fixed per-tile cost (epilogue, barrier)
-      if (cost < best) {
-        best = cost;
-        found = true;
-        Narrow2Geom q{};
-        q.RS = RS; q.Th = Th; q.nth = nth; q.nb = nb; q.npos = npos; q.G = G; q.pitch = pitch;
-        bands(RS, &q);
-        *out = q;
-        *ntiles = nt;
-      }
-    }
-  }
-  if (!found) return false;
-  // every output column needs its in-image neighbours inside the band's window
-  for (int k = 0; k < out->nb; ++k) {
-    const int lo = out->ob[k] - 1 < 0 ? 0 : out->ob[k] - 1;
-    const int hi = out->ob[k] + out->on[k] > W - 1 ? W - 1 : out->ob[k] + out->on[k];
-    if (out->on[k] < 0 || lo < out->ws[k] || hi >= out->ws[k] + out->RS) return false;
-  }
-  return true;
-}
-
-template <int KT>
-int launch_conv_narrow2(const ConvFwdArgs& a, const Narrow2Geom& g, long ntiles, hipStream_t s) {
-  const int ksteps = hpvg_cdiv(a.Cin * KT, 2);
-  const size_t lds = (size_t)(9 * a.Cout) * g.pitch * sizeof(float);
-#define HPVG_NARROW2(NT, JB)                                                                                         \
-  {                                                                                                                  \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_narrow2_kernel<KT, NT, JB>),                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                 \
-        (void)hipGetLastError();                                                                                     \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
-    hipLaunchKernelGGL((conv_narrow2_kernel<KT, NT, JB>), dim3((unsigned)ntiles), dim3(256), lds, s, a, g, ksteps);  \
-  }
-  if (9 * a.Cout <= 32) HPVG_NARROW2(1, 4) else HPVG_NARROW2(2, 2)
-#undef HPVG_NARROW2
-  return hpvg_launch_status();
-}
-
 // B fragments of the narrow kernel; transpose_flip as in conv_pack_kernel
 __global__ void conv_pack_narrow_kernel(const float* __restrict__ w, const float* __restrict__ inv_scale, float* __restrict__ wn,
                                         int Cin_k, int Cout_k, int KT, int NT, int ksteps, int transpose_flip, long total) {
@@ -1044,7 +963,65 @@ __global__ void conv_pack_batch_kernel(const PackBatchArgs a, int C, int taps, i
   a.wp[it][idx] = val;
 }
 
+// ================================================================================================================ host part
+// Knobs, planners, plan memo, scratch, the decision, launches, entry points - the layout of conv_wgrad.hip.
+struct CShape { int B, Cin, Cout, T, H, W, KT; };   // kernel view of one launch (2-D: T = 1, KT = 1)
+// HPVG_ERR_ARG for a dimension below 1, HPVG_ERR_UNSUPPORTED for a kernel depth other than 1 or 3
+inline int conv_check(const CShape& c) {
+  if (c.B < 1 || c.Cin < 1 || c.Cout < 1 || c.T < 1 || c.H < 1 || c.W < 1) return HPVG_ERR_ARG;
+  return c.KT == 1 || c.KT == 3 ? HPVG_OK : HPVG_ERR_UNSUPPORTED;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ knobs
+// Every knob of the forward host path, read from the environment once, on first use.  The fields below the line are what
+// is in force: hpvg_conv_wino_config rewrites them at run time (tests and A/B tools).
+struct CKnobs {
+  bool sk_off;         // HPVG_CONV_SK=0: the one-workgroup-per-tile schedule even with a workspace
+  bool narrow2_off;    // HPVG_NARROW2=0: the first-generation narrow kernel for every tail
+  // HPVG_WINO2R=0 keeps the first-generation two-axis kernel (every wave all 16 points of one block: conv_wino2d_kernel);
+  // default: the points split over the waves by row (conv_wino2r_kernel: half the input-transform instructions and U loads
+  // per MFMA)
+  bool w2r;
+  bool w2d_off;        // HPVG_WINO2D=0: no two-axis section in the packs, no two-axis kernel in the dispatch
+  int stagger;         // HPVG_WINO_STAGGER: ConvFwdArgs::stagger of a one-axis launch with two workgroups per CU
+  int only_nb, only_mb, only_ntw;   // development: HPVG_PLAN_NB / _MB / _NTW restrict the wide searches to one value
+  // HPVG_WINO as the process started: 0 = no Winograd path at all (the weight packs carry no U fragments either, and
+  // hpvg_conv_wino_config refuses), 2 = every eligible launch, 1 / unset = eligible launches of at least min_pos positions
+  int env_wino;
+  // ---- in force
+  int wino;            // 0 = direct kernel only, 2 = every eligible launch, else by size
+  long min_pos;        // HPVG_WINO_MIN: the one-axis threshold in output positions B*T*H*W (< 0: conv_use_wino's defaults)
+  int stg;             // HPVG_WINO_STG, conv_wino_kernel's staging form: 0 = by size, 1 = halo'd bands only, 2 = rows as in memory wherever it fits
+  int w2d;             // the two-axis kernel: 0 = by size, 1 = never, 2 = wherever it can run
+  int gen;             // bumped when stg changes: what plan_wino_search may pick has changed, the plan memo drops its entries
+};
+CKnobs& cknobs() {
+  static CKnobs knobs = [] {
+    auto num = [](const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; };
+    CKnobs k{};
+    k.sk_off = num("HPVG_CONV_SK", 1) == 0;
+    k.narrow2_off = num("HPVG_NARROW2", 1) == 0;
+    k.w2r = num("HPVG_WINO2R", 1) != 0;
+    k.w2d_off = num("HPVG_WINO2D", 1) == 0;
+    k.stagger = (int)num("HPVG_WINO_STAGGER", 0);
+    k.only_nb = (int)num("HPVG_PLAN_NB", 0);
+    k.only_mb = (int)num("HPVG_PLAN_MB", 0);
+    k.only_ntw = (int)num("HPVG_PLAN_NTW", 0);
+    k.wino = k.env_wino = (int)num("HPVG_WINO", 1);
+    k.min_pos = num("HPVG_WINO_MIN", -1);
+    const long stg = num("HPVG_WINO_STG", 0);
+    k.stg = stg == 1 || stg == 2 ? (int)stg : 0;
+    return k;
+  }();
+  return knobs;
+}
+
+// which layers have which kernels (and pack sections)
 inline int conv_cc(int Cin) { return Cin <= 4 ? 4 : 8; }
+inline bool conv_is_narrow(int Cin, int Cout) { return Cout <= 4 && Cin > 4; }
+inline bool conv_is_wino(const CKnobs& k, int Cin, int Cout) { return k.env_wino != 0 && Cin >= 8 && Cout > 32; }
+// the two-axis kernel (conv_wino2d.inl) has its own fragment section behind the one-axis one for the 3x3x3 layers
+inline bool conv_is_wino2d(const CKnobs& k, int Cin, int Cout, int KT) { return !k.w2d_off && KT == 3 && conv_is_wino(k, Cin, Cout); }
 
 // floats of the direct kernel's A-fragment pack (the Winograd fragments, when the layer has them, follow it)
 inline size_t direct_pack_floats(int Cin, int Cout, int KT) {
@@ -1054,7 +1031,15 @@ inline size_t direct_pack_floats(int Cin, int Cout, int KT) {
   const size_t per_tap = (size_t)mbtot * 64 * (CC / 2);
   return ((size_t)nchunk * KT * 9 + 2) * per_tap;  // +2 taps of zero tail padding (A prefetch runs one tap / one m-tile ahead)
 }
+// number of floats of the packed-weight buffer for a conv with Cin -> Cout (kernel view)
+size_t wpack_floats(int Cin, int Cout, int KT, bool with2d) {
+  const CKnobs& k = cknobs();
+  if (conv_is_narrow(Cin, Cout)) return (size_t)hpvg_cdiv(Cin * KT, 2) * hpvg_cdiv(9 * Cout, 32) * 64;  // wn[kstep][ntile][lane]
+  return direct_pack_floats(Cin, Cout, KT) + (conv_is_wino(k, Cin, Cout) ? wino_pack_floats(Cin, Cout, KT) : 0) +
+         (with2d && conv_is_wino2d(k, Cin, Cout, KT) ? wino2_pack_floats(Cin, Cout) : 0);
+}
 
+// ---------------------------------------------------------------------------------------------------------------- planners
 struct Plan {
   int Th, Tw, RS, PL, L, qstride, nrange, ntw, nblocks, NB, MB, gridy, nj;  // Th != 0 only for the narrow kernel's 2-D tiles
   size_t lds;  // bytes of the LDS tile buffer
@@ -1064,61 +1049,89 @@ struct Plan {
 constexpr long CONV_SLOTS = 2L * HPVG_NUM_CU;  // co-resident workgroups: two per CU (256 VGPRs each, LDS <= 80 KB)
 inline long conv_slots(int MB, int NB) { return (long)HPVG_CONV_WGS(MB, NB) * HPVG_NUM_CU; }
 
-// Tile planner.  streamk = true: the launch is S = min(items, 512) persistent workgroups that share the (tile, chunk)
-// items evenly (needs the partial-slab workspace).  streamk = false: one workgroup per tile, dealt out by the
-// hardware dispatcher (no workspace; grids of 1-5 tiles per slot are quantised - the reason stream-K exists).
-// Cost in us; constants chosen to minimise the REGRET of the plan picked over the measured landscapes of stages 3-9 at
-// B = 2 and 4 (tools/ab_conv_plan.sh: every band count x NB forced; mean regret 0.3 %, worst 1.6 %): an item costs its
-// MFMA rounds (6.5 us per 32-position x 32-channel x 8-channel-chunk round when two workgroups share the CU's matrix
-// pipe, half that when alone) + ~6 us of staging / barrier work the co-resident workgroup does not hide (2 when alone)
-// + the input planes it stages (2 us per 1000 positions); tiles cut across workgroups travel through HBM as raw accumulator slabs (16 KB per 32x32 block,
-// written by the main kernel, read back by the fix-up: ~5.5 us per block at the chip's share of bandwidth).
-Plan plan_conv_search(int B, int Cin, int Cout, int T, int H, int W, int KT, bool streamk, bool narrow) {
+// Cost in us of one wide launch of ntl tiles of nchunk items each, for both wide planners.  streamk = true: the launch is
+// S = min(items, slots) persistent workgroups that share the (tile, chunk) items evenly (needs the partial-slab workspace).
+// streamk = false: one workgroup per tile, dealt out by the hardware dispatcher (no workspace; grids of 1-5 tiles per slot
+// are quantised - the reason stream-K exists): whole tiles per CU, pairs run together, an odd one runs alone at the end.
+// Constants chosen to minimise the REGRET of the plan picked over the measured landscapes of stages 3-9 at B = 2 and 4
+// (tools/ab_conv_plan.sh: every band count x NB forced; mean regret 0.3 %, worst 1.6 %; tools/perf_conv.py, stages 5-9,
+// within 5 %): an item costs its MFMA rounds (mfma_paired when two workgroups share the CU's matrix pipe, mfma_alone
+// otherwise) + ~6 us of staging / barrier work the co-resident workgroup does not hide (2 when alone) + the input planes it
+// stages (stage_us); tiles cut across workgroups travel through HBM as raw accumulator slabs (16 KB per 32x32 block, `blocks`
+// of them, written by the main kernel, read back by the fix-up: ~5.5 us per block at the chip's share of bandwidth).
+// The planners break ties at 1e-9: keep the order of the operations (`blocks` is a power of two).
+inline double conv_cost(bool streamk, long ntl, int nchunk, long slots, double mfma_paired, double mfma_alone, double stage_us,
+                        int blocks) {
+  if (!streamk) {
+    const long per_cu = (ntl + HPVG_NUM_CU - 1) / HPVG_NUM_CU;
+    const double tile_paired = nchunk * (mfma_paired + 6.0 + stage_us) + 0.4 * blocks;
+    const double tile_alone = nchunk * (mfma_alone + 2.0 + stage_us) + 0.4 * blocks;
+    return (double)(per_cu / 2) * tile_paired + (double)(per_cu & 1) * tile_alone + 1e-4 * (double)ntl;
+  }
+  const long items_tot = ntl * nchunk;
+  const long S = items_tot < slots ? items_tot : slots;
+  const long ndp = ntl / S;
+  const long rem = (ntl - ndp * S) * nchunk;
+  const double items = (double)(ndp * nchunk) + (double)((rem + S - 1) / S);
+  const bool paired = S > HPVG_NUM_CU;
+  const double per_item = (paired ? mfma_paired : mfma_alone) + (paired ? 6.0 : 2.0) + stage_us;
+  const double tiles = (double)(ndp + (rem ? 1 : 0));
+  double parts = 0.0;
+  if (rem) {
+    parts = 1.0 + (double)rem / (double)S / (double)nchunk;
+    if (parts > 2.0) parts = 2.0;
+  }
+  return items * per_item + tiles * 0.4 * blocks + parts * 5.5 * blocks + 1e-4 * (double)ntl;
+}
+
+// 2-D tiles (Th x Tw) for conv_narrow_kernel: a GEMM over the tile + halo positions, one workgroup per tile: blocks of 32
+// positions over 4 waves, K steps of 64 cycles each, ~3 us of epilogue; the P image (9*Cout rows) must leave room for >= 4
+// workgroups per CU (they hide the load latency)
+Plan plan_narrow_search(const CShape& c) {
+  const auto [B, Cin, Cout, T, H, W, KT] = c;
+  Plan best{};
+  double best_cost = 1e300;
+  for (int Tw = 1; Tw <= W; ++Tw) {
+    const int ntw = hpvg_cdiv(W, Tw);
+    if (Tw != hpvg_cdiv(W, ntw)) continue;  // only balanced splits of W
+    const int RS = Tw + 2;
+    for (int Th = 1; Th <= H; ++Th) {
+      const int nth = hpvg_cdiv(H, Th);
+      if (Th != hpvg_cdiv(H, nth)) continue;
+      const int nblk_h = hpvg_cdiv((Th + 2) * RS, 32);
+      if ((Th + 2) * RS > NJMAX * 256) break;
+      if ((size_t)(9 * Cout) * ((size_t)nblk_h * 32 + 1) * sizeof(float) > 38 * 1024) continue;
+      const long ntl = (long)B * T * nth * ntw;
+      const double per_tile = hpvg_cdiv(nblk_h, 4) * (double)hpvg_cdiv(Cin * KT, 2) * hpvg_cdiv(9 * Cout, 32) * 0.033 + 3.0;
+      const double waves = ntl <= CONV_SLOTS ? 1.0 : (double)ntl / (double)CONV_SLOTS;
+      const double cost = waves * per_tile + 1e-3 * (double)ntl;
+      if (cost < best_cost - 1e-9) {
+        best_cost = cost;
+        best = Plan{Th, Tw, RS, (Th + 2) * RS, Th * RS, Th * RS, nth, ntw, hpvg_cdiv(Th * RS, 32), 4, 1, 1, hpvg_cdiv((Th + 2) * RS, 256), 0};
+      }
+    }
+  }
+  return best;
+}
+
+// conv_mfma_kernel: W is cut into ntw balanced bands of Tw columns; a band plane, flattened row by row with stride RS = Tw+2
+// (its two halo columns are the junk GEMM columns), is cut into nrange balanced ranges of L <= NB*128 positions.  Wide
+// bands waste few junk columns, and a range - unlike a whole number of rows - fills its 32-position blocks.  An MFMA round
+// (32 positions x 32 channels x 8-channel chunk) costs 6.5 us paired, 3.0 alone; staging 2 us per 1000 positions.
+Plan plan_conv_search(const CKnobs& k, const CShape& c, bool streamk) {
+  const auto [B, Cin, Cout, T, H, W, KT] = c;
   const int CC = conv_cc(Cin);
   const int nchunk = hpvg_cdiv(Cin, CC);
   const int mbtot = hpvg_cdiv(Cout, 32);
   Plan best{};
   double best_cost = 1e300;
-  // development knobs: restrict the search to one NB / MB
-  static const int only_nb = [] { const char* e = getenv("HPVG_PLAN_NB"); return e ? atoi(e) : 0; }();
-  static const int only_mb = [] { const char* e = getenv("HPVG_PLAN_MB"); return e ? atoi(e) : 0; }();
-  static const int only_ntw = [] { const char* e = getenv("HPVG_PLAN_NTW"); return e ? atoi(e) : 0; }();
-  if (narrow) {
-    // 2-D tiles (Th x Tw) for conv_narrow_kernel: a GEMM over the tile + halo positions, one workgroup per tile: blocks
-    // of 32 positions over 4 waves, K steps of 64 cycles each, ~3 us of epilogue; the P image (9*Cout rows) must leave
-    // room for >= 4 workgroups per CU (they hide the load latency)
-    for (int Tw = 1; Tw <= W; ++Tw) {
-      const int ntw = hpvg_cdiv(W, Tw);
-      if (Tw != hpvg_cdiv(W, ntw)) continue;  // only balanced splits of W
-      const int RS = Tw + 2;
-      for (int Th = 1; Th <= H; ++Th) {
-        const int nth = hpvg_cdiv(H, Th);
-        if (Th != hpvg_cdiv(H, nth)) continue;
-        const int nblk_h = hpvg_cdiv((Th + 2) * RS, 32);
-        if ((Th + 2) * RS > NJMAX * 256) break;
-        if ((size_t)(9 * Cout) * ((size_t)nblk_h * 32 + 1) * sizeof(float) > 38 * 1024) continue;
-        const long ntl = (long)B * T * nth * ntw;
-        const double per_tile = hpvg_cdiv(nblk_h, 4) * (double)hpvg_cdiv(Cin * KT, 2) * hpvg_cdiv(9 * Cout, 32) * 0.033 + 3.0;
-        const double waves = ntl <= CONV_SLOTS ? 1.0 : (double)ntl / (double)CONV_SLOTS;
-        const double cost = waves * per_tile + 1e-3 * (double)ntl;
-        if (cost < best_cost - 1e-9) {
-          best_cost = cost;
-          best = Plan{Th, Tw, RS, (Th + 2) * RS, Th * RS, Th * RS, nth, ntw, hpvg_cdiv(Th * RS, 32), 4, 1, 1, hpvg_cdiv((Th + 2) * RS, 256), 0};
-        }
-      }
-    }
-    return best;
-  }
-  // MFMA kernel: W is cut into ntw balanced bands of Tw columns; a band plane, flattened row by row with stride RS = Tw+2
-  // (its two halo columns are the junk GEMM columns), is cut into nrange balanced ranges of L <= NB*128 positions.  Wide
-  // bands waste few junk columns, and a range - unlike a whole number of rows - fills its 32-position blocks.
   for (int MB = (mbtot >= 2 ? 2 : 1); MB >= 1; --MB) {
-    if (only_mb && MB != only_mb && mbtot >= 2) continue;
+    if (k.only_mb && MB != k.only_mb && mbtot >= 2) continue;
     const int gridy = hpvg_cdiv(mbtot, MB);
     for (int ntw = 1; ntw <= W; ++ntw) {
       const int Tw = hpvg_cdiv(W, ntw);
       if (ntw > 1 && hpvg_cdiv(W, ntw - 1) == Tw) continue;  // same band width as the previous ntw: more bands, no gain
-      if (only_ntw && ntw != only_ntw) continue;
+      if (k.only_ntw && ntw != k.only_ntw) continue;
       const int RS = Tw + 2;
       const long flat = (long)(H - 1) * RS + Tw;  // flattened positions that hold outputs
       // candidate tiles of this band.  3x3x3: balanced ranges of at most NB*128 positions.  3x3 (a third of the MFMA work
@@ -1144,7 +1157,7 @@ Plan plan_conv_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
           qstride = L;
           if (L > NB * 128) L = NB * 128;             // the (at most two) positions cut off are halo columns
         }
-        if (only_nb && NB != only_nb) continue;
+        if (k.only_nb && NB != k.only_nb) continue;
         const int Lmax = NB * 128;
         const int plload = L + 2 * RS + 2;
         if (plload > NJMAX * 256) continue;
@@ -1152,37 +1165,8 @@ Plan plan_conv_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
         const size_t lds = (size_t)CC * KT * PL * sizeof(float);
         if (lds > (HPVG_CONV_WGS(MB, NB) == 4 ? 38 : 80) * 1024) continue;
         const long ntl = (long)B * T * nrange * ntw * gridy;
-        const double stage_us = 0.002 * plload;
-        double cost;
-        if (streamk) {
-          // S co-resident workgroups share the (tile, chunk) items evenly.  Cost in us, constants fitted to measured
-          // launches (tools/perf_conv.py, stages 5-9, within 5 %): an item costs its MFMA rounds (6.5 us per 32-position
-          // x 32-channel x 8-channel-chunk round when two workgroups share the CU's matrix pipe, half that when alone)
-          // + ~6 us of staging / barrier work the co-resident workgroup does not hide + the input planes it stages;
-          // tiles cut across workgroups travel through HBM as raw accumulator slabs (16 KB per 32x32 block, written by
-          // the main kernel, read back by the fix-up: ~5.5 us per block at the chip's share of bandwidth)
-          const long items_tot = ntl * nchunk;
-          const long slots = conv_slots(MB, NB);
-          const long S = items_tot < slots ? items_tot : slots;
-          const long ndp = ntl / S;
-          const long rem = (ntl - ndp * S) * nchunk;
-          const double items = (double)(ndp * nchunk) + (double)((rem + S - 1) / S);
-          const bool paired = S > HPVG_NUM_CU;
-          const double per_item = (double)NB * MB * (paired ? 6.5 : 3.0) + (paired ? 6.0 : 2.0) + stage_us;
-          const double tiles = (double)(ndp + (rem ? 1 : 0));
-          double parts = 0.0;
-          if (rem) {
-            parts = 1.0 + (double)rem / (double)S / (double)nchunk;
-            if (parts > 2.0) parts = 2.0;
-          }
-          cost = items * per_item + tiles * 0.4 * NB * MB + parts * 5.5 * NB * MB + 1e-4 * (double)ntl;
-        } else {
-          // one workgroup per tile: whole tiles per CU, pairs run together, an odd one runs alone at the end
-          const long per_cu = (ntl + HPVG_NUM_CU - 1) / HPVG_NUM_CU;
-          const double tile_paired = nchunk * ((double)NB * MB * 6.5 + 6.0 + stage_us) + 0.4 * NB * MB;
-          const double tile_alone = nchunk * ((double)NB * MB * 3.0 + 2.0 + stage_us) + 0.4 * NB * MB;
-          cost = (double)(per_cu / 2) * tile_paired + (double)(per_cu & 1) * tile_alone + 1e-4 * (double)ntl;
-        }
+        const double cost = conv_cost(streamk, ntl, nchunk, conv_slots(MB, NB), (double)NB * MB * 6.5, (double)NB * MB * 3.0,
+                                      0.002 * plload, NB * MB);
         if (cost < best_cost - 1e-9) {
           best_cost = cost;
           best = Plan{0, Tw, RS, PL, L, qstride, nrange, ntw, hpvg_cdiv(L, 32), NB, MB, gridy, hpvg_cdiv(plload, 256), lds};
@@ -1196,15 +1180,15 @@ Plan plan_conv_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
 // Tile plan of conv_wino_kernel: bands of an EVEN width Tw (row stride RS = Tw + 2 even: an output pair never straddles a
 // row), a band plane cut into balanced ranges of an even L <= NBP*128 positions (NBP*64 pairs).  Same cost form as above
 // with the Winograd item: 36 instead of 27 MFMA k-steps per channel pair on half the positions per accumulator set.
-Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, bool streamk) {
+Plan plan_wino_search(const CKnobs& k, const CShape& c, bool streamk) {
+  const auto [B, Cin, Cout, T, H, W, KT] = c;
   const int nchunk = hpvg_cdiv(Cin, WINO_CC);
   const int mbtot = hpvg_cdiv(Cout, 32);
   const int gridy = hpvg_cdiv(mbtot, 2);
-  static const int only_ntw = [] { const char* e = getenv("HPVG_PLAN_NTW"); return e ? atoi(e) : 0; }();
   Plan best{};
   double best_cost = 1e300;
   const int Lmax = WINO_NBP * 128;
-  if (g_wino_stg != 1 && (W & 1) == 0 && W >= 2) {
+  if (k.stg != 1 && (W & 1) == 0 && W >= 2) {
     // staging form 2: one band of the full width, row stride W, no halo columns, a quarter of the staging instructions.
     // Measured (profiles/r02_perf_wino_stg2.txt): -4.2 % at stage 9, -3.7 % at stage 8, +-1-2 % at stages 5-7, where a
     // workgroup sees fewer than two whole tiles: taken from two tiles per co-resident workgroup up (or when forced).
@@ -1222,7 +1206,7 @@ Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
     const size_t lds = (size_t)WINO_CC * KT * PL * sizeof(float);
     const int ngmax = (L + 2 * W + 2 + 3 + 3) >> 2;           // 16-byte groups of the staged span: one per lane
     const long ntl = (long)B * T * nrange * gridy;
-    if (lds <= 80 * 1024 && ngmax <= 256 && (g_wino_stg == 2 || ntl >= 2 * CONV_SLOTS))
+    if (lds <= 80 * 1024 && ngmax <= 256 && (k.stg == 2 || ntl >= 2 * CONV_SLOTS))
       return Plan{0, W, W, PL, L, L, nrange, 1, hpvg_cdiv(L, 32), WINO_NBP, 2, gridy, 1, lds, 2};
   }
   int prev_tw = 0;
@@ -1231,7 +1215,7 @@ Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
     Tw += Tw & 1;
     if (Tw == prev_tw || (long)(ntw - 1) * Tw >= W) continue;  // same band width as before / an empty last band
     prev_tw = Tw;
-    if (only_ntw && ntw != only_ntw) continue;
+    if (k.only_ntw && ntw != k.only_ntw) continue;
     const int RS = Tw + 2;
     const long flat = (long)(H - 1) * RS + Tw;
     const int nrange = hpvg_cdiv(flat, Lmax);
@@ -1245,31 +1229,8 @@ Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
     const long ntl = (long)B * T * nrange * ntw * gridy;
     // (staging weighs half of what it does for the direct kernel: measured landscape, profiles/r02_ab_wino_plan.txt - wide
     // bands with few junk columns win at stages 7-9 although they stage three rows per row of outputs)
-    const double stage_us = 0.001 * plload;
     const double mfma_paired = 6.5 * (2.0 * WINO_NBP) * (2.0 / 3.0);  // 64 ch x NBP*64 pairs = 2*NBP direct 32x32 block pairs, at 36/54 of their k-steps
-    double cost;
-    if (streamk) {
-      const long items_tot = ntl * nchunk;
-      const long slots = CONV_SLOTS;
-      const long S = items_tot < slots ? items_tot : slots;
-      const long ndp = ntl / S;
-      const long rem = (ntl - ndp * S) * nchunk;
-      const double items = (double)(ndp * nchunk) + (double)((rem + S - 1) / S);
-      const bool paired = S > HPVG_NUM_CU;
-      const double per_item = (paired ? mfma_paired : mfma_paired * 3.0 / 6.5) + (paired ? 6.0 : 2.0) + stage_us;
-      const double tiles = (double)(ndp + (rem ? 1 : 0));
-      double parts = 0.0;
-      if (rem) {
-        parts = 1.0 + (double)rem / (double)S / (double)nchunk;
-        if (parts > 2.0) parts = 2.0;
-      }
-      cost = items * per_item + tiles * 0.4 * 4 + parts * 5.5 * 4 + 1e-4 * (double)ntl;
-    } else {
-      const long per_cu = (ntl + HPVG_NUM_CU - 1) / HPVG_NUM_CU;
-      const double tile_paired = nchunk * (mfma_paired + 6.0 + stage_us) + 1.6;
-      const double tile_alone = nchunk * (mfma_paired * 3.0 / 6.5 + 2.0 + stage_us) + 1.6;
-      cost = (double)(per_cu / 2) * tile_paired + (double)(per_cu & 1) * tile_alone + 1e-4 * (double)ntl;
-    }
+    const double cost = conv_cost(streamk, ntl, nchunk, CONV_SLOTS, mfma_paired, mfma_paired * 3.0 / 6.5, 0.001 * plload, 2 * WINO_NBP);
     if (cost < best_cost - 1e-9) {
       best_cost = cost;
       best = Plan{0, Tw, RS, PL, L, L, nrange, ntw, hpvg_cdiv(L, 32), WINO_NBP, 2, gridy, hpvg_cdiv(plload, 256), lds};
@@ -1278,36 +1239,13 @@ Plan plan_wino_search(int B, int Cin, int Cout, int T, int H, int W, int KT, boo
   return best;
 }
 
-// Which kernel a wide conv runs on (see wino_env_mode in conv_wino.inl).  Default threshold, measured per pyramid stage at
-// B = 2 (tools/perf_wino.py, profiles/r02_perf_wino.txt): the 3x3x3 convs gain at every stage (x1.14-1.18 at stages 0-1,
-// parity at 2, x1.08-1.32 from 3 up); the 3x3 convs are launch / fix-up bound below ~25 K output positions (x0.75-1.0) and
-// gain from there (x1.07-1.25 at stages 7-9).
-inline bool conv_use_wino(int B, int Cin, int Cout, int T, int H, int W, int KT, bool prologue) {
-  if (prologue || !conv_is_wino(Cin, Cout)) return false;
-  if (g_wino_mode < 0) {
-    g_wino_mode = wino_env_mode();
-    const char* e = getenv("HPVG_WINO_MIN");
-    if (e) g_wino_min_pos = atol(e);
-    const char* f = getenv("HPVG_WINO_STG");   // staging form: 1 = halo'd bands only, 2 = rows-as-in-memory wherever it fits
-    if (f) g_wino_stg = atoi(f) == 1 ? 1 : (atoi(f) == 2 ? 2 : 0);
-  }
-  if (g_wino_mode == 0) return false;
-  if (g_wino_mode == 2) return true;
-  const long min_pos = g_wino_min_pos >= 0 ? g_wino_min_pos : (KT == 3 ? 0L : 24000L);
-  return (long)B * T * H * W >= min_pos;
-}
-
-// The two-axis Winograd kernel (conv_wino2d.inl): where it can run and where it is taken.  g_wino2d: 0 = by size, 1 = never,
-// 2 = wherever it can run (hpvg_conv_wino_config modes 5 / 6 set 2 / 1).
-// HPVG_WINO2R=0 keeps the first-generation kernel (every wave all 16 points of one block: conv_wino2d_kernel); default: the
-// points split over the waves by row (conv_wino2r_kernel: half the input-transform instructions and U loads per MFMA)
-static const bool g_wino2r = [] { const char* e = getenv("HPVG_WINO2R"); return !e || atoi(e) != 0; }();
-int g_wino2d = 0;
+// Geometry of the two-axis Winograd kernels (conv_wino2d.inl, conv_wino2r.inl); ok = false where they cannot run
 struct W2Geom { int Cq, R, ntq, tqw, gridy, nsc, ntl; bool ok; };
-inline W2Geom wino2d_geom(int B, int Cin, int Cout, int T, int H, int W, int KT) {
+W2Geom wino2d_geom(const CKnobs& k, const CShape& c) {
+  const auto [B, Cin, Cout, T, H, W, KT] = c;
   W2Geom q{};
-  if (!conv_is_wino2d(Cin, Cout, KT) || ((W & 1) && !g_wino2r) || W < 2 || (long)H * W < 4) return q;   // (odd W: conv_wino2r_kernel's ODD instance)
-  if (g_wino2r && (long)H * W + 4 > HPVG_ZERO_PLANE_FLOATS) return q;                                     // (its zero plane)
+  if (!conv_is_wino2d(k, Cin, Cout, KT) || ((W & 1) && !k.w2r) || W < 2 || (long)H * W < 4) return q;   // (odd W: conv_wino2r_kernel's ODD instance)
+  if (k.w2r && (long)H * W + 4 > HPVG_ZERO_PLANE_FLOATS) return q;                                       // (its zero plane)
   q.Cq = (W + 1) / 2;
   q.R = hpvg_cdiv(H, 2);
   const int nq = q.R * q.Cq;
@@ -1333,7 +1271,125 @@ inline W2Geom wino2d_geom(int B, int Cin, int Cout, int T, int H, int W, int KT)
   q.ok = true;
   return q;
 }
-// Taken by size where it was measured to win.  Whole tiles, one workgroup per CU, no stream-K: a launch takes ceil(tiles / 256)
+
+// tile plan of conv_narrow2_kernel; returns false when the shape does not fit (then conv_narrow_kernel runs)
+bool plan_narrow2(int B, int Cin, int Cout, int T, int H, int W, int KT, Narrow2Geom* out, long* ntiles) {
+  if ((Cin & 1) || W < 4) return false;
+  const int NT = hpvg_cdiv(9 * Cout, 32);
+  const int JB = NT == 1 ? 4 : 2;
+  const int GP = 32 * JB;
+  double best = 1e300;
+  bool found = false;
+  // bands of a window width RS: band 0 = window [0, RS), outputs columns 0 .. RS-2 (all W of them when RS == W); a middle
+  // band outputs RS-2 columns from the window that starts one column before its first output; a band whose remaining
+  // columns number <= RS-1 is the last: its window is pulled back to end at W (the right image border needs no neighbour)
+  auto bands = [&](int RS, Narrow2Geom* q) -> int {
+    int nb = 0, o = 0;
+    while (o < W) {
+      if (nb == 16) return 0;
+      int n, ws;
+      if (nb == 0) { n = (RS == W) ? W : RS - 1; ws = 0; }
+      else if (W - o <= RS - 1) { n = W - o; ws = W - RS; }
+      else { n = RS - 2; ws = o - 1; }
+      if (n < 1) return 0;
+      if (q) { q->ws[nb] = ws; q->ob[nb] = o; q->on[nb] = n; }
+      o += n;
+      ++nb;
+    }
+    return nb;
+  };
+  for (int RS = 4; RS <= 256 && RS <= W; RS += 4) {
+    const int nb = bands(RS, nullptr);
+    if (nb == 0) continue;
+    for (int Th = 1; Th <= H; ++Th) {
+      const int nth = hpvg_cdiv(H, Th);
+      if (Th != hpvg_cdiv(H, nth)) continue;
+      const int npos = (Th + 2) * RS;
+      const int G = hpvg_cdiv(npos, GP);
+      if (G > 16) break;
+      const int pitch = (G * GP) | 1;
+      if ((size_t)(9 * Cout) * pitch * sizeof(float) > 76 * 1024) break;
+      const long nt = (long)B * T * nth * nb;
+      const double rounds = hpvg_cdiv(G, 4);
+      const double waves = nt <= 2L * HPVG_NUM_CU ? 1.0 : (double)nt / (2.0 * HPVG_NUM_CU);
+      const double cost = waves * (rounds * GP + 30.0);     // MFMA work of the slowest wave + a fixed per-tile cost (epilogue, barrier)
+      if (cost < best) {
+        best = cost;
+        found = true;
+        Narrow2Geom q{};
+        q.RS = RS; q.Th = Th; q.nth = nth; q.nb = nb; q.npos = npos; q.G = G; q.pitch = pitch;
+        bands(RS, &q);
+        *out = q;
+        *ntiles = nt;
+      }
+    }
+  }
+  if (!found) return false;
+  // every output column needs its in-image neighbours inside the band's window
+  for (int k = 0; k < out->nb; ++k) {
+    const int lo = out->ob[k] - 1 < 0 ? 0 : out->ob[k] - 1;
+    const int hi = out->ob[k] + out->on[k] > W - 1 ? W - 1 : out->ob[k] + out->on[k];
+    if (out->on[k] < 0 || lo < out->ws[k] || hi >= out->ws[k] + out->RS) return false;
+  }
+  return true;
+}
+
+// --------------------------------------------------------------------------------------------------------------- plan memo
+// (memo_lookup: hpvg_host.h)  Every plan of one launch shape, filled at its first launch or query: a search costs 10-100 us of
+// host time and shapes repeat every iteration.  direct / wino: [0] one workgroup per tile, [1] stream-K.  A narrow shape has
+// its first-generation tiles in both direct slots and the second generation's geometry in n2; a wide one the rest, the
+// Winograd entries only where the layer has the kernels (L == 0: no tile fits, w2.ok / n2_ok false: cannot run).
+// hpvg_conv_wino_config's staging forms move plan_wino_search, and bump CKnobs::gen with them.
+struct CPlans {
+  Plan direct[2], wino[2];
+  W2Geom w2;
+  Narrow2Geom n2;
+  long n2_tiles;
+  bool n2_ok;
+};
+const CPlans& conv_plans(const CKnobs& k, const CShape& c) {
+  return memo_lookup<CPlans>(k.gen, c.B, c.Cin, c.Cout, c.T, c.H, c.W, c.KT, [&] {
+    CPlans pl{};
+    if (conv_is_narrow(c.Cin, c.Cout)) {
+      pl.direct[0] = pl.direct[1] = plan_narrow_search(c);
+      pl.n2_ok = plan_narrow2(c.B, c.Cin, c.Cout, c.T, c.H, c.W, c.KT, &pl.n2, &pl.n2_tiles);
+      return pl;
+    }
+    for (int sk = 0; sk < 2; ++sk) {
+      pl.direct[sk] = plan_conv_search(k, c, sk != 0);
+      if (conv_is_wino(k, c.Cin, c.Cout)) pl.wino[sk] = plan_wino_search(k, c, sk != 0);
+    }
+    pl.w2 = wino2d_geom(k, c);
+    return pl;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------ scratch, per kernel family
+inline int conv_ntiles(const CShape& c, const Plan& p) { return c.B * c.T * p.nrange * p.ntw * p.gridy; }
+// stream-K grid for a plan: all co-resident slots, or one workgroup per item when there are fewer items than slots
+inline int conv_sk_grid(const CShape& c, const Plan& p) {
+  const long items = (long)conv_ntiles(c, p) * hpvg_cdiv(c.Cin, conv_cc(c.Cin));
+  const long slots = conv_slots(p.MB, p.NB);
+  return (int)(items < slots ? items : slots);
+}
+// the stream-K schedule's partial slabs of the direct and the one-axis Winograd kernel (the other two kernels need none)
+inline size_t conv_sk_ws_bytes(const CShape& c, const Plan& p) {
+  return p.L ? (size_t)conv_sk_grid(c, p) * 2 * p.MB * p.NB * 16 * 256 * sizeof(float) : 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the decision
+// Where the one-axis Winograd kernel is taken.  Default threshold, measured per pyramid stage at B = 2 (tools/perf_wino.py,
+// profiles/r02_perf_wino.txt): the 3x3x3 convs gain at every stage (x1.14-1.18 at stages 0-1, parity at 2, x1.08-1.32 from 3
+// up); the 3x3 convs are launch / fix-up bound below ~25 K output positions (x0.75-1.0) and gain from there (x1.07-1.25 at
+// stages 7-9).
+inline bool conv_use_wino(const CKnobs& k, const CShape& c, bool prologue) {
+  if (prologue || !conv_is_wino(k, c.Cin, c.Cout) || k.wino == 0) return false;
+  if (k.wino == 2) return true;
+  const long min_pos = k.min_pos >= 0 ? k.min_pos : (c.KT == 3 ? 0L : 24000L);
+  return (long)c.B * c.T * c.H * c.W >= min_pos;
+}
+// Where the two-axis kernel is taken, of the launches conv_use_wino lets through: by size where it was measured to win.
+// Whole tiles, one workgroup per CU, no stream-K: a launch takes ceil(tiles / 256)
 // rounds of ~72 us (64 -> 64), the one-axis kernel + fix-up ~100-120 us per 256 tiles' worth of work (more below one round).
 // Round 3, conv_wino2r_kernel against the one-axis kernel (tools/perf_wino2.py, profiles/r03_perf_wino2r_sizes.txt; rounds =
 // tiles / 256): 0.35 x0.94, 0.59 x1.12, 0.70 x1.48, 0.94 x1.43, 1.17 x0.94, 1.88 x1.36, 1.97 x1.07 (odd W), 3.23 x1.18-1.21,
@@ -1341,139 +1397,146 @@ inline W2Geom wino2d_geom(int B, int Cin, int Cout, int T, int H, int W, int KT)
 // instance - H * W % 4 != 0 - lost below two rounds; round 2's conv_wino2d_kernel wanted three rounds filled to 88 %.)
 // Rule: a single round from half a chip of tiles (the one-axis kernel pays its fix-up launch and stream-K seams there), else
 // the rounds at least 60 % full on average.
-inline bool conv_use_wino2d(const W2Geom& q, bool prologue) {
-  if (!q.ok || prologue || g_wino2d == 1 || g_wino_mode == 0) return false;
-  if (g_wino2d == 2) return true;
+inline bool conv_use_wino2d(const CKnobs& k, const W2Geom& q) {
+  if (!q.ok || k.w2d == 1) return false;
+  if (k.w2d == 2) return true;
   const long rounds = (q.ntl + HPVG_NUM_CU - 1) / HPVG_NUM_CU;
   if (rounds == 1) return q.ntl * 2 >= HPVG_NUM_CU;
   return (long)q.ntl * 10 >= 6L * rounds * HPVG_NUM_CU;
 }
-template <typename K>
-int launch_wino2d_kern(K kern, bool& attr_set, const Wino2Args& a, hipStream_t s) {
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      (void)hipGetLastError();
-    attr_set = true;
+
+// Which kernel family runs a launch, on which plan, grid and scratch.  The launcher, its "workspace too small" step and the
+// host queries all read this one answer.  The chain: narrow (second generation, then first), two-axis Winograd, one-axis
+// Winograd (back to direct where no tile fits), direct; stream-K where a large enough workspace is given.
+struct CDecision {
+  int kind;           // hpvg_conv_fwd_kernel_kind's numbering: 0 conv_mfma_kernel, 1 conv_wino_kernel, 2 the two-axis
+                      // kernels (plans->w2), 3 the narrow kernels
+  int narrow_gen;     // kind 3: 2 = conv_narrow2_kernel (plans->n2), 1 = conv_narrow_kernel (on plan's tiles)
+  const CPlans* plans;
+  const Plan* plan;   // kinds 0, 1, 3; L == 0: no tile fits the shape
+  bool streamk;
+  int ntl, S;         // tiles, workgroups
+  size_t ws_bytes;    // the scratch that launch needs
+};
+CDecision conv_decide(const CShape& c, bool prologue, bool fp32_out_mask, const void* ws, size_t ws_bytes) {
+  const CKnobs& k = cknobs();
+  CDecision d{};
+  const CPlans& pl = conv_plans(k, c);
+  d.plans = &pl;
+  if (conv_is_narrow(c.Cin, c.Cout)) {
+    d.kind = 3;
+    d.plan = &pl.direct[0];
+    d.narrow_gen = !k.narrow2_off && !prologue && !fp32_out_mask && pl.n2_ok ? 2 : 1;
+    d.ntl = d.S = conv_ntiles(c, *d.plan);
+    return d;
   }
-  const int S = a.ntl < HPVG_NUM_CU ? a.ntl : HPVG_NUM_CU;
-  hipLaunchKernelGGL(kern, dim3(S), dim3(256), (size_t)3 * 12 * W2_PL * sizeof(float), s, a);   // three input buffers
-  return hpvg_launch_status();
-}
-template <int VAR, bool TAIL>
-int launch_wino2d_inst(const Wino2Args& a, hipStream_t s) {
-  static bool attr_r = false, attr_o = false, attr_d = false;
-  if (a.W & 1) return launch_wino2d_kern(conv_wino2r_kernel<VAR, TAIL, true>, attr_o, a, s);    // (only the row-split kernel has an odd-W instance)
-  if (g_wino2r) return launch_wino2d_kern(conv_wino2r_kernel<VAR, TAIL, false>, attr_r, a, s);
-  return launch_wino2d_kern(conv_wino2d_kernel<VAR, TAIL>, attr_d, a, s);
-}
-
-template <int VAR>
-int launch_wino2d_var(const Wino2Args& a, hipStream_t s) {
-  return (((long)a.H * a.W) & 3) ? launch_wino2d_inst<VAR, true>(a, s) : launch_wino2d_inst<VAR, false>(a, s);
-}
-
-// The search costs ~10-20 us of host time; shapes repeat every iteration, so plans are memoised (host-side, tiny).
-inline bool conv_is_narrow(int Cin, int Cout) { return Cout <= 4 && Cin > 4; }
-
-Plan plan_conv(int B, int Cin, int Cout, int T, int H, int W, int KT, bool streamk, bool wino = false) {
-  const bool narrow = conv_is_narrow(Cin, Cout);
-  if (narrow) streamk = false;
-  // open-addressing table (a ten-stage run touches ~150 distinct shapes; the search is up to ~100 us for wide 2-D images)
-  struct Key { int B, Cin, Cout, T, H, W, KT, sk; };
-  struct Entry { Key k; Plan p; bool used; };
-  constexpr int NSLOT = 2048;
-  static thread_local Entry cache[NSLOT];
-  static thread_local int filled = 0;
-  const Key k{B, Cin, Cout, T, H, W, KT, (streamk ? 1 : 0) | (wino ? 2 : 0) | (wino ? g_wino_stg << 2 : 0)};
-  unsigned h = 2166136261u;
-  for (int v : {B, Cin, Cout, T, H, W, KT, k.sk}) h = (h ^ (unsigned)v) * 16777619u;
-  for (int probe = 0; probe < NSLOT; ++probe) {
-    Entry& e = cache[(h + probe) & (NSLOT - 1)];
-    if (!e.used) {
-      const Plan p = wino ? plan_wino_search(B, Cin, Cout, T, H, W, KT, streamk) : plan_conv_search(B, Cin, Cout, T, H, W, KT, streamk, narrow);
-      if (filled < NSLOT / 2) {  // keep the table sparse; past that, shapes are simply planned again
-        e.k = k; e.p = p; e.used = true;
-        ++filled;
-      }
-      return p;
-    }
-    const Key& c = e.k;
-    if (c.B == B && c.Cin == Cin && c.Cout == Cout && c.T == T && c.H == H && c.W == W && c.KT == KT && c.sk == k.sk) return e.p;
+  bool wino = conv_use_wino(k, c, prologue);
+  if (wino && conv_use_wino2d(k, pl.w2) && !fp32_out_mask) {   // (fp32 out-masks: one-axis kernel)
+    d.kind = 2;
+    d.ntl = pl.w2.ntl;
+    d.S = d.ntl < HPVG_NUM_CU ? d.ntl : HPVG_NUM_CU;
+    return d;
   }
-  return wino ? plan_wino_search(B, Cin, Cout, T, H, W, KT, streamk) : plan_conv_search(B, Cin, Cout, T, H, W, KT, streamk, narrow);
+  d.streamk = !k.sk_off && ws != nullptr;
+  if (wino && pl.wino[d.streamk].L == 0) wino = false;   // no Winograd tile fits this shape: the direct kernel takes it
+  const Plan* both = wino ? pl.wino : pl.direct;
+  if (d.streamk && ws_bytes < conv_sk_ws_bytes(c, both[1])) d.streamk = false;   // workspace too small: the plan without stream-K
+  d.kind = wino ? 1 : 0;
+  d.plan = &both[d.streamk];
+  d.ntl = conv_ntiles(c, *d.plan);
+  d.S = d.streamk ? conv_sk_grid(c, *d.plan) : d.ntl;   // S = ntl: one data-parallel round, no stream-K part
+  d.ws_bytes = d.streamk ? conv_sk_ws_bytes(c, *d.plan) : 0;
+  return d;
+}
+// what the host queries ask: no prologue, no fp32 mask, scratch available
+inline CDecision conv_decide_query(const CShape& c) { return conv_decide(c, false, false, &c, ~(size_t)0); }
+
+// ---------------------------------------------------------------------------------------------------------------- launches
+// (launch_lds: hpvg_host.h)  The operands of one hpvg_conv_fwd_* call
+struct CCall {
+  const float* x; const float* wp; const float* bias;
+  const float* in_scale; const float* in_shift; int in_lrelu;
+  float* y; int out_lrelu;
+  const float* out_mask; const unsigned* mask_bits; unsigned* bits_out;
+  void* ws; size_t ws_bytes;
+  CShape c;
+  hipStream_t s;
+};
+
+// kernel arguments of the direct, one-axis Winograd and narrow kernels
+ConvFwdArgs conv_args(const CCall& q, const CDecision& d, int stagger) {
+  const CShape& c = q.c;
+  const Plan& p = *d.plan;
+  ConvFwdArgs a{};
+  a.x = q.x; a.bias = q.bias; a.in_scale = q.in_scale; a.in_shift = q.in_shift; a.mask = q.out_mask; a.y = q.y;
+  a.wp = d.kind == 1 ? q.wp + direct_pack_floats(c.Cin, c.Cout, c.KT) : q.wp;   // the U fragments follow the direct pack
+  a.mask_bits = q.mask_bits; a.bits_out = q.bits_out;
+  a.B = c.B; a.Cin = c.Cin; a.Cout = c.Cout; a.T = c.T; a.H = c.H; a.W = c.W;
+  a.Th = p.Th; a.Tw = p.Tw; a.RS = p.RS; a.PL = p.PL; a.L = p.L; a.qstride = p.qstride; a.nrange = p.nrange; a.ntw = p.ntw; a.nblocks = p.nblocks;
+  a.nchunk = hpvg_cdiv(c.Cin, conv_cc(c.Cin));
+  a.mbtot = hpvg_cdiv(c.Cout, 32);
+  a.nj = p.nj;
+  a.in_lrelu = q.in_lrelu; a.out_lrelu = q.out_lrelu;
+  a.gridy = p.gridy;
+  a.ntl = d.ntl;
+  a.ndp = d.ntl / d.S;
+  a.skbase = a.ndp * d.S;
+  a.skpart = d.kind == 3 ? nullptr : (float*)q.ws;
+  a.stagger = d.kind == 1 && d.S > HPVG_NUM_CU ? stagger : 0;   // only when two workgroups share a CU
+  return a;
+}
+// ... of the two-axis Winograd kernels
+Wino2Args wino2_args(const CCall& q, const W2Geom& g) {
+  const CShape& c = q.c;
+  Wino2Args a{};
+  a.x = q.x; a.bias = q.bias; a.mask_bits = q.mask_bits; a.bits_out = q.bits_out; a.y = q.y;
+  a.wp = q.wp + direct_pack_floats(c.Cin, c.Cout, c.KT) + wino_pack_floats(c.Cin, c.Cout, c.KT);
+  a.B = c.B; a.Cin = c.Cin; a.Cout = c.Cout; a.T = c.T; a.H = c.H; a.W = c.W;
+  a.Cq = g.Cq; a.R = g.R; a.ntq = g.ntq; a.tqw = g.tqw; a.mbtot = wino2_mb(c.Cout); a.gridy = g.gridy;
+  a.nsc = g.nsc; a.ntl = g.ntl; a.PL = W2_PL; a.out_lrelu = q.out_lrelu;
+  a.mbreal = hpvg_cdiv(c.Cout, 32);   // (the mask words are laid out over the layer's real m-tile count)
+  return a;
 }
 
-// Launch of S workgroups.  The dynamic LDS request is padded to 56 KB so that a third workgroup never fits on a CU:
-// the persistent grid is sized for exactly two.
+// conv_mfma_kernel on S workgroups, then the fix-up of the tiles cut across them.  The dynamic LDS request is padded to
+// 56 KB so that a third workgroup never fits on a CU: the persistent grid is sized for exactly two (four per CU: padded to
+// 33 KB so that a fifth never fits).
 constexpr size_t CONV_MIN_LDS = 56 * 1024;
 template <int CC, int KT, int MB, int NB, int VAR>
 int launch_conv_var(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
-  static bool attr_set = false;
-  auto kern = conv_mfma_kernel<CC, KT, MB, NB, VAR>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-        hipSuccess)
-      (void)hipGetLastError();
-    attr_set = true;
-  }
-  // (four per CU: pad to 33 KB so that a fifth never fits)
   const size_t min_lds = HPVG_CONV_WGS(MB, NB) == 4 ? (size_t)33 * 1024 : CONV_MIN_LDS;
-  hipLaunchKernelGGL(kern, dim3(S), dim3(256), p.lds < min_lds ? min_lds : p.lds, s, a);
-  int rc = hpvg_launch_status();
-  if (rc != HPVG_OK) return rc;
+  const int rc = launch_lds<conv_mfma_kernel<CC, KT, MB, NB, VAR>>(dim3(S), dim3(256), p.lds < min_lds ? min_lds : p.lds, s, a);
   const int nsk = a.ntl - a.skbase;
-  if (nsk > 0) {
-    hipLaunchKernelGGL(conv_fixup_kernel, dim3(nsk, MB * NB), dim3(256), 0, s, a, S, MB, NB);
-    rc = hpvg_launch_status();
-  }
-  return rc;
+  if (rc != HPVG_OK || nsk <= 0) return rc;
+  hipLaunchKernelGGL(conv_fixup_kernel, dim3(nsk, MB * NB), dim3(256), 0, s, a, S, MB, NB);
+  return hpvg_launch_status();
 }
-
 template <int CC, int KT, int MB, int NB>
-int launch_conv(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
+int launch_conv_tile(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
   if (a.in_scale) return launch_conv_var<CC, KT, MB, NB, VAR_PRO>(a, p, S, s);
   if (a.mask || a.mask_bits) return launch_conv_var<CC, KT, MB, NB, VAR_MASK>(a, p, S, s);
   if (a.bits_out) return launch_conv_var<CC, KT, MB, NB, VAR_BITS>(a, p, S, s);
   return launch_conv_var<CC, KT, MB, NB, VAR_PLAIN>(a, p, S, s);
 }
-
 template <int CC, int KT>
-int dispatch_conv(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
+int launch_conv(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
   if (p.MB == 2) {
-    switch (p.NB) {
-      case 1: return launch_conv<CC, KT, 2, 1>(a, p, S, s);
-      case 2: return launch_conv<CC, KT, 2, 2>(a, p, S, s);
-      default: return launch_conv<CC, KT, 2, 4>(a, p, S, s);
-    }
+    if (p.NB == 1) return launch_conv_tile<CC, KT, 2, 1>(a, p, S, s);
+    return p.NB == 2 ? launch_conv_tile<CC, KT, 2, 2>(a, p, S, s) : launch_conv_tile<CC, KT, 2, 4>(a, p, S, s);
   }
-  switch (p.NB) {
-    case 1: return launch_conv<CC, KT, 1, 1>(a, p, S, s);
-    case 2: return launch_conv<CC, KT, 1, 2>(a, p, S, s);
-    default: return launch_conv<CC, KT, 1, 4>(a, p, S, s);
-  }
+  if (p.NB == 1) return launch_conv_tile<CC, KT, 1, 1>(a, p, S, s);
+  return p.NB == 2 ? launch_conv_tile<CC, KT, 1, 2>(a, p, S, s) : launch_conv_tile<CC, KT, 1, 4>(a, p, S, s);
 }
 
+// conv_wino_kernel and its fix-up
 template <int KT, int VAR, int STG>
 int launch_wino_var(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
-  static bool attr_set = false;
-  auto kern = conv_wino_kernel<KT, WINO_NBP, VAR, STG>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
-        hipSuccess)
-      (void)hipGetLastError();
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(S), dim3(256), p.lds < CONV_MIN_LDS ? CONV_MIN_LDS : p.lds, s, a);
-  int rc = hpvg_launch_status();
-  if (rc != HPVG_OK) return rc;
+  const int rc = launch_lds<conv_wino_kernel<KT, WINO_NBP, VAR, STG>>(dim3(S), dim3(256), p.lds < CONV_MIN_LDS ? CONV_MIN_LDS : p.lds, s, a);
   const int nsk = a.ntl - a.skbase;
-  if (nsk > 0) {
-    hipLaunchKernelGGL(conv_wino_fixup_kernel, dim3(nsk, WINO_NBP * 2), dim3(256), 0, s, a, S, WINO_NBP);
-    rc = hpvg_launch_status();
-  }
-  return rc;
+  if (rc != HPVG_OK || nsk <= 0) return rc;
+  hipLaunchKernelGGL(conv_wino_fixup_kernel, dim3(nsk, WINO_NBP * 2), dim3(256), 0, s, a, S, WINO_NBP);
+  return hpvg_launch_status();
 }
-
 template <int KT, int STG>
 int launch_wino_stg(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
   if (a.mask || a.mask_bits) return launch_wino_var<KT, VAR_MASK, STG>(a, p, S, s);
@@ -1485,117 +1548,40 @@ int launch_wino(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
   return p.stg == 2 ? launch_wino_stg<KT, 2>(a, p, S, s) : launch_wino_stg<KT, 1>(a, p, S, s);
 }
 
+// the two-axis kernels: conv_wino2r_kernel (only it has an odd-W instance), or the first generation with HPVG_WINO2R=0
+template <int VAR, bool TAIL>
+int launch_wino2d_inst(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
+  const size_t lds = (size_t)3 * 12 * W2_PL * sizeof(float);   // three input buffers
+  if (a.W & 1) return launch_lds<conv_wino2r_kernel<VAR, TAIL, true>>(dim3(S), dim3(256), lds, s, a);
+  if (w2r) return launch_lds<conv_wino2r_kernel<VAR, TAIL, false>>(dim3(S), dim3(256), lds, s, a);
+  return launch_lds<conv_wino2d_kernel<VAR, TAIL>>(dim3(S), dim3(256), lds, s, a);
+}
+template <int VAR>
+int launch_wino2d_var(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
+  return (((long)a.H * a.W) & 3) ? launch_wino2d_inst<VAR, true>(w2r, a, S, s) : launch_wino2d_inst<VAR, false>(w2r, a, S, s);
+}
+int launch_wino2d(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
+  if (a.mask_bits) return launch_wino2d_var<VAR_MASK>(w2r, a, S, s);
+  if (a.bits_out) return launch_wino2d_var<VAR_BITS>(w2r, a, S, s);
+  return launch_wino2d_var<VAR_PLAIN>(w2r, a, S, s);
+}
+
+// the narrow kernels: one or two 32-column tiles of the 9 * Cout rows of P
 template <int KT>
-int launch_conv_narrow(const ConvFwdArgs& a, const Plan& p, hipStream_t s) {
+int launch_narrow(const ConvFwdArgs& a, const CDecision& d, hipStream_t s) {
   const int ksteps = hpvg_cdiv(a.Cin * KT, 2);
-  const int pitch = (hpvg_cdiv((p.Th + 2) * p.RS, 32) * 32) | 1;  // odd: the 32 columns of a block land in 32 banks
+  const bool one = 9 * a.Cout <= 32;
+  if (d.narrow_gen == 2) {
+    const Narrow2Geom& g = d.plans->n2;
+    const dim3 grid((unsigned)d.plans->n2_tiles);
+    const size_t lds = (size_t)(9 * a.Cout) * g.pitch * sizeof(float);
+    return one ? launch_lds<conv_narrow2_kernel<KT, 1, 4>>(grid, dim3(256), lds, s, a, g, ksteps)
+               : launch_lds<conv_narrow2_kernel<KT, 2, 2>>(grid, dim3(256), lds, s, a, g, ksteps);
+  }
+  const int pitch = (hpvg_cdiv((d.plan->Th + 2) * d.plan->RS, 32) * 32) | 1;  // odd: the 32 columns of a block land in 32 banks
   const size_t lds = (size_t)(9 * a.Cout) * pitch * sizeof(float);
-#define HPVG_NARROW(NT)                                                                                              \
-  {                                                                                                                  \
-    static bool attr = false;                                                                                        \
-    if (!attr) {                                                                                                     \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_narrow_kernel<KT, NT>),                             \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                 \
-        (void)hipGetLastError();                                                                                     \
-      attr = true;                                                                                                   \
-    }                                                                                                                \
-    hipLaunchKernelGGL((conv_narrow_kernel<KT, NT>), dim3(a.ntl), dim3(256), lds, s, a, ksteps, pitch);              \
-  }
-  if (9 * a.Cout <= 32) HPVG_NARROW(1) else HPVG_NARROW(2)
-#undef HPVG_NARROW
-  return hpvg_launch_status();
-}
-
-// stream-K grid for a plan: all co-resident slots, or one workgroup per item when there are fewer items than slots
-inline int conv_sk_grid(int ntl, int nchunk, const Plan& p) {
-  const long items = (long)ntl * nchunk;
-  const long slots = conv_slots(p.MB, p.NB);
-  return (int)(items < slots ? items : slots);
-}
-inline size_t conv_sk_ws_bytes(const Plan& p, int S) { return (size_t)S * 2 * p.MB * p.NB * 16 * 256 * sizeof(float); }
-
-}  // namespace
-
-extern "C" {
-
-// number of floats of the packed-weight buffer for a conv with Cin -> Cout (kernel view)
-static size_t wpack_floats_impl(int Cin, int Cout, int KT, bool with2d) {
-  if (conv_is_narrow(Cin, Cout)) return (size_t)hpvg_cdiv(Cin * KT, 2) * hpvg_cdiv(9 * Cout, 32) * 64;  // wn[kstep][ntile][lane]
-  return direct_pack_floats(Cin, Cout, KT) + (conv_is_wino(Cin, Cout) ? wino_pack_floats(Cin, Cout, KT) : 0) +
-         (with2d && conv_is_wino2d(Cin, Cout, KT) ? wino2_pack_floats(Cin, Cout) : 0);
-}
-// does a launch of this geometry run the two-axis Winograd kernel (and therefore read the pack's third section)?
-static bool wants_wino2d(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (B < 1 || T < 1 || H < 1 || W < 1 || !conv_use_wino(B, Cin, Cout, T, H, W, KT, false)) return false;
-  return conv_use_wino2d(wino2d_geom(B, Cin, Cout, T, H, W, KT), false);
-}
-// A pack made WITHOUT a geometry serves every launch of the layer (all sections); the _for forms leave out the two-axis
-// Winograd fragments (786 KB for 64 -> 64 x 27) unless a launch of the given geometry (kernel view: the conv's input
-// B, T, H, W) reads them, and are valid for launches of that geometry only.
-size_t hpvg_conv_wpack_floats(int Cin, int Cout, int KT) { return wpack_floats_impl(Cin, Cout, KT, true); }
-size_t hpvg_conv_wpack_floats_for(int Cin, int Cout, int KT, int B, int T, int H, int W) {
-  return wpack_floats_impl(Cin, Cout, KT, wants_wino2d(B, Cin, Cout, T, H, W, KT));
-}
-int hpvg_conv_wants_wino2d(int B, int Cin, int Cout, int T, int H, int W, int KT) { return wants_wino2d(B, Cin, Cout, T, H, W, KT) ? 1 : 0; }
-
-// w: natural layout of the LAYER weight [Cout_layer][Cin_layer][KT][3][3].
-// transpose_flip = 0: pack for the forward conv (kernel Cin=Cin_layer, Cout=Cout_layer)
-// transpose_flip = 1: pack for backward-data (kernel Cin=Cout_layer, Cout=Cin_layer)
-static int pack_weight_impl(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
-                            int transpose_flip, bool with2d, void* stream);
-int hpvg_conv_pack_weight_f32(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
-                              int transpose_flip, void* stream) {
-  return pack_weight_impl(w, inv_scale, wp, Cin_layer, Cout_layer, KT, transpose_flip, true, stream);
-}
-int hpvg_conv_pack_weight_for_f32(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
-                                  int transpose_flip, int B, int T, int H, int W, void* stream) {
-  const int Cin_k = transpose_flip ? Cout_layer : Cin_layer, Cout_k = transpose_flip ? Cin_layer : Cout_layer;
-  return pack_weight_impl(w, inv_scale, wp, Cin_layer, Cout_layer, KT, transpose_flip, wants_wino2d(B, Cin_k, Cout_k, T, H, W, KT), stream);
-}
-static int pack_weight_impl(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
-                            int transpose_flip, bool with2d, void* stream) {
-  if (!w || !wp || (KT != 1 && KT != 3) || Cin_layer < 1 || Cout_layer < 1) return HPVG_ERR_ARG;
-  const int Cin_k = transpose_flip ? Cout_layer : Cin_layer;
-  const int Cout_k = transpose_flip ? Cin_layer : Cout_layer;
-  if (conv_is_narrow(Cin_k, Cout_k)) {
-    const long total = (long)wpack_floats_impl(Cin_k, Cout_k, KT, with2d);
-    hipLaunchKernelGGL(conv_pack_narrow_kernel, dim3(hpvg_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, inv_scale, wp,
-                       Cin_k, Cout_k, KT, hpvg_cdiv(9 * Cout_k, 32), hpvg_cdiv(Cin_k * KT, 2), transpose_flip, total);
-    return hpvg_launch_status();
-  }
-  const int CC = conv_cc(Cin_k);
-  const int nchunk = hpvg_cdiv(Cin_k, CC);
-  const int mbtot = hpvg_cdiv(Cout_k, 32);
-  const long total = (long)wpack_floats_impl(Cin_k, Cout_k, KT, with2d);
-  hipLaunchKernelGGL(conv_pack_kernel, dim3(hpvg_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, inv_scale, wp,
-                     Cin_k, Cout_k, KT * 9, CC, nchunk, mbtot, transpose_flip, (long)direct_pack_floats(Cin_k, Cout_k, KT), total);
-  return hpvg_launch_status();
-}
-
-// n <= HPVG_PACK_BATCH_MAX weights of one SQUARE layer shape (C -> C, C > 4) packed in one launch; flip[i] selects the
-// backward-data pack for item i.  Host arrays of device pointers (copied into the kernel arguments).
-static int pack_batch_impl(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, bool with2d, void* stream);
-int hpvg_conv_pack_weight_batch_f32(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, void* stream) {
-  return pack_batch_impl(n, w, wp, flip, C, KT, true, stream);
-}
-int hpvg_conv_pack_weight_batch_for_f32(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, int B, int T,
-                                        int H, int W, void* stream) {
-  return pack_batch_impl(n, w, wp, flip, C, KT, wants_wino2d(B, C, C, T, H, W, KT), stream);
-}
-static int pack_batch_impl(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, bool with2d, void* stream) {
-  if (n < 1 || n > HPVG_PACK_BATCH_MAX || !w || !wp || !flip || C <= 4 || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  PackBatchArgs a;
-  for (int i = 0; i < n; ++i) {
-    if (!w[i] || !wp[i]) return HPVG_ERR_ARG;
-    a.w[i] = w[i]; a.wp[i] = wp[i]; a.flip[i] = flip[i];
-  }
-  const int CC = conv_cc(C);
-  const int nchunk = hpvg_cdiv(C, CC);
-  const int mbtot = hpvg_cdiv(C, 32);
-  const long total = (long)wpack_floats_impl(C, C, KT, with2d);
-  hipLaunchKernelGGL(conv_pack_batch_kernel, dim3(hpvg_cdiv(total, 256), n), dim3(256), 0, (hipStream_t)stream, a, C, KT * 9, CC,
-                     nchunk, mbtot, (long)direct_pack_floats(C, C, KT), total);
-  return hpvg_launch_status();
+  return one ? launch_lds<conv_narrow_kernel<KT, 1>>(dim3(a.ntl), dim3(256), lds, s, a, ksteps, pitch)
+             : launch_lds<conv_narrow_kernel<KT, 2>>(dim3(a.ntl), dim3(256), lds, s, a, ksteps, pitch);
 }
 
 // y[b][o][t][h][w] = bias[o] + sum_{c,tap} Wp[o][c][tap] * f(x)[b][c][t+dt-pt][h+dh-1][w+dw-1]
@@ -1605,15 +1591,105 @@ static int pack_batch_impl(int n, const float* const* w, float* const* wp, const
 // the layer below, fused into this conv when it runs as that layer's consumer's backward-data pass.
 // ws / ws_bytes: hpvg_conv_fwd_ws_bytes() of scratch enables the stream-K schedule; with ws = NULL (or too small)
 // the same kernel runs one workgroup per tile.
-static int conv_fwd_impl(const float* x, const float* wp, const float* bias, const float* in_scale, const float* in_shift,
-                         int in_lrelu, float* y, int out_lrelu, const float* out_mask, const unsigned* mask_bits, unsigned* bits_out,
-                         void* ws, size_t ws_bytes, int B, int Cin, int Cout, int T, int H, int W, int KT, void* stream);
+int conv_fwd_launch(const CCall& q) {
+  const CShape& c = q.c;
+  if (!q.x || !q.wp || !q.y) return HPVG_ERR_ARG;
+  if (const int rc = conv_check(c)) return rc;
+  if ((q.in_scale == nullptr) != (q.in_shift == nullptr)) return HPVG_ERR_ARG;
+  if (q.in_scale && q.out_mask && !conv_is_narrow(c.Cin, c.Cout)) return HPVG_ERR_UNSUPPORTED;  // no caller combines prologue and mask
+  const CDecision d = conv_decide(c, q.in_scale != nullptr, q.out_mask != nullptr, q.ws, q.ws_bytes);
+  if (d.kind == 2) return launch_wino2d(cknobs().w2r, wino2_args(q, d.plans->w2), d.S, q.s);
+  if (d.plan->L == 0) return HPVG_ERR_UNSUPPORTED;
+  const ConvFwdArgs a = conv_args(q, d, cknobs().stagger);
+  if (d.kind == 3) return c.KT == 3 ? launch_narrow<3>(a, d, q.s) : launch_narrow<1>(a, d, q.s);
+  if (d.kind == 1) return c.KT == 3 ? launch_wino<3>(a, *d.plan, d.S, q.s) : launch_wino<1>(a, *d.plan, d.S, q.s);
+  if (conv_cc(c.Cin) == 8) return c.KT == 3 ? launch_conv<8, 3>(a, *d.plan, d.S, q.s) : launch_conv<8, 1>(a, *d.plan, d.S, q.s);
+  return c.KT == 3 ? launch_conv<4, 3>(a, *d.plan, d.S, q.s) : launch_conv<4, 1>(a, *d.plan, d.S, q.s);
+}
+
+// does a launch of this geometry run the two-axis Winograd kernel (and therefore read the pack's third section)?
+bool wants_wino2d(const CShape& c) { return conv_check(c) == HPVG_OK && conv_decide_query(c).kind == 2; }
+
+// w: natural layout of the LAYER weight [Cout_layer][Cin_layer][KT][3][3].
+// transpose_flip = 0: pack for the forward conv (kernel Cin=Cin_layer, Cout=Cout_layer)
+// transpose_flip = 1: pack for backward-data (kernel Cin=Cout_layer, Cout=Cin_layer)
+int pack_weight_launch(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT, int transpose_flip,
+                       bool with2d, void* stream) {
+  if (!w || !wp || (KT != 1 && KT != 3) || Cin_layer < 1 || Cout_layer < 1) return HPVG_ERR_ARG;
+  const int Cin_k = transpose_flip ? Cout_layer : Cin_layer;
+  const int Cout_k = transpose_flip ? Cin_layer : Cout_layer;
+  const long total = (long)wpack_floats(Cin_k, Cout_k, KT, with2d);
+  if (conv_is_narrow(Cin_k, Cout_k)) {
+    hipLaunchKernelGGL(conv_pack_narrow_kernel, dim3(hpvg_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, inv_scale, wp,
+                       Cin_k, Cout_k, KT, hpvg_cdiv(9 * Cout_k, 32), hpvg_cdiv(Cin_k * KT, 2), transpose_flip, total);
+    return hpvg_launch_status();
+  }
+  const int CC = conv_cc(Cin_k);
+  hipLaunchKernelGGL(conv_pack_kernel, dim3(hpvg_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, inv_scale, wp, Cin_k, Cout_k,
+                     KT * 9, CC, hpvg_cdiv(Cin_k, CC), hpvg_cdiv(Cout_k, 32), transpose_flip, (long)direct_pack_floats(Cin_k, Cout_k, KT),
+                     total);
+  return hpvg_launch_status();
+}
+
+// n <= HPVG_PACK_BATCH_MAX weights of one SQUARE layer shape (C -> C, C > 4) packed in one launch; flip[i] selects the
+// backward-data pack for item i.  Host arrays of device pointers (copied into the kernel arguments).
+int pack_batch_launch(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, bool with2d, void* stream) {
+  if (n < 1 || n > HPVG_PACK_BATCH_MAX || !w || !wp || !flip || C <= 4 || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
+  PackBatchArgs a;
+  for (int i = 0; i < n; ++i) {
+    if (!w[i] || !wp[i]) return HPVG_ERR_ARG;
+    a.w[i] = w[i]; a.wp[i] = wp[i]; a.flip[i] = flip[i];
+  }
+  const int CC = conv_cc(C);
+  const long total = (long)wpack_floats(C, C, KT, with2d);
+  hipLaunchKernelGGL(conv_pack_batch_kernel, dim3(hpvg_cdiv(total, 256), n), dim3(256), 0, (hipStream_t)stream, a, C, KT * 9, CC,
+                     hpvg_cdiv(C, CC), hpvg_cdiv(C, 32), (long)direct_pack_floats(C, C, KT), total);
+  return hpvg_launch_status();
+}
+
+// out[0..9] of the two wide plan queries, which differ in out[4] and in the tile count
+int write_plan(const Plan& p, int out4, int ntiles, int* out) {
+  out[0] = p.L; out[1] = p.Tw; out[2] = p.nrange; out[3] = p.ntw; out[4] = out4; out[5] = p.NB; out[6] = p.MB;
+  out[7] = p.gridy; out[8] = (int)p.lds; out[9] = ntiles;
+  return HPVG_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------ entry points
+extern "C" {
+
+// A pack made WITHOUT a geometry serves every launch of the layer (all sections); the _for forms leave out the two-axis
+// Winograd fragments (786 KB for 64 -> 64 x 27) unless a launch of the given geometry (kernel view: the conv's input
+// B, T, H, W) reads them, and are valid for launches of that geometry only.
+size_t hpvg_conv_wpack_floats(int Cin, int Cout, int KT) { return wpack_floats(Cin, Cout, KT, true); }
+size_t hpvg_conv_wpack_floats_for(int Cin, int Cout, int KT, int B, int T, int H, int W) {
+  return wpack_floats(Cin, Cout, KT, wants_wino2d({B, Cin, Cout, T, H, W, KT}));
+}
+int hpvg_conv_wants_wino2d(int B, int Cin, int Cout, int T, int H, int W, int KT) { return wants_wino2d({B, Cin, Cout, T, H, W, KT}) ? 1 : 0; }
+
+int hpvg_conv_pack_weight_f32(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
+                              int transpose_flip, void* stream) {
+  return pack_weight_launch(w, inv_scale, wp, Cin_layer, Cout_layer, KT, transpose_flip, true, stream);
+}
+int hpvg_conv_pack_weight_for_f32(const float* w, const float* inv_scale, float* wp, int Cin_layer, int Cout_layer, int KT,
+                                  int transpose_flip, int B, int T, int H, int W, void* stream) {
+  const int Cin_k = transpose_flip ? Cout_layer : Cin_layer, Cout_k = transpose_flip ? Cin_layer : Cout_layer;
+  return pack_weight_launch(w, inv_scale, wp, Cin_layer, Cout_layer, KT, transpose_flip, wants_wino2d({B, Cin_k, Cout_k, T, H, W, KT}), stream);
+}
+int hpvg_conv_pack_weight_batch_f32(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, void* stream) {
+  return pack_batch_launch(n, w, wp, flip, C, KT, true, stream);
+}
+int hpvg_conv_pack_weight_batch_for_f32(int n, const float* const* w, float* const* wp, const int* flip, int C, int KT, int B, int T,
+                                        int H, int W, void* stream) {
+  return pack_batch_launch(n, w, wp, flip, C, KT, wants_wino2d({B, C, C, T, H, W, KT}), stream);
+}
 
 int hpvg_conv_fwd_f32(const float* x, const float* wp, const float* bias, const float* in_scale, const float* in_shift,
                       int in_lrelu, float* y, int out_lrelu, const float* out_mask, void* ws, size_t ws_bytes, int B, int Cin,
                       int Cout, int T, int H, int W, int KT, void* stream) {
-  return conv_fwd_impl(x, wp, bias, in_scale, in_shift, in_lrelu, y, out_lrelu, out_mask, nullptr, nullptr, ws, ws_bytes, B, Cin,
-                       Cout, T, H, W, KT, stream);
+  return conv_fwd_launch({x, wp, bias, in_scale, in_shift, in_lrelu, y, out_lrelu, out_mask, nullptr, nullptr, ws, ws_bytes,
+                          {B, Cin, Cout, T, H, W, KT}, (hipStream_t)stream});
 }
 
 // number of 32-bit words of the 1-bit LeakyReLU mask of a [B][C][T][H][W] activation: [B][ceil(C/32)][T*H*W] (position fastest:
@@ -1627,169 +1703,81 @@ int hpvg_conv_fwd_bits_f32(const float* x, const float* wp, const float* bias, f
                            void* stream) {
   if (conv_is_narrow(Cin, Cout)) return HPVG_ERR_UNSUPPORTED;
   if (mask_bits && bits_out) return HPVG_ERR_UNSUPPORTED;
-  return conv_fwd_impl(x, wp, bias, nullptr, nullptr, 0, y, out_lrelu, nullptr, mask_bits, bits_out, ws, ws_bytes, B, Cin, Cout, T, H,
-                       W, KT, stream);
-}
-
-static int conv_fwd_impl(const float* x, const float* wp, const float* bias, const float* in_scale, const float* in_shift,
-                         int in_lrelu, float* y, int out_lrelu, const float* out_mask, const unsigned* mask_bits, unsigned* bits_out,
-                         void* ws, size_t ws_bytes, int B, int Cin, int Cout, int T, int H, int W, int KT, void* stream) {
-  if (!x || !wp || !y) return HPVG_ERR_ARG;
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
-  if (KT != 1 && KT != 3) return HPVG_ERR_UNSUPPORTED;
-  if ((in_scale == nullptr) != (in_shift == nullptr)) return HPVG_ERR_ARG;
-  if (in_scale && out_mask && !conv_is_narrow(Cin, Cout)) return HPVG_ERR_UNSUPPORTED;  // no caller combines prologue and mask
-  // development knob: HPVG_CONV_SK=0 forces the one-workgroup-per-tile schedule
-  static const bool sk_off = [] { const char* e = getenv("HPVG_CONV_SK"); return e && atoi(e) == 0; }();
-  const int CC = conv_cc(Cin);
-  const int nchunk = hpvg_cdiv(Cin, CC);
-  bool streamk = !sk_off && ws != nullptr && !conv_is_narrow(Cin, Cout);
-  bool wino = conv_use_wino(B, Cin, Cout, T, H, W, KT, in_scale != nullptr);
-  if (wino) {
-    const W2Geom q2 = wino2d_geom(B, Cin, Cout, T, H, W, KT);
-    if (conv_use_wino2d(q2, in_scale != nullptr) && !out_mask) {   // (fp32 out-masks: one-axis kernel)
-      Wino2Args w2;
-      w2.x = x; w2.bias = bias; w2.mask_bits = mask_bits; w2.bits_out = bits_out; w2.y = y;
-      w2.wp = wp + direct_pack_floats(Cin, Cout, KT) + wino_pack_floats(Cin, Cout, KT);
-      w2.B = B; w2.Cin = Cin; w2.Cout = Cout; w2.T = T; w2.H = H; w2.W = W;
-      w2.Cq = q2.Cq; w2.R = q2.R; w2.ntq = q2.ntq; w2.tqw = q2.tqw; w2.mbtot = wino2_mb(Cout); w2.gridy = q2.gridy;
-      w2.nsc = q2.nsc; w2.ntl = q2.ntl; w2.PL = W2_PL; w2.out_lrelu = out_lrelu; w2.mbreal = hpvg_cdiv(Cout, 32);
-      // (the mask words are laid out over the layer's real m-tile count)
-      Wino2Args a2 = w2;
-      hipStream_t s2 = (hipStream_t)stream;
-      if (mask_bits) return launch_wino2d_var<VAR_MASK>(a2, s2);
-      if (bits_out) return launch_wino2d_var<VAR_BITS>(a2, s2);
-      return launch_wino2d_var<VAR_PLAIN>(a2, s2);
-    }
-  }
-  Plan p = plan_conv(B, Cin, Cout, T, H, W, KT, streamk, wino);
-  if (wino && p.L == 0) {  // no Winograd tile fits this shape: the direct kernel takes it
-    wino = false;
-    p = plan_conv(B, Cin, Cout, T, H, W, KT, streamk, false);
-  }
-  if (p.L == 0) return HPVG_ERR_UNSUPPORTED;
-  int ntl = B * T * p.nrange * p.ntw * p.gridy;
-  if (streamk && ws_bytes < conv_sk_ws_bytes(p, conv_sk_grid(ntl, nchunk, p))) {
-    streamk = false;
-    p = plan_conv(B, Cin, Cout, T, H, W, KT, false, wino);
-    if (p.L == 0) return HPVG_ERR_UNSUPPORTED;
-    ntl = B * T * p.nrange * p.ntw * p.gridy;
-  }
-  ConvFwdArgs a;
-  a.x = x; a.wp = wp; a.bias = bias; a.in_scale = in_scale; a.in_shift = in_shift; a.mask = out_mask; a.y = y;
-  a.mask_bits = mask_bits; a.bits_out = bits_out;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.T = T; a.H = H; a.W = W;
-  a.Th = p.Th; a.Tw = p.Tw; a.RS = p.RS; a.PL = p.PL; a.L = p.L; a.qstride = p.qstride; a.nrange = p.nrange; a.ntw = p.ntw; a.nblocks = p.nblocks;
-  a.nchunk = nchunk;
-  a.mbtot = hpvg_cdiv(Cout, 32);
-  a.nj = p.nj;
-  a.in_lrelu = in_lrelu; a.out_lrelu = out_lrelu;
-  a.gridy = p.gridy;
-  a.ntl = ntl;
-  if (conv_is_narrow(Cin, Cout)) {
-    a.ndp = 1; a.skbase = ntl; a.skpart = nullptr;
-    // development knob: HPVG_NARROW2=0 keeps the first-generation kernel
-    static const bool n2_off = [] { const char* e = getenv("HPVG_NARROW2"); return e && atoi(e) == 0; }();
-    Narrow2Geom g2;
-    long nt2 = 0;
-    if (!n2_off && !in_scale && !out_mask && plan_narrow2(B, Cin, Cout, T, H, W, KT, &g2, &nt2))
-      return KT == 3 ? launch_conv_narrow2<3>(a, g2, nt2, (hipStream_t)stream) : launch_conv_narrow2<1>(a, g2, nt2, (hipStream_t)stream);
-    return KT == 3 ? launch_conv_narrow<3>(a, p, (hipStream_t)stream) : launch_conv_narrow<1>(a, p, (hipStream_t)stream);
-  }
-  const int S = streamk ? conv_sk_grid(ntl, nchunk, p) : ntl;  // S = ntl: one data-parallel round, no stream-K part
-  a.ndp = ntl / S;
-  a.skbase = a.ndp * S;
-  a.skpart = (float*)ws;
-  hipStream_t s = (hipStream_t)stream;
-  a.stagger = 0;
-  if (wino) {
-    static const int stagger_env = [] { const char* e = getenv("HPVG_WINO_STAGGER"); return e ? atoi(e) : 0; }();
-    a.stagger = (S > HPVG_NUM_CU) ? stagger_env : 0;   // only when two workgroups share a CU
-    a.wp = wp + direct_pack_floats(Cin, Cout, KT);   // the U fragments follow the direct pack
-    return KT == 3 ? launch_wino<3>(a, p, S, s) : launch_wino<1>(a, p, S, s);
-  }
-  if (CC == 8) return KT == 3 ? dispatch_conv<8, 3>(a, p, S, s) : dispatch_conv<8, 1>(a, p, S, s);
-  return KT == 3 ? dispatch_conv<4, 3>(a, p, S, s) : dispatch_conv<4, 1>(a, p, S, s);
+  return conv_fwd_launch({x, wp, bias, nullptr, nullptr, 0, y, out_lrelu, nullptr, mask_bits, bits_out, ws, ws_bytes,
+                          {B, Cin, Cout, T, H, W, KT}, (hipStream_t)stream});
 }
 
 // host only: which kernel family hpvg_conv_fwd_f32 / hpvg_conv_fwd_bits_f32 run this shape on (no prologue, no fp32 out-mask):
 // 0 = direct implicit GEMM (conv_mfma_kernel), 1 = Winograd F(2,3) along W (conv_wino_kernel: 2/3 of the direct matrix-core
 // work), 2 = Winograd F(2x2,3x3) (conv_wino2d_kernel: 4/9), 3 = the narrow-output kernel (Cout <= 4)
 int hpvg_conv_fwd_kernel_kind(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1 || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  if (conv_is_narrow(Cin, Cout)) return 3;
-  if (!conv_use_wino(B, Cin, Cout, T, H, W, KT, false)) return 0;
-  if (conv_use_wino2d(wino2d_geom(B, Cin, Cout, T, H, W, KT), false)) return 2;
-  return plan_conv(B, Cin, Cout, T, H, W, KT, true, true).L != 0 ? 1 : 0;
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  return conv_check(c) == HPVG_OK ? conv_decide_query(c).kind : HPVG_ERR_ARG;
 }
 
-// scratch the stream-K schedule of hpvg_conv_fwd_f32 wants for this shape
+// scratch the stream-K schedule of hpvg_conv_fwd_f32 wants for this shape: the larger of the direct and the one-axis kernel's
+// needs, since a launch with a BatchNorm prologue or an fp32 out-mask lands there whatever conv_decide_query answers
 size_t hpvg_conv_fwd_ws_bytes(int B, int Cin, int Cout, int T, int H, int W, int KT) {
-  if (B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1 || (KT != 1 && KT != 3)) return 0;
-  if (conv_is_narrow(Cin, Cout)) return 0;
-  // the larger of the two kernels' needs: a launch with a BatchNorm prologue runs the direct kernel on a Winograd shape
-  size_t need = 0;
-  for (int wino = 0; wino < 2; ++wino) {
-    if (wino && !conv_use_wino(B, Cin, Cout, T, H, W, KT, false)) break;
-    const Plan p = plan_conv(B, Cin, Cout, T, H, W, KT, true, wino != 0);
-    if (p.L == 0) continue;
-    const size_t n = conv_sk_ws_bytes(p, conv_sk_grid(B * T * p.nrange * p.ntw * p.gridy, hpvg_cdiv(Cin, conv_cc(Cin)), p));
-    if (n > need) need = n;
-  }
-  return need;
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (conv_check(c) != HPVG_OK || conv_is_narrow(Cin, Cout)) return 0;
+  const CKnobs& k = cknobs();
+  const CPlans& pl = conv_plans(k, c);
+  const size_t direct = conv_sk_ws_bytes(c, pl.direct[1]), wino = conv_use_wino(k, c, false) ? conv_sk_ws_bytes(c, pl.wino[1]) : 0;
+  return direct > wino ? direct : wino;
 }
 
-// Debug/introspection: the tile plan of the stream-K launch (for tests and DESIGN.md tables).
+// Debug/introspection: the tile plan of the direct kernel's stream-K launch (for tests and DESIGN.md tables), whichever
+// kernel runs the shape; a narrow shape: conv_narrow_kernel's tiles.
 // out[0..9] = L (positions per tile), Tw (band width), nrange (tiles per band plane), ntw (bands), nblocks, NB, MB, gridy,
-// lds_bytes, ntiles
+// lds_bytes, ntiles (of one output-channel group)
 int hpvg_conv_fwd_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
-  if (!out || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  const Plan p = plan_conv(B, Cin, Cout, T, H, W, KT, true);
-  out[0] = p.L; out[1] = p.Tw; out[2] = p.nrange; out[3] = p.ntw; out[4] = p.nblocks; out[5] = p.NB; out[6] = p.MB;
-  out[7] = p.gridy; out[8] = (int)p.lds; out[9] = B * T * p.nrange * p.ntw;
-  return HPVG_OK;
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
+  const Plan& p = conv_plans(cknobs(), c).direct[1];
+  return write_plan(p, p.nblocks, B * T * p.nrange * p.ntw, out);
 }
 
-// Run-time switch of the Winograd path (tests and A/B tools; see wino_env_mode): mode 0 = direct kernel only, 1 = from
-// `min_positions` output positions up, 2 = every eligible launch; a negative argument leaves that setting alone.  Returns
-// the mode in force, or HPVG_ERR_UNSUPPORTED when the library was started with HPVG_WINO=0 (packs carry no U fragments).
+// Run-time switch of the Winograd path (tests and A/B tools; see CKnobs): mode 0 = direct kernel only, 1 = from
+// `min_positions` output positions up, 2 = every eligible launch; 3 / 4: every eligible launch AND one staging form forced
+// (rows as in memory / halo'd bands); 5: every eligible launch, the two-axis kernel wherever it can run; 3 / 4 / 6: the
+// one-axis kernel only.  A negative argument leaves that setting alone.  Returns the mode in force, or HPVG_ERR_UNSUPPORTED
+// when the library was started with HPVG_WINO=0 (packs carry no U fragments).
 int hpvg_conv_wino_config(int mode, long min_positions) {
-  if (wino_env_mode() == 0) return HPVG_ERR_UNSUPPORTED;
-  (void)conv_use_wino(1, 8, 64, 1, 1, 1, 3, false);   // settle the defaults
+  CKnobs& k = cknobs();
+  if (k.env_wino == 0) return HPVG_ERR_UNSUPPORTED;
   if (mode >= 0) {
-    g_wino_mode = mode > 2 ? 2 : mode;
-    g_wino_stg = mode == 3 ? 2 : (mode == 4 ? 1 : 0);   // 3 / 4: every eligible launch AND one staging form forced (tests)
-    // 5: every eligible launch, the two-axis kernel wherever it can run; 3 / 4 / 6: the one-axis kernel only
-    g_wino2d = mode == 5 ? 2 : (mode == 3 || mode == 4 || mode == 6 ? 1 : 0);
+    const int stg = mode == 3 ? 2 : (mode == 4 ? 1 : 0);
+    if (stg != k.stg) ++k.gen;
+    k.wino = mode > 2 ? 2 : mode;
+    k.stg = stg;
+    k.w2d = mode == 5 ? 2 : (mode == 3 || mode == 4 || mode == 6 ? 1 : 0);
   }
-  if (min_positions >= 0) g_wino_min_pos = min_positions;
-  if (g_wino_mode == 2 && g_wino2d == 2) return 5;
-  if (g_wino_mode == 2 && g_wino_stg) return g_wino_stg == 2 ? 3 : 4;
-  if (g_wino_mode == 2 && g_wino2d == 1) return 6;
-  return g_wino_mode;
+  if (min_positions >= 0) k.min_pos = min_positions;
+  if (k.wino == 2 && k.w2d == 2) return 5;
+  if (k.wino == 2 && k.stg) return k.stg == 2 ? 3 : 4;
+  if (k.wino == 2 && k.w2d == 1) return 6;
+  return k.wino;
 }
 
 // Debug/introspection: the tile plan conv_wino_kernel would run this shape with (whether or not the launch picks it):
 // out[0..9] = L, Tw, nrange, ntw, RS, NBP, m-tiles per workgroup, gridy, lds_bytes, ntiles; HPVG_ERR_UNSUPPORTED when the
 // layer is not eligible (Cin < 8, Cout <= 32) or no tile fits.
 int hpvg_conv_wino_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
-  if (!out || (KT != 1 && KT != 3) || B < 1 || Cin < 1 || Cout < 1 || T < 1 || H < 1 || W < 1) return HPVG_ERR_ARG;
-  if (!conv_is_wino(Cin, Cout)) return HPVG_ERR_UNSUPPORTED;
-  const Plan p = plan_conv(B, Cin, Cout, T, H, W, KT, true, true);
-  if (p.L == 0) return HPVG_ERR_UNSUPPORTED;
-  out[0] = p.L; out[1] = p.Tw; out[2] = p.nrange; out[3] = p.ntw; out[4] = p.RS; out[5] = p.NB; out[6] = p.MB;
-  out[7] = p.gridy; out[8] = (int)p.lds; out[9] = B * T * p.nrange * p.ntw * p.gridy;
-  return HPVG_OK;
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
+  const Plan& p = conv_plans(cknobs(), c).wino[1];   // (not eligible: never searched)
+  return p.L ? write_plan(p, p.RS, conv_ntiles(c, p), out) : HPVG_ERR_UNSUPPORTED;
 }
 
 // Debug/introspection: the tile plan of the narrow-output kernel (conv_narrow2_kernel) for tests: out[0..6] = RS, Th, nth,
 // nb, npos, G, pitch, then nb triples (window start, first output column, output columns).  Returns HPVG_ERR_UNSUPPORTED
-// when the shape runs on the first-generation kernel instead.
+// when the shape runs on the first-generation kernel instead (HPVG_NARROW2 aside).
 int hpvg_conv_narrow_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
-  if (!out || (KT != 1 && KT != 3)) return HPVG_ERR_ARG;
-  Narrow2Geom g;
-  long nt = 0;
-  if (!conv_is_narrow(Cin, Cout) || !plan_narrow2(B, Cin, Cout, T, H, W, KT, &g, &nt)) return HPVG_ERR_UNSUPPORTED;
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
+  const CPlans& pl = conv_plans(cknobs(), c);   // (not narrow: n2_ok stays false)
+  if (!pl.n2_ok) return HPVG_ERR_UNSUPPORTED;
+  const Narrow2Geom& g = pl.n2;
   out[0] = g.RS; out[1] = g.Th; out[2] = g.nth; out[3] = g.nb; out[4] = g.npos; out[5] = g.G; out[6] = g.pitch;
   for (int k = 0; k < g.nb; ++k) { out[7 + 3 * k] = g.ws[k]; out[8 + 3 * k] = g.ob[k]; out[9 + 3 * k] = g.on[k]; }
   return HPVG_OK;

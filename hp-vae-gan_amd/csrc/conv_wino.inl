@@ -445,23 +445,6 @@ __device__ __forceinline__ float wino_pack_value(const float* __restrict__ w, lo
   return j == 0 ? gk[0] : (j == 1 ? 0.5f * ((gk[0] + gk[2]) + gk[1]) : (j == 2 ? 0.5f * ((gk[0] + gk[2]) - gk[1]) : gk[2]));
 }
 
-// HPVG_WINO (read once): 0 = no Winograd path at all (the weight pack carries no U fragments either), 2 = every eligible
-// launch, 1 / unset = eligible launches of at least HPVG_WINO_MIN output positions (B*T*H*W); mode and threshold can be
-// changed at run time through hpvg_conv_wino_config (tests, A/B tools) - except from / to 0 at start-up, which sizes the packs.
-inline int wino_env_mode() {
-  static const int m = [] { const char* e = getenv("HPVG_WINO"); return e ? atoi(e) : 1; }();
-  return m;
-}
-int g_wino_mode = -1;          // -1: not configured yet, take the environment's
-long g_wino_min_pos = -1;
-int g_wino_stg = 0;            // staging form of conv_wino_kernel: 0 = by size, 1 = halo'd bands only, 2 = rows-as-in-memory wherever it fits
-inline bool conv_is_wino(int Cin, int Cout) { return wino_env_mode() != 0 && Cin >= 8 && Cout > 32; }
-// the two-axis kernel (conv_wino2d.inl) has its own fragment section behind this one for the 3x3x3 layers; HPVG_WINO2D=0
-// (read once) leaves it out of the packs and of the dispatch
-inline bool conv_is_wino2d(int Cin, int Cout, int KT) {
-  static const bool off = [] { const char* e = getenv("HPVG_WINO2D"); return e && atoi(e) == 0; }();
-  return !off && KT == 3 && conv_is_wino(Cin, Cout);
-}
 inline size_t wino_pack_floats(int Cin, int Cout, int KT) {
   const int nchunk = hpvg_cdiv(Cin, WINO_CC);
   const int mbtot = hpvg_cdiv(Cout, 32);

@@ -84,6 +84,36 @@ def test_conv_stream_k_schedules_and_plain_launch(ops, B, Cin, Cout, sp):
     assert_close(y_pl, y_sk, 1e-5, "conv.plain-vs-streamk")
 
 
+@pytest.mark.parametrize("mode", [0, 4])
+def test_conv_workspace_one_byte_short_runs_the_plain_schedule(ops, wino_mode, mode):
+    """A launch whose workspace is one byte smaller than hpvg_conv_fwd_ws_bytes plans again without stream-K: the same kernel
+    on the same tiles as the ws = NULL launch, so the two outputs are equal bit for bit (direct kernel, mode 0; one-axis
+    Winograd kernel on halo'd bands, mode 4)."""
+    import ctypes
+    from hp_vae_gan_amd import lib as hplib
+    B, Cin, Cout, sp = 1, 64, 64, (4, 18, 33)
+    x = _rand(B, Cin, *sp, seed=31)
+    w = _rand(Cout, Cin, 3, 3, 3, seed=32, scale=0.05)
+    b = _rand(Cout, seed=33)
+    want = O.conv(x, w, b)
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    wino_mode(mode)
+    T, H, W = sp
+    assert hplib.load().hpvg_conv_fwd_kernel_kind(B, Cin, Cout, T, H, W, 3) == (1 if mode else 0)
+    need = hplib.call("hpvg_conv_fwd_ws_bytes", B, Cin, Cout, T, H, W, 3)
+    assert need > 1
+    wp = ops.pack_weight(wd, False)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    got = {}
+    for tag, wsp, nbytes in (("short", hplib.ptr(ws), need - 1), ("null", None, 0)):
+        y = torch.full((B, Cout) + sp, float("nan"), device=DEV)
+        hplib.call("hpvg_conv_fwd_f32", hplib.ptr(xd), hplib.ptr(wp), hplib.ptr(bd), None, None, 0, hplib.ptr(y), 0, None, wsp,
+                   ctypes.c_size_t(nbytes), B, Cin, Cout, T, H, W, 3, hplib.stream())
+        got[tag] = y
+    assert_close(got["short"], want, RTOL, "conv.ws-one-byte-short")
+    assert torch.equal(got["short"], got["null"])
+
+
 @pytest.fixture
 def wino_mode():
     """Switch the Winograd path (hpvg_conv_wino_config) for one test; restored afterwards."""

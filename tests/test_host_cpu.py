@@ -108,6 +108,9 @@ def test_size_queries_and_plans_run_without_gpu():
         assert hplib.call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT) > 0
     with pytest.raises(RuntimeError, match="HPVG_ERR_ARG"):  # bad KT -> error code, not a crash
         hplib.call("hpvg_conv_fwd_plan", 1, 1, 1, 1, 1, 1, 2, out)
+    with pytest.raises(RuntimeError, match="HPVG_ERR_ARG"):  # a dimension below 1 -> error code, not a division by zero
+        hplib.call("hpvg_conv_fwd_plan", 0, 64, 64, 4, 18, 33, 3, out)
+    assert hplib.load().hpvg_conv_narrow_plan(0, 64, 3, 4, 18, 33, 3, (ctypes.c_int * 55)()) == -1
 
 
 def test_winograd_conv_plan_geometry():

@@ -63,6 +63,10 @@
 // relaxed agent-scope atomics on parent (the XCDs' L2s are not coherent: a plain load may miss another XCD's atomicMin), it
 // waits for nobody, and each of its loops strictly lowers an index per trip; whatever needs the finished forest is a later
 // launch.  Sizes and statistics are integer atomic adds / max, so all outputs are independent of launch geometry and timing.
+//
+// Precision / recall / density / coverage of patch sets (the evaluate program's --prdc): patchnn_prdc.inl, included at the end,
+// puts two more epilogues on kernel 2's tile: the k smallest distances of every patch within its own volume, and the number
+// of keys whose per-key radius reaches a query.
 #include <limits.h>
 
 #include <type_traits>
@@ -1111,3 +1115,6 @@ int hpvg_nnf_chunks_i32(const int* nn, const int* d2, int max_d2, const int* qgr
 }
 
 }  // extern "C"
+
+// evaluate --prdc: the self k-nearest search and the ball count, two more epilogues on the tile above
+#include "patchnn_prdc.inl"

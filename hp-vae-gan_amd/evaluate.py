@@ -1,7 +1,7 @@
 """`python -m hp_vae_gan_amd.evaluate --exp-dir run/<clip>/<checkname>/experiment_<n>` (after `generate`), or
 `--samples S.npy --real R.npy` without an experiment: patch nearest-neighbour coherence / completeness, nn_unique_frac and
 diversity of the samples against the training clip, written to metrics.json; with --chunks also the copied-region statistics of
-the nearest-neighbour field."""
+the nearest-neighbour field; with --prdc K also the patch sets' precision, recall, density and coverage at k = K."""
 import argparse
 import json
 import math
@@ -39,6 +39,13 @@ def evaluate_parser():
                    '(default: every patch does)')
     p.add_argument('--save-chunks', action='store_true', help='with --chunks (which it implies): write chunks.npz (labels, sizes, '
                    'nn) and one source_XXXX.gif / .png per sample, coloured by where each patch came from')
+    p.add_argument('--prdc', type=_prdc_k, default=0, metavar='K', help='also report precision, recall, density and coverage of '
+                   'each sample\'s patch set against the real one, every patch\'s radius being the distance to its K-th nearest '
+                   'other patch of its own volume (1 <= K <= {}; default 0: off)'.format(ops.PATCH_KNN_MAX_K))
+    p.add_argument('--prdc-floor', type=_nonneg_float, default=None, metavar='X', help='with --prdc (required): no radius below '
+                   'floor(X * D * 255^2), X in the unit of coherence (default: none; saturated regions have radius 0)')
+    p.add_argument('--save-prdc', action='store_true', help='with --prdc (without it: nothing): write prdc.npz (count per sample patch, '
+                   'real_radius and real_covered on the real grid)')
     return p
 
 
@@ -46,6 +53,13 @@ def _nonneg_float(text):
     v = float(text)
     if not (v >= 0.0 and math.isfinite(v)):
         raise argparse.ArgumentTypeError("must be a finite number >= 0, got %s" % text)
+    return v
+
+
+def _prdc_k(text):
+    v = int(text)
+    if not 0 <= v <= ops.PATCH_KNN_MAX_K:
+        raise argparse.ArgumentTypeError("must be in [1, %d] (0: off), got %s" % (ops.PATCH_KNN_MAX_K, text))
     return v
 
 
@@ -130,6 +144,33 @@ def chunk_metrics(stats, Nq, E, kept_frac=False):
     return m
 
 
+def prdc_check(k, floor=None, Ns=None, Nr=None):
+    """Refuse what --prdc cannot score, as the program's exit: --prdc-floor without --prdc, K outside
+    [1, ops.PATCH_KNN_MAX_K], a floor < 0 and, once the patch counts are known, a side with no more than K patches (its K-th
+    neighbour does not exist).  k == 0 without a floor is "off" and passes."""
+    k = int(k or 0)
+    if k == 0:
+        if floor is not None:
+            raise SystemExit("evaluate: --prdc-floor needs --prdc K")
+        return
+    if not 1 <= k <= ops.PATCH_KNN_MAX_K:
+        raise SystemExit("evaluate: --prdc K must be in [1, {}], got {}".format(ops.PATCH_KNN_MAX_K, k))
+    if floor is not None and not (float(floor) >= 0.0 and math.isfinite(float(floor))):
+        raise SystemExit("evaluate: --prdc-floor must be a finite number >= 0, got {}".format(floor))
+    for name, n in (("sample", Ns), ("real volume", Nr)):
+        if n is not None and int(n) <= k:
+            raise SystemExit("evaluate: --prdc {}: the {} has {} patches, and every patch needs k = {} others".format(k, name, int(n), k))
+
+
+def prdc_metrics(inside, ball_sum, reached, covered, Ns, Nr, k):
+    """The four per-sample scores from integer counts, each one Python int / int division: precision = inside / Ns (sample
+    patches inside some real patch's ball), density = ball_sum / (k Ns) (the balls that hold a sample patch, summed),
+    recall = reached / Nr (real patches inside some sample patch's ball), coverage = covered / Nr (real patches whose own ball
+    holds a sample patch)."""
+    inside, ball_sum, reached, covered, Ns, Nr, k = (int(v) for v in (inside, ball_sum, reached, covered, Ns, Nr, k))
+    return {"precision": inside / Ns, "recall": reached / Nr, "density": ball_sum / (k * Ns), "coverage": covered / Nr}
+
+
 def source_colours(nn, ref_grid):
     """uint8 [..., 3] shaped as nn's patch grid: (R, G, B) = the (x, y, t) key coordinate of each patch's nearest neighbour,
     coordinate c of an axis of k positions as the byte (2 * 255 * c + (k - 1)) // (2 * (k - 1)), 0 when k == 1."""
@@ -140,10 +181,14 @@ def source_colours(nn, ref_grid):
 
 
 def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0,
-             chunks=False, chunk_tol=None, save_chunks=False):
+             chunks=False, chunk_tol=None, save_chunks=False, prdc=0, prdc_floor=None, save_prdc=False):
     """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
     `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions.
-    chunks (implied by chunk_tol / save_chunks): also the copied-region statistics of the coherence direction's field."""
+    chunks (implied by chunk_tol / save_chunks): also the copied-region statistics of the coherence direction's field.
+    prdc = k > 0: also precision / recall / density / coverage of the patch sets (prdc_floor is refused without it, save_prdc
+    does nothing without it)."""
+    prdc_check(prdc, prdc_floor)
+    prdc = int(prdc or 0)
     if exp_dir is None and (samples is None or real is None):
         raise SystemExit("evaluate: give --exp-dir, or both --samples and --real")
     spath = samples or os.path.join(exp_dir, 'eval', 'samples', 'samples.npy')
@@ -182,6 +227,21 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         max_d2 = None if chunk_tol is None else min(int(math.floor(float(chunk_tol) * (D * 255 * 255))), 2 ** 31 - 1)
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         chunk_seconds, saved = 0.0, []
+    if prdc:
+        # S: the sample's patches on the strided grid, R: the real volume's on the dense grid (as for --swd)
+        Ns, Nr = coh_counts[0], coh_counts[1]
+        prdc_check(prdc, prdc_floor, Ns, Nr)
+        one = (1, 1, 1)
+        grid3 = lambda t, st: tuple((v - p) // s + 1 for v, p, s in zip(vol(t), patch, st))   # noqa: E731
+        floor_d2 = None if prdc_floor is None else min(int(math.floor(float(prdc_floor) * (D * 255 * 255))), 2 ** 31 - 1)
+        p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        p0.record()
+        rad_real = ops.patch_knn_self(real_dev, patch, prdc)[..., prdc - 1]
+        zero_radius = int((rad_real == 0).sum())
+        rad_real = (rad_real if floor_d2 is None else rad_real.clamp(min=floor_d2)).contiguous()
+        p1.record()
+        p1.synchronize()
+        prdc_seconds, prdc_saved = p0.elapsed_time(p1) / 1e3, []
     per_sample = []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seconds = 0.0
@@ -205,6 +265,22 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
             if save_chunks:
                 saved.append((labels.cpu().numpy().reshape(grid), sizes.cpu().numpy().reshape(grid), nnc.cpu().numpy().reshape(grid),
                               source_colours(nnc, ref_grid).cpu().numpy()))
+        if prdc:
+            p0.record()
+            rad_smp = ops.patch_knn_self(smp, patch, prdc, stride)[..., prdc - 1]
+            rad_smp = (rad_smp if floor_d2 is None else rad_smp.clamp(min=floor_d2)).contiguous()
+            count = ops.patch_ball_count(smp, real_dev, rad_real, patch, qstride=stride)     # balls of R that hold s_i
+            reach = ops.patch_ball_count(real_dev, smp, rad_smp, patch, rstride=stride)      # balls of S that hold r_j
+            # min_i d2(r_j, s_i) over the strided sample grid; at stride 1 1 1 that is the completeness search
+            near = d2r if stride == one else ops.patch_nn(real_dev, smp, patch, rstride=stride)[0]
+            covered = near <= rad_real
+            ints = torch.stack([(count > 0).sum(), count.sum(dtype=torch.int64), (reach > 0).sum(), covered.sum()])
+            p1.record()
+            p1.synchronize()
+            prdc_seconds += p0.elapsed_time(p1) / 1e3
+            per_sample[-1].update(prdc_metrics(*ints.tolist(), Ns, Nr, prdc))
+            if save_prdc:
+                prdc_saved.append((count.cpu().numpy().reshape(grid3(smp, stride)), covered.cpu().numpy()))
     n = len(per_sample)
     metrics = {"samples": os.path.abspath(spath), "num_samples": n, "patch": list(patch), "stride": list(stride),
                "Nq": coh_counts[0], "Nr": coh_counts[1], "D": D, "Nq_completeness": com_counts[0], "Nr_completeness": com_counts[1],
@@ -241,20 +317,33 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
                      nn=np.stack([s[2] for s in saved]))
             for i, s in enumerate(saved):
                 write_frames(s[3], os.path.join(out, 'source_{:04d}{}'.format(i, '.gif' if video else '.png')), 10)
+    prdc_text = ""
+    if prdc:
+        for k in ("precision", "recall", "density", "coverage"):
+            metrics[k] = sum(p[k] for p in per_sample) / n
+        metrics.update({"prdc_k": prdc, "prdc_floor": None if prdc_floor is None else float(prdc_floor),
+                        "prdc_zero_radius_frac": zero_radius / Nr, "prdc_seconds": prdc_seconds})
+        prdc_text = " precision {:.6f} recall {:.6f} density {:.6f} coverage {:.6f}".format(
+            metrics["precision"], metrics["recall"], metrics["density"], metrics["coverage"])
+        if save_prdc:
+            rgrid = grid3(real_dev, one)
+            np.savez(os.path.join(out, 'prdc.npz'), count=np.stack([s[0] for s in prdc_saved]),
+                     real_radius=rad_real.cpu().numpy().reshape(rgrid),
+                     real_covered=np.stack([s[1].reshape(rgrid) for s in prdc_saved]))
     with open(os.path.join(out, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1, sort_keys=True)
-    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{} "
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{}{} "
           "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
                                                metrics["nn_unique_frac"],
                                                "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
-                                               swd_text, chunk_text, seconds, os.path.join(out, 'metrics.json')))
+                                               swd_text, chunk_text, prdc_text, seconds, os.path.join(out, 'metrics.json')))
     return metrics
 
 
 def main(argv=None):
     a = evaluate_parser().parse_args(argv)
     evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed, a.chunks, a.chunk_tol,
-             a.save_chunks)
+             a.save_chunks, a.prdc, a.prdc_floor, a.save_prdc)
     return 0
 
 

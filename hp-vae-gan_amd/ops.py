@@ -1448,6 +1448,63 @@ def patch_mask_count(mask_u8, patch, stride=(1, 1, 1)):
     return count[0] if image else count
 
 
+PATCH_KNN_MAX_K = 8   # hpvg_patchknn_self_u8 keeps at most this many distances per patch
+
+
+def patch_knn_self(vol_u8, patch, k, stride=(1, 1, 1)):
+    """The k smallest exact squared distances from every patch of a volume to the OTHER patches of the same strided grid
+    (hpvg_patchknn_self_u8, i8 matrix cores, one pass): vol is a uint8 device tensor [T,H,W,3] or [H,W,3], 1 <= k <= 8 < the
+    patch count.  Returns int32 [gT,gH,gW,k] ([gH,gW,k] for an image), ascending along the last axis and with multiplicity: a
+    patch is excluded from its own list by index, so an exact duplicate elsewhere contributes a 0.  [..., k-1] is the radius
+    of improved precision / recall."""
+    (v,), image = _patch_volumes("patch_knn_self", (("vol", vol_u8),))
+    pa, st = _triple(patch, "patch", "patch_knn_self"), _triple(stride, "stride", "patch_knn_self")
+    g = tuple(v.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *g, *g, pa, st, st, counts)   # refuses bad arguments by name
+    N = counts[0]
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > PATCH_KNN_MAX_K:
+        raise RuntimeError("patch_knn_self: k must be an int in [1, %d], got %r" % (PATCH_KNN_MAX_K, k))
+    if N <= k:
+        raise RuntimeError("patch_knn_self: %d patches cannot have %d neighbours each (the patch count must exceed k)" % (N, k))
+    grid = tuple((g[a] - pa[a]) // st[a] + 1 for a in range(3))
+    nbytes = call("hpvg_patchknn_self_ws_bytes", *g, pa, st, k)
+    ws = _scratch(nbytes, v.device)
+    kth = torch.empty(grid + (k,), dtype=torch.int32, device=v.device)
+    call("hpvg_patchknn_self_u8", ptr(v), *g, pa, st, k, ptr(kth), *ws, stream())
+    return kth[0] if image else kth
+
+
+def patch_ball_count(query_u8, ref_u8, ref_radius, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+    """For every patch of the query's strided grid the number of patches j of ref's grid with d2(q_i, r_j) <= ref_radius[j]
+    (hpvg_patch_ball_count_u8, i8 matrix cores; d2 the exact squared distance of patch_nn).  ref_radius: int32 device tensor of
+    Nr entries (flat, or shaped as ref's patch grid), every one >= 0.  Returns int32 shaped as the query's patch grid; > 0 is
+    "inside some ball" (precision / recall), the sum is the numerator of density."""
+    (q, r), image = _patch_volumes("patch_ball_count", (("query", query_u8), ("ref", ref_u8)))
+    pa, qs, rs = _triple(patch, "patch", "patch_ball_count"), _triple(qstride, "qstride", "patch_ball_count"), \
+        _triple(rstride, "rstride", "patch_ball_count")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
+    Nr = counts[1]
+    rgrid = tuple((rg[a] - pa[a]) // rs[a] + 1 for a in range(3))
+    rad = ref_radius
+    if not isinstance(rad, torch.Tensor) or rad.dtype != torch.int32 or rad.device != r.device or \
+            tuple(rad.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
+        raise RuntimeError("patch_ball_count: ref_radius must be int32 [%d] or %s on %s, got %s %s on %s"
+                           % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(rad, "dtype", type(rad)),
+                              tuple(getattr(rad, "shape", ())), getattr(rad, "device", None)))
+    rad = _c(rad)
+    if not bool((rad >= 0).all()):   # one device reduction
+        raise RuntimeError("patch_ball_count: every ref_radius must be >= 0")
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    nbytes = call("hpvg_patch_ball_count_ws_bytes", *qg, *rg, pa, qs, rs)
+    ws = _scratch(nbytes, q.device)
+    count = torch.empty(grid, dtype=torch.int32, device=q.device)
+    call("hpvg_patch_ball_count_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(rad), ptr(count), *ws, stream())
+    return count[0] if image else count
+
+
 def nnf_chunks(nn, ref_grid, qstride=(1, 1, 1), rstride=(1, 1, 1), d2=None, max_d2=None):
     """The copied regions of a nearest-neighbour field (hpvg_nnf_chunks_i32, a union-find over the patch grid): nn is an int32
     device tensor shaped as a query patch grid [gT,gH,gW] (or [gH,gW], as patch_nn returns it for images: gT = 1) of indices

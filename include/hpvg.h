@@ -343,6 +343,32 @@ int hpvg_patchproj_hist_u8(const unsigned char* vol, int T, int H, int W, const 
  * Na or Nb outside [1, 2^31), NB not 256 D + 1 for a D = 3 pt ph pw that hpvg_patchproj_bins accepts, Na * Nb * 256 D >= 2^63. */
 int hpvg_hist_w1_i32(const int* histA, long Na, const int* histB, long Nb, int P, long NB, long long* num, void* stream);
 
+/* ---- evaluation: the two searches of improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et
+ * al. 2020) on patch sets (evaluate --prdc; ops.patch_knn_self / ops.patch_ball_count).  Volumes, patches, strides and the exact
+ * int32 squared distance d2 are those of hpvg_patchnn_u8; both run on its i8 matrix-core tile, never store the products, and
+ * their results are functions of the inputs alone, independent of launch geometry and timing.
+ * Self k-nearest: kth[i][0..k) = the k smallest d2(i, j) over the patches j != i of the SAME volume's strided grid (N patches),
+ * ascending and with multiplicity - the exclusion is by index, so another patch at distance 0 counts, each once.  kth: int32
+ * [N][k] on the device.  One pass over the N x N products whatever k is.  HPVG_ERR_ARG: k < 1, k > 8, N <= k, and whatever
+ * hpvg_patchnn_counts refuses. */
+/* host only: bytes of workspace (the packed int8 patch matrix, its squared norms, the partial lists of the column splits); 0
+ * for arguments hpvg_patchknn_self_u8 refuses */
+size_t hpvg_patchknn_self_ws_bytes(int T, int H, int W, const int* patch, const int* stride, int k);
+/* ws as for hpvg_patchnn_u8 */
+int hpvg_patchknn_self_u8(const unsigned char* vol, int T, int H, int W, const int* patch, const int* stride, int k,
+                          int* kth /* [N][k] ascending */, void* ws, size_t ws_bytes, void* stream);
+/* Ball count: count[i] = #{j < Nr : d2(q_i, r_j) <= ref_radius[j]}, int32 [Nq], with an int32 radius per reference patch on the
+ * device, every one >= 0 (the caller's contract; a negative radius counts nothing).  count is cleared by the call itself, so a
+ * second call on the same output gives the same result; count[i] > 0 is "some ball holds q_i".  HPVG_ERR_ARG: what
+ * hpvg_patchnn_counts refuses, a null pointer, count not 4-byte aligned. */
+/* host only: bytes of workspace (both packed int8 patch matrices and their squared norms); 0 for arguments the call refuses */
+size_t hpvg_patch_ball_count_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
+                                      const int* rstride);
+/* ws as for hpvg_patchnn_u8 */
+int hpvg_patch_ball_count_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                             const int* patch, const int* qstride, const int* rstride, const int* ref_radius /* [Nr], >= 0 */,
+                             int* count /* [Nq] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- spectral norm (nn.utils.spectral_norm, networks_3d.py:63): one power iteration, sigma, 1/sigma; backward through sigma */
 int hpvg_sn_power_iter_f32(const float* w, float* u, float* v, float* sigma, float* inv_sigma, float* uv_copy, int Co, int K,
                            int do_iter, float eps, void* ws, size_t ws_bytes, void* stream);

@@ -983,6 +983,7 @@ struct CKnobs {
   // per MFMA)
   bool w2r;
   bool w2d_off;        // HPVG_WINO2D=0: no two-axis section in the packs, no two-axis kernel in the dispatch
+  bool w2_split_off;   // HPVG_W2_SPLIT=0: conv_wino2r_kernel in whole-tile rounds only (w2_split_plan)
   int stagger;         // HPVG_WINO_STAGGER: ConvFwdArgs::stagger of a one-axis launch with two workgroups per CU
   int only_nb, only_mb, only_ntw;   // development: HPVG_PLAN_NB / _MB / _NTW restrict the wide searches to one value
   // HPVG_WINO as the process started: 0 = no Winograd path at all (the weight packs carry no U fragments either, and
@@ -1003,6 +1004,7 @@ CKnobs& cknobs() {
     k.narrow2_off = num("HPVG_NARROW2", 1) == 0;
     k.w2r = num("HPVG_WINO2R", 1) != 0;
     k.w2d_off = num("HPVG_WINO2D", 1) == 0;
+    k.w2_split_off = num("HPVG_W2_SPLIT", 1) == 0;
     k.stagger = (int)num("HPVG_WINO_STAGGER", 0);
     k.only_nb = (int)num("HPVG_PLAN_NB", 0);
     k.only_mb = (int)num("HPVG_PLAN_MB", 0);
@@ -1240,7 +1242,25 @@ Plan plan_wino_search(const CKnobs& k, const CShape& c, bool streamk) {
 }
 
 // Geometry of the two-axis Winograd kernels (conv_wino2d.inl, conv_wino2r.inl); ok = false where they cannot run
-struct W2Geom { int Cq, R, ntq, tqw, gridy, nsc, ntl; bool ok; };
+struct W2Geom {
+  int Cq, R, ntq, tqw, gridy, nsc, ntl;
+  int sp_full, sp_parts, sp_wgs;   // w2_split_plan: tiles of the whole-tile launch, parts per leftover tile (1: no split), workgroups of the part launch
+  bool ok;
+};
+// conv_wino2r_kernel runs whole tiles, one persistent workgroup per CU: ceil(ntl / 256) rounds, the last one as long as the
+// others however few tiles it holds (6 of 256 at level 6, B = 2).  A thinly filled last round is cut out of the whole-tile
+// launch and run by a second launch of the kernel's SUB instances, one PART of a tile per workgroup - no workspace, no
+// partial sums, the same bits (conv_wino2r.inl): with r = ntl mod 256 leftover tiles after at least one full round,
+// r <= 64: 4 r quarter tiles (one 32 x 32 block each), r <= 128: 2 r half tiles (one quad half each); the parts fit one
+// round.  More leftover tiles, a launch of one round or less, the first-generation kernel, HPVG_W2_SPLIT=0: whole tiles.
+void w2_split_plan(const CKnobs& k, W2Geom& q) {
+  q.sp_full = q.ntl; q.sp_parts = 1; q.sp_wgs = 0;
+  const int r = q.ntl % HPVG_NUM_CU;
+  if (k.w2_split_off || !k.w2r || q.ntl <= HPVG_NUM_CU || r == 0 || r > HPVG_NUM_CU / 2) return;
+  q.sp_parts = r <= HPVG_NUM_CU / 4 ? 4 : 2;
+  q.sp_full = q.ntl - r;
+  q.sp_wgs = r * q.sp_parts;
+}
 W2Geom wino2d_geom(const CKnobs& k, const CShape& c) {
   const auto [B, Cin, Cout, T, H, W, KT] = c;
   W2Geom q{};
@@ -1268,6 +1288,7 @@ W2Geom wino2d_geom(const CKnobs& k, const CShape& c) {
   const long ntl = (long)B * T * q.ntq * q.gridy;
   if (ntl > 0x7fffffffL) return q;
   q.ntl = (int)ntl;
+  w2_split_plan(k, q);
   q.ok = true;
   return q;
 }
@@ -1390,7 +1411,8 @@ inline bool conv_use_wino(const CKnobs& k, const CShape& c, bool prologue) {
 }
 // Where the two-axis kernel is taken, of the launches conv_use_wino lets through: by size where it was measured to win.
 // Whole tiles, one workgroup per CU, no stream-K: a launch takes ceil(tiles / 256)
-// rounds of ~72 us (64 -> 64), the one-axis kernel + fix-up ~100-120 us per 256 tiles' worth of work (more below one round).
+// rounds of ~72 us (64 -> 64; w2_split_plan runs a last round that is at most half full as half / quarter tiles, 0.45-0.7 of a
+// round - the rule below was measured without it and counts whole rounds), the one-axis kernel + fix-up ~100-120 us per 256 tiles' worth of work (more below one round).
 // Round 3, conv_wino2r_kernel against the one-axis kernel (tools/perf_wino2.py, profiles/r03_perf_wino2r_sizes.txt; rounds =
 // tiles / 256): 0.35 x0.94, 0.59 x1.12, 0.70 x1.48, 0.94 x1.43, 1.17 x0.94, 1.88 x1.36, 1.97 x1.07 (odd W), 3.23 x1.18-1.21,
 // 3.94 x1.13 (odd W), 4.98 x1.37, 6.45 x1.31, 14.6 x1.33.  (Before the plane-end patch ran on twelve lanes at once the TAIL
@@ -1549,21 +1571,38 @@ int launch_wino(const ConvFwdArgs& a, const Plan& p, int S, hipStream_t s) {
 }
 
 // the two-axis kernels: conv_wino2r_kernel (only it has an odd-W instance), or the first generation with HPVG_WINO2R=0
+// (sub: conv_wino2r_kernel's SUB - 0 whole tiles, 1 half tiles, 2 quarter tiles; only w2_split_plan asks for 1 or 2)
+template <int VAR, bool TAIL, bool ODD>
+int launch_wino2r_sub(int sub, const Wino2Args& a, int S, size_t lds, hipStream_t s) {
+  if (sub == 2) return launch_lds<conv_wino2r_kernel<VAR, TAIL, ODD, 2>>(dim3(S), dim3(256), lds, s, a);
+  if (sub == 1) return launch_lds<conv_wino2r_kernel<VAR, TAIL, ODD, 1>>(dim3(S), dim3(256), lds, s, a);
+  return launch_lds<conv_wino2r_kernel<VAR, TAIL, ODD, 0>>(dim3(S), dim3(256), lds, s, a);
+}
 template <int VAR, bool TAIL>
-int launch_wino2d_inst(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
+int launch_wino2d_inst(bool w2r, int sub, const Wino2Args& a, int S, hipStream_t s) {
   const size_t lds = (size_t)3 * 12 * W2_PL * sizeof(float);   // three input buffers
-  if (a.W & 1) return launch_lds<conv_wino2r_kernel<VAR, TAIL, true>>(dim3(S), dim3(256), lds, s, a);
-  if (w2r) return launch_lds<conv_wino2r_kernel<VAR, TAIL, false>>(dim3(S), dim3(256), lds, s, a);
+  if (a.W & 1) return launch_wino2r_sub<VAR, TAIL, true>(sub, a, S, lds, s);
+  if (w2r) return launch_wino2r_sub<VAR, TAIL, false>(sub, a, S, lds, s);
   return launch_lds<conv_wino2d_kernel<VAR, TAIL>>(dim3(S), dim3(256), lds, s, a);
 }
 template <int VAR>
-int launch_wino2d_var(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
-  return (((long)a.H * a.W) & 3) ? launch_wino2d_inst<VAR, true>(w2r, a, S, s) : launch_wino2d_inst<VAR, false>(w2r, a, S, s);
+int launch_wino2d_var(bool w2r, int sub, const Wino2Args& a, int S, hipStream_t s) {
+  return (((long)a.H * a.W) & 3) ? launch_wino2d_inst<VAR, true>(w2r, sub, a, S, s) : launch_wino2d_inst<VAR, false>(w2r, sub, a, S, s);
 }
-int launch_wino2d(bool w2r, const Wino2Args& a, int S, hipStream_t s) {
-  if (a.mask_bits) return launch_wino2d_var<VAR_MASK>(w2r, a, S, s);
-  if (a.bits_out) return launch_wino2d_var<VAR_BITS>(w2r, a, S, s);
-  return launch_wino2d_var<VAR_PLAIN>(w2r, a, S, s);
+int launch_wino2d_form(bool w2r, int sub, const Wino2Args& a, int S, hipStream_t s) {
+  if (a.mask_bits) return launch_wino2d_var<VAR_MASK>(w2r, sub, a, S, s);
+  if (a.bits_out) return launch_wino2d_var<VAR_BITS>(w2r, sub, a, S, s);
+  return launch_wino2d_var<VAR_PLAIN>(w2r, sub, a, S, s);
+}
+// the whole-tile launch over the full rounds, then (w2_split_plan) the leftover tiles' parts on the same stream
+int launch_wino2d(bool w2r, Wino2Args a, const W2Geom& g, int S, hipStream_t s) {
+  if (g.sp_parts == 1) return launch_wino2d_form(w2r, 0, a, S, s);
+  a.ntl = g.sp_full;
+  const int rc = launch_wino2d_form(w2r, 0, a, HPVG_NUM_CU, s);
+  if (rc != HPVG_OK) return rc;
+  a.sub0 = g.sp_full;
+  a.ntl = g.sp_wgs;
+  return launch_wino2d_form(w2r, g.sp_parts == 4 ? 2 : 1, a, g.sp_wgs, s);
 }
 
 // the narrow kernels: one or two 32-column tiles of the 9 * Cout rows of P
@@ -1598,7 +1637,7 @@ int conv_fwd_launch(const CCall& q) {
   if ((q.in_scale == nullptr) != (q.in_shift == nullptr)) return HPVG_ERR_ARG;
   if (q.in_scale && q.out_mask && !conv_is_narrow(c.Cin, c.Cout)) return HPVG_ERR_UNSUPPORTED;  // no caller combines prologue and mask
   const CDecision d = conv_decide(c, q.in_scale != nullptr, q.out_mask != nullptr, q.ws, q.ws_bytes);
-  if (d.kind == 2) return launch_wino2d(cknobs().w2r, wino2_args(q, d.plans->w2), d.S, q.s);
+  if (d.kind == 2) return launch_wino2d(cknobs().w2r, wino2_args(q, d.plans->w2), d.plans->w2, d.S, q.s);
   if (d.plan->L == 0) return HPVG_ERR_UNSUPPORTED;
   const ConvFwdArgs a = conv_args(q, d, cknobs().stagger);
   if (d.kind == 3) return c.KT == 3 ? launch_narrow<3>(a, d, q.s) : launch_narrow<1>(a, d, q.s);
@@ -1735,6 +1774,19 @@ int hpvg_conv_fwd_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, in
   if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
   const Plan& p = conv_plans(cknobs(), c).direct[1];
   return write_plan(p, p.nblocks, B * T * p.nrange * p.ntw, out);
+}
+
+// host only: how a launch of this shape that runs the two-axis kernel (hpvg_conv_fwd_kernel_kind 2; any other shape:
+// HPVG_ERR_UNSUPPORTED) is cut (w2_split_plan): out[0..3] = tiles of the whole-tile launch, leftover tiles, parts per leftover
+// tile (1 = none, 2 = half tiles, 4 = quarter tiles), workgroups of the launch that runs the parts
+int hpvg_conv_w2_split(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
+  const CDecision d = conv_decide_query(c);
+  if (d.kind != 2) return HPVG_ERR_UNSUPPORTED;
+  const W2Geom& g = d.plans->w2;
+  out[0] = g.sp_full; out[1] = g.ntl - g.sp_full; out[2] = g.sp_parts; out[3] = g.sp_wgs;
+  return HPVG_OK;
 }
 
 // Run-time switch of the Winograd path (tests and A/B tools; see CKnobs): mode 0 = direct kernel only, 1 = from

@@ -37,6 +37,7 @@ struct Wino2Args {
   int Cq, R, ntq, tqw;    // quads per row, quad rows, tiles per plane (64 consecutive quads each), unused
   int mbtot, gridy, nsc, ntl, PL, out_lrelu;
   int mbreal;             // m-tiles of the layer (the 1-bit mask words' layout); mbtot is rounded up to an even count
+  int sub0;               // conv_wino2r_kernel's SUB instances: the first tile of the launch (ntl then counts its parts)
 };
 
 constexpr int W2_PL = 1024 + 8;   // floats per plane slot: 256 lanes x 16 bytes + the one-float shift (+ pad)

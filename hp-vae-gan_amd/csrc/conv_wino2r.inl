@@ -21,7 +21,18 @@
 // patch row starts at an odd float: the rows are read with four ds_read_b32 each instead of two ds_read_b64 (LDS reads are free
 // beside the MFMAs), the last quad column's input columns W, W + 1 are zeroed by a third border factor (f2), its second output
 // column is not stored, and the 1-bit mask words are accessed one by one; the plane-end patch (TAIL) copies H * W % 4 floats.
+// SUB (separate instances, launched behind the whole-tile launch for the tiles of a thinly filled last round: conv_mfma.hip,
+// W2Geom): a workgroup computes ONE part of one tile - SUB = 1 a quad half (both m-tiles x 32 quads: half the MFMAs, half the
+// input transform, two of the four epilogue blocks), SUB = 2 one 32 x 32 block (a quarter of the MFMAs) - and then ends.
+// a.ntl counts the parts, part g belongs to tile a.sub0 + g / parts-per-tile.  Staging, U-load and wait sequence are the whole
+// tile's (every lane of every wave stages: conv_dma_piece16_all's precondition); only the MFMAs, transforms and stores of the
+// other parts are left out at compile time, and wave i still owns point row i, so every output element is summed by the
+// same MFMA sequence and epilogue order as in a whole tile: bit-identical results.  Block (m-tile lm, quad half lq) of the part
+// is finished by wave lq * 2 + lm; a wave without a block only sends its rows.
 
+// byte offset of ring entry [1]: the second m-tile's fragment; a part with one m-tile loads its own a second time there (never
+// used), so that the vector-memory sequence the wait counts below are made for stays what it is
+#define W2R_A1 (NMT == 2 ? 1024 : 0)
 #define W2R_WAIT_A(N, S) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(au[S][0]), "+v"(au[S][1]) : : "memory")
 
 #ifdef HPVG_ABL2_NOSTAGE
@@ -35,15 +46,17 @@
 #define W2R_ABL_LOADA(D, O, B) w2_load_a(D, O, B)
 #endif
 
-template <int VAR, bool TAIL, bool ODD>
+template <int VAR, bool TAIL, bool ODD, int SUB = 0>
 __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) {
+  constexpr int NMT = SUB == 2 ? 1 : 2, NQH = SUB == 0 ? 2 : 1;   // m-tiles, quad halves a workgroup computes
+  constexpr int NSUB = 4 / (NMT * NQH);                          // parts per tile
   extern __shared__ __attribute__((aligned(16))) float xs[];
   typedef __attribute__((address_space(3))) void* lptr_t;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, l31 = lane & 31;
-  const int mw = wave & 1, nw = wave >> 1;          // the block this wave owns in the epilogue
+  const int mw0 = wave & 1, nw0 = wave >> 1;        // the block this wave owns in the epilogue (SUB: of the part's blocks)
   // point row of this wave: vertical pass  t[c] = d[ra][c] + sv * d[rb][c]  (B^T rows: d0 - d2, d1 + d2, d2 - d1, d1 - d3)
   const int ri = wave;
   const int ra = ri == 0 ? 0 : (ri == 2 ? 2 : 1);
@@ -56,7 +69,11 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
   const int S = gridDim.x;
   const int g = hpvg_xcd_remap(blockIdx.x, S);
   if (g >= a.ntl) return;
-  const int nmy = (a.ntl - 1 - g) / S + 1;          // this workgroup's tiles: g, g + S, ...
+  const int nmy = SUB ? 1 : (a.ntl - 1 - g) / S + 1;   // this workgroup's tiles: g, g + S, ... (SUB: one part of one tile)
+  const int smt = SUB == 2 ? (g & 1) : 0;              // first m-tile / quad half of this workgroup's part
+  const int sqh = SUB == 2 ? ((g >> 1) & 1) : (SUB == 1 ? (g & 1) : 0);
+  const int mw = mw0 + smt, nw = nw0 + sqh;            // ... of the tile's
+  const bool own = SUB == 0 || (mw0 < NMT && nw0 < NQH);   // (SUB: the waves past the part's blocks own none)
   const int nsc = a.nsc;
   const unsigned lds0 = (unsigned)(size_t)(lptr_t)xs;
   const char* zero_ptr = reinterpret_cast<const char*>(g_zero_word);
@@ -143,8 +160,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
     decode(tile, b, t, tp, yb);
     const int lo4 = span_lo4(tp);
 #pragma unroll
-    for (int qh = 0; qh < 2; ++qh) {
-      int Q = tp * 64 + qh * 32 + l31;
+    for (int qh = 0; qh < NQH; ++qh) {
+      int Q = tp * 64 + (qh + sqh) * 32 + l31;
       if (Q > nq - 1) Q = nq - 1;                                // lanes past the plane's last quad read (and discard) its patch
       const int Rq = Q / a.Cq, w = 2 * (Q - Rq * a.Cq);
       const int base = half * 3 * PL + 1 + ((2 * Rq - 1) * W + w - 1 - lo4);   // even; + (2 cp * 3 + dt) * PL + r * W + c
@@ -154,13 +171,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
       q.f3[qh] = w + 2 >= W ? 0.f : 1.f;
       q.f2[qh] = w + 1 >= W ? 0.f : 1.f;     // (odd W only: the last quad column's second column is outside the image)
     }
+    if constexpr (NQH == 1) { q.ba[1] = q.ba[0]; q.bb[1] = q.bb[0]; q.f0[1] = q.f0[0]; q.f3[1] = q.f3[0]; q.f2[1] = q.f2[0]; }
     return q;
   };
   auto cmp_setup = [&](int tile) __attribute__((always_inline)) {   // the owned block's quad of this lane (epilogue)
     int tp;
     decode(tile, c_b, c_t, tp, c_yb);
     const int Q = tp * 64 + nw * 32 + l31;
-    c_vq = Q < nq;
+    c_vq = Q < nq && own;
     const int Rq = Q / a.Cq;
     c_h = 2 * Rq;
     c_w = 2 * (Q - Rq * a.Cq);
@@ -198,10 +216,12 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
     if constexpr (!ODD) {                                                                       \
       W2R_DSREAD(rwa[0][0], (XA)[0], so_); W2R_DSREAD(rwa[0][1], (XA)[0], so_ + 8);             \
       W2R_DSREAD(rwb[0][0], (XB)[0], so_); W2R_DSREAD(rwb[0][1], (XB)[0], so_ + 8);             \
-      W2R_DSREAD(rwa[1][0], (XA)[1], so_); W2R_DSREAD(rwa[1][1], (XA)[1], so_ + 8);             \
-      W2R_DSREAD(rwb[1][0], (XB)[1], so_); W2R_DSREAD(rwb[1][1], (XB)[1], so_ + 8);             \
+      if constexpr (NQH == 2) {                                                                 \
+        W2R_DSREAD(rwa[1][0], (XA)[1], so_); W2R_DSREAD(rwa[1][1], (XA)[1], so_ + 8);           \
+        W2R_DSREAD(rwb[1][0], (XB)[1], so_); W2R_DSREAD(rwb[1][1], (XB)[1], so_ + 8);           \
+      }                                                                                         \
     } else {                                                                                    \
-      _Pragma("unroll") for (int qh_ = 0; qh_ < 2; ++qh_) {                                     \
+      _Pragma("unroll") for (int qh_ = 0; qh_ < NQH; ++qh_) {                                   \
         W2R_DSREAD1(rfa[qh_][0], (XA)[qh_], so_); W2R_DSREAD1(rfa[qh_][1], (XA)[qh_], so_ + 4); \
         W2R_DSREAD1(rfa[qh_][2], (XA)[qh_], so_ + 8); W2R_DSREAD1(rfa[qh_][3], (XA)[qh_], so_ + 12); \
         W2R_DSREAD1(rfb[qh_][0], (XB)[qh_], so_); W2R_DSREAD1(rfb[qh_][1], (XB)[qh_], so_ + 4); \
@@ -211,7 +231,12 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
   }
 #define W2R_WAIT_RAW()                                                                          \
   {                                                                                             \
-    if constexpr (!ODD)                                                                         \
+    if constexpr (NQH == 1 && !ODD)                                                             \
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rwa[0][0]), "+v"(rwa[0][1]), "+v"(rwb[0][0]), "+v"(rwb[0][1]));  \
+    else if constexpr (NQH == 1)                                                                \
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rfa[0][0]), "+v"(rfa[0][1]), "+v"(rfa[0][2]), "+v"(rfa[0][3]),  \
+                   "+v"(rfb[0][0]), "+v"(rfb[0][1]), "+v"(rfb[0][2]), "+v"(rfb[0][3]));         \
+    else if constexpr (!ODD)                                                                    \
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rwa[0][0]), "+v"(rwa[0][1]), "+v"(rwa[1][0]), "+v"(rwa[1][1]),  \
                    "+v"(rwb[0][0]), "+v"(rwb[0][1]), "+v"(rwb[1][0]), "+v"(rwb[1][1]));         \
     else                                                                                        \
@@ -257,6 +282,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
       OUT[QH][3] = __builtin_fmaf(-(F3[QH]), tn[QH][3], tn[QH][1]);                             \
     }                                                                                           \
   }
+// both passes of the next step's patches (the part's quad halves)
+#define W2R_XFORM(OUT, F0, F3, F2)                                                              \
+  {                                                                                             \
+    W2R_VERT(0, 0) W2R_VERT(0, 1)                                                               \
+    if constexpr (NQH == 2) { W2R_VERT(1, 0) W2R_VERT(1, 1) }                                   \
+    W2R_HORZ(0, 0, OUT, F0, F3, F2) W2R_HORZ(0, 1, OUT, F0, F3, F2)                             \
+    if constexpr (NQH == 2) { W2R_HORZ(1, 0, OUT, F0, F3, F2) W2R_HORZ(1, 1, OUT, F0, F3, F2) } \
+  }
   f32x2a rwa[2][2], rwb[2][2];
   const f32x2a sv2 = {sv, sv};
   f32x2a tp[2][2];                                  // (even W: the vertical pass as pairs (t0, t1), (t2, t3))
@@ -264,15 +297,15 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
   float vA[2][4], vB[2][4], tn[2][4];
 
   // ---- prologue: first item of the first tile (nothing to overlap with)
-  int tile = g;
+  int tile = SUB ? a.sub0 + g / NSUB : g;
   StageT st_cur = stage_setup(tile);
   ReadT rd_cur = read_setup(tile);
   {
-    const char* ab = reinterpret_cast<const char*>(a.wp) + ((long)((tile % a.gridy) * 2)) * 1024 + (long)ri * afrag;
+    const char* ab = reinterpret_cast<const char*>(a.wp) + ((long)((tile % a.gridy) * 2 + smt)) * 1024 + (long)ri * afrag;
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
       w2_load_a(au[s][0], aoff, ab + ((long)(s * 4)) * afrag);
-      w2_load_a(au[s][1], aoff, ab + ((long)(s * 4)) * afrag + 1024);
+      w2_load_a(au[s][1], aoff, ab + ((long)(s * 4)) * afrag + W2R_A1);
     }
     const char* p0 = plane0(st_cur, 0);
 #pragma unroll 1
@@ -294,9 +327,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
     const unsigned xb0[2] = {lds0 + (unsigned)rd_cur.bb[0] * 4u, lds0 + (unsigned)rd_cur.bb[1] * 4u};
     W2R_LOAD_RAW(xa0, xb0, 0)
     W2R_WAIT_RAW();
-    W2R_VERT(0, 0) W2R_VERT(0, 1) W2R_VERT(1, 0) W2R_VERT(1, 1)
-    W2R_HORZ(0, 0, vA, rd_cur.f0, rd_cur.f3, rd_cur.f2) W2R_HORZ(0, 1, vA, rd_cur.f0, rd_cur.f3, rd_cur.f2)
-    W2R_HORZ(1, 0, vA, rd_cur.f0, rd_cur.f3, rd_cur.f2) W2R_HORZ(1, 1, vA, rd_cur.f0, rd_cur.f3, rd_cur.f2)
+    W2R_XFORM(vA, rd_cur.f0, rd_cur.f3, rd_cur.f2)
   }
 
   int bufsel = 0;
@@ -309,8 +340,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
     const StageT st_nxt = last_tile ? st_cur : stage_setup(ntile);
     const ReadT rd_nxt = last_tile ? rd_cur : read_setup(ntile);
     cmp_setup(tile);
-    const char* abase_cur = reinterpret_cast<const char*>(a.wp) + ((long)((tile % a.gridy) * 2)) * 1024 + (long)ri * afrag;
-    const char* abase_nxt = reinterpret_cast<const char*>(a.wp) + ((long)((ntile % a.gridy) * 2)) * 1024 + (long)ri * afrag;
+    const char* abase_cur = reinterpret_cast<const char*>(a.wp) + ((long)((tile % a.gridy) * 2 + smt)) * 1024 + (long)ri * afrag;
+    const char* abase_nxt = reinterpret_cast<const char*>(a.wp) + ((long)((ntile % a.gridy) * 2 + smt)) * 1024 + (long)ri * afrag;
     float f0[2] = {rd_cur.f0[0], rd_cur.f0[1]}, f3[2] = {rd_cur.f3[0], rd_cur.f3[1]}, f2[2] = {rd_cur.f2[0], rd_cur.f2[1]};
     int last_cb = 0;
 
@@ -369,13 +400,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
       // the NEXT item (buffer nb, the next tile's geometry at a tile wrap).
 #define W2R_SLOT(STEP, K, VC, VN)                                                                                  \
   {                                                                                                                \
-    acc[K] = __builtin_amdgcn_mfma_f32_32x32x2f32(au[STEP][(K) >> 3][(K) & 3], VC[((K) >> 2) & 1][(K) & 3], acc[K], 0, 0, 0); \
+    if constexpr (((K) >> 3) < NMT && (((K) >> 2) & 1) < NQH)                                                      \
+      acc[K] = __builtin_amdgcn_mfma_f32_32x32x2f32(au[STEP][(K) >> 3][(K) & 3], VC[((K) >> 2) & 1][(K) & 3], acc[K], 0, 0, 0); \
     if ((K) == 0 && (STEP) < 5) W2R_LOAD_RAW(xa, xb, (STEP) + 1)                                                   \
     if ((K) == 0 && (STEP) == 5) W2R_LOAD_RAW(xan, xbn, 0)                                                         \
     W2R_XF_SLOTS(STEP, K, VN)                                                                                      \
     if (((K) & 3) == 0 && (STEP) < 3) W2R_STAGE_ADDR((STEP) * 4 + ((K) >> 2))                                      \
     if (((K) & 3) == 1 && (STEP) < 3) W2R_ABL_STAGE((STEP) * 4 + ((K) >> 2))                                       \
-    if ((K) >= 14) W2R_ABL_LOADA(au[STEP][(K) & 1], aoff, anext + (long)((STEP) * 4) * afrag + ((K) & 1) * 1024);  \
+    if ((K) >= 14) W2R_ABL_LOADA(au[STEP][(K) & 1], aoff, anext + (long)((STEP) * 4) * afrag + ((K) & 1) * W2R_A1);  \
     __builtin_amdgcn_sched_barrier(0);                                                                             \
   }
 // the transform of the next step's patches as ONE group in slot 4 (the LDS reads of slot 0 have had four MFMAs to land): beside
@@ -384,9 +416,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
 #define W2R_XF_SLOTS(STEP, K, VN)                                                                                  \
     if ((K) == 4) {                                                                                                \
       W2R_WAIT_RAW();                                                                                              \
-      W2R_VERT(0, 0) W2R_VERT(0, 1) W2R_VERT(1, 0) W2R_VERT(1, 1)                                                  \
-      if ((STEP) < 5) { W2R_HORZ(0, 0, VN, f0, f3, f2) W2R_HORZ(0, 1, VN, f0, f3, f2) W2R_HORZ(1, 0, VN, f0, f3, f2) W2R_HORZ(1, 1, VN, f0, f3, f2) } \
-      else { W2R_HORZ(0, 0, VN, nf0, nf3, nf2) W2R_HORZ(0, 1, VN, nf0, nf3, nf2) W2R_HORZ(1, 0, VN, nf0, nf3, nf2) W2R_HORZ(1, 1, VN, nf0, nf3, nf2) } \
+      if ((STEP) < 5) W2R_XFORM(VN, f0, f3, f2)                                                                    \
+      else W2R_XFORM(VN, nf0, nf3, nf2)                                                                            \
     }
 #define W2R_STEP(STEP, NWAIT, VC, VN)                                                                              \
   {                                                                                                                \
@@ -413,6 +444,15 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
 #undef W2R_SLOT
 #undef W2R_STAGE
 #undef W2R_STAGE_ADDR
+    }
+    if constexpr (SUB != 0) {
+      // One tile per workgroup: no tile loop keeps the ring's registers reserved through the epilogue, while the U loads that the
+      // last item issued for an item that never comes are still in flight - they have to land before their registers are reused
+      asm volatile("s_waitcnt vmcnt(0)"
+                   : "+v"(au[0][0]), "+v"(au[0][1]), "+v"(au[1][0]), "+v"(au[1][1]), "+v"(au[2][0]), "+v"(au[2][1]),
+                     "+v"(au[3][0]), "+v"(au[3][1]), "+v"(au[4][0]), "+v"(au[4][1]), "+v"(au[5][0]), "+v"(au[5][1])
+                   :
+                   : "memory");
     }
 
     // ---- tile complete.  Every wave holds ROW ri of the 4 x 4 points of all four blocks; the output transform needs the four
@@ -474,7 +514,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
       for (int blk = 0; blk < 4; ++blk) {
         const int bmt = blk & 1, bqh = blk >> 1;
         const int a0 = (bmt * 2 + bqh) * 4;
-        if (blk != wave) {
+        if (bmt < NMT && bqh < NQH && blk != wave) {   // (SUB: the part's blocks only)
           const int ridx = wave * 3 + (blk > wave ? blk - 1 : blk);
           float* rg = xs + (ridx < 6 ? last_cb : third) * BUFF + (ridx < 6 ? ridx : ridx - 6) * 2048 + lane * 4;
 #pragma unroll
@@ -589,6 +629,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+#undef W2R_XFORM
 #undef W2R_HORZ
 #undef W2R_VERT
 #undef W2R_LOAD_RAW
@@ -598,3 +639,4 @@ __global__ __launch_bounds__(256, 1) void conv_wino2r_kernel(const Wino2Args a) 
 #undef W2R_RA
 #undef W2R_RB
 #undef W2R_WAIT_A
+#undef W2R_A1

@@ -73,6 +73,12 @@ int hpvg_conv_fwd_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, in
  * the direct matrix-core work), 2 Winograd F(2x2,3x3) (4/9), 3 narrow-output kernel (Cout <= 4).  bench.py prices the
  * roofline's executed flops with it. */
 int hpvg_conv_fwd_kernel_kind(int B, int Cin, int Cout, int T, int H, int W, int KT);
+/* host only: how a kind-2 launch of this shape is cut (any other shape: HPVG_ERR_UNSUPPORTED).  The two-axis kernel runs
+ * rounds of 256 whole tiles; the tiles of a last round that is at most half full (after at least one full round) run in a
+ * second launch as half tiles (2 per tile) or, up to 64 of them, quarter tiles (4 per tile), one per workgroup, with the same
+ * bits as whole tiles (HPVG_W2_SPLIT=0: never).  out[0..3] = tiles of the whole-tile launch, leftover tiles, parts per
+ * leftover tile (1 = not cut, 2, 4), workgroups of the second launch (0 when not cut). */
+int hpvg_conv_w2_split(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out4);
 /* Wide layers (kernel view Cin >= 8, Cout > 32) have a second kernel behind the same entry points: Winograd F(2,3) along W
  * (four products per output pair and (dt, dh) instead of six, summed over the channels before the output transform: 2/3 of
  * the matrix-core work; fp32, ~1e-6 of the output scale away from the direct kernel).  The weight pack carries both forms;

@@ -1118,3 +1118,6 @@ int hpvg_nnf_chunks_i32(const int* nn, const int* d2, int max_d2, const int* qgr
 
 // evaluate --prdc: the self k-nearest search and the ball count, two more epilogues on the tile above
 #include "patchnn_prdc.inl"
+
+// generate_patchnn --search patchmatch: the deterministic approximate search (its own kernel; shares the geometry above)
+#include "patchmatch.inl"

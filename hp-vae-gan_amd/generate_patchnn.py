@@ -1,7 +1,8 @@
 """`python -m hp_vae_gan_amd.generate_patchnn --exp-dir run/<clip>/<checkname>/experiment_<n>` (or `--video-path clip.npy --out
 dir`, `--image-path img.png --out dir`): training-free samples of the clip by coarse-to-fine patch nearest neighbours (GPNN /
 VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json.  With `--mask hole.npy` the samples are completions of
-the masked region of the clip (patch inpainting) and every other voxel stays as it is."""
+the masked region of the clip (patch inpainting) and every other voxel stays as it is.  With `--search patchmatch` the levels
+above the coarsest search by a deterministic PatchMatch (linear in the patch count) instead of exhaustively."""
 import argparse
 import json
 import math
@@ -23,6 +24,11 @@ from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_
 # not built), every level repeats one step: search, for each patch of the current guess, the key patch that minimises
 # d2 / (alpha_abs + the key's distance to ITS nearest guess patch) (the completeness normalisation: key patches the guess
 # does not use yet become cheap), then vote the value patches of the winners into the next guess.
+PM_ITERS = 4        # --pm-iters: a warm-started search at the finest level is within 1.05 of the exact mean d2 after 4
+PM_FROM_LEVEL = 1   # --pm-from-level
+PM_SEED_STRIDE = 1000003
+
+
 def generate_patchnn_parser():
     def alpha(s):
         v = float(s)
@@ -53,6 +59,13 @@ def generate_patchnn_parser():
                    '(T, H, W) (.npy [T,H,W] / [H,W] bool or uint8, or [...,3], an image file or a frame directory; nonzero = hole). '
                    'Only patches that overlap the hole are searched, only patches that avoid it answer, and voxels outside the '
                    'hole are kept; the search is the plain nearest neighbour (--alpha is not used)')
+    p.add_argument('--search', choices=('exact', 'patchmatch'), default='exact', help='exact: every step searches all keys '
+                   '(quadratic in the patch count); patchmatch: from --pm-from-level on, the deterministic PatchMatch '
+                   '(linear in the patch count), started from the previous step\'s field')
+    p.add_argument('--pm-iters', type=int, default=None, help='PatchMatch iterations per search (default %d); only with '
+                   '--search patchmatch' % PM_ITERS)
+    p.add_argument('--pm-from-level', type=int, default=None, help='first pyramid level searched by PatchMatch, >= 1 (default %d; '
+                   'level 0 is always exact); only with --search patchmatch' % PM_FROM_LEVEL)
     return p
 
 
@@ -104,16 +117,73 @@ def patchnn_weights(m, alpha_abs):
     return 1.0 / (m.to(torch.float32) + torch.tensor(alpha_abs, dtype=torch.float32, device=m.device))
 
 
-def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False):
+def patchnn_field_resize(nn, qgrid_from, rgrid_from, qgrid_to, rgrid_to):
+    """A nearest-neighbour field carried to another pair of dense patch grids, in integer arithmetic (torch, any device).  nn: an
+    integer tensor with prod(qgrid_from) entries, indices into the key grid rgrid_from (clamped into it).  Per axis, target
+    query coordinate a (grid side Gt) reads the source (side Gf) at (2 a (Gf - 1) + (Gt - 1)) // (2 (Gt - 1)) - the nearest
+    source coordinate under the align-corners map, halves up; 0 when Gt = 1 - and the key coordinate b' found there (side Kf)
+    becomes (2 b' (Kt - 1) + (Kf - 1)) // (2 (Kf - 1)) in the target key grid (side Kt; 0 when Kf = 1).  Returns int32 shaped
+    qgrid_to."""
+    qf, rf, qt, rt = (tuple(int(e) for e in g) for g in (qgrid_from, rgrid_from, qgrid_to, rgrid_to))
+    if any(len(g) != 3 or min(g) < 1 for g in (qf, rf, qt, rt)) or nn.numel() != qf[0] * qf[1] * qf[2]:
+        raise ValueError("patchnn_field_resize: grids of 3 sides >= 1 and a field of prod(qgrid_from) entries, got %s %s %s %s, %d"
+                         % (qf, rf, qt, rt, nn.numel()))
+    dev = nn.device
+    src = nn.reshape(qf).to(torch.int64).clamp(0, rf[0] * rf[1] * rf[2] - 1)
+    for axis in range(3):
+        a = torch.arange(qt[axis], dtype=torch.int64, device=dev)
+        idx = (2 * a * (qf[axis] - 1) + (qt[axis] - 1)) // (2 * (qt[axis] - 1)) if qt[axis] > 1 else torch.zeros_like(a)
+        src = src.index_select(axis, idx)
+    b = [src // (rf[1] * rf[2]), (src // rf[2]) % rf[1], src % rf[2]]
+    for axis in range(3):
+        b[axis] = (2 * b[axis] * (rt[axis] - 1) + (rf[axis] - 1)) // (2 * (rf[axis] - 1)) if rf[axis] > 1 else torch.zeros_like(b[axis])
+    return ((b[0] * rt[1] + b[1]) * rt[2] + b[2]).to(torch.int32).contiguous()
+
+
+def patchnn_search_state(seed=0, index=0):
+    """What the PatchMatch steps of one sample carry from step to step: `fwd` (guess -> keys) and `rev` (keys -> guess), the
+    kept int32 fields (None: not known yet, the search starts from the hash), and the seed rule: PatchMatch search number n of
+    the sample (0-based, in launch order: a step's reverse search comes before its forward search) runs under the seed
+    (seed + index) * 1000003 + n."""
+    return {"fwd": None, "rev": None, "base": (int(seed) + int(index)) * PM_SEED_STRIDE, "count": 0}
+
+
+def _next_seed(state):
+    s = state["base"] + state["count"]
+    state["count"] += 1
+    return s
+
+
+def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, search='exact', pm_iters=PM_ITERS,
+                   pm_from_level=PM_FROM_LEVEL, level=None, state=None):
     """One GPNN step on uint8 volumes (or images): m = for every key patch the distance to its nearest query patch,
     w = 1 / (float32(m) + float32(alpha_abs)), nn = the weighted nearest key of every query patch, result = the vote of the
     value patches nn (keys and values share one grid) with the query as fallback.  alpha_abs = inf: the plain nearest key,
-    one search.  return_score: also the mean of the minimised quantity (d2 * w; d2 for inf)."""
-    if math.isinf(alpha_abs):
+    one search.  return_score: also the mean of the minimised quantity (d2 * w; d2 for inf).
+    search = 'patchmatch' (and level None or >= max(pm_from_level, 1); below that the step is the exact one): both searches are
+    ops.patch_match with pm_iters iterations - m is the d2 of patch_match(keys, query) started from state['rev'], the forward
+    search is patch_match(query, keys, ref_weight=w) started from state['fwd'] - each under its own seed
+    (patchnn_search_state).  state: that dict, updated in place with the fields of this step's searches, exact ones included
+    (None: a fresh one, i.e. hash starts under seeds 0 and 1)."""
+    if search not in ("exact", "patchmatch"):
+        raise ValueError("patchnn_refine: search must be 'exact' or 'patchmatch', got %r" % (search,))
+    pm = search == "patchmatch" and (level is None or int(level) >= max(int(pm_from_level), 1))
+    if pm and state is None:
+        state = patchnn_search_state()
+    rev = None
+    if pm:
+        if math.isinf(alpha_abs):
+            score, nn = ops.patch_match(query, keys, patch, pm_iters, _next_seed(state), None, state["fwd"])
+        else:
+            m, rev = ops.patch_match(keys, query, patch, pm_iters, _next_seed(state), None, state["rev"])
+            score, nn = ops.patch_match(query, keys, patch, pm_iters, _next_seed(state), patchnn_weights(m, alpha_abs), state["fwd"])
+    elif math.isinf(alpha_abs):
         score, nn = ops.patch_nn(query, keys, patch)
     else:
-        m, _ = ops.patch_nn(keys, query, patch)
+        m, rev = ops.patch_nn(keys, query, patch)
         score, nn = ops.patch_nn_weighted(query, keys, patchnn_weights(m, alpha_abs), patch)
+    if state is not None:
+        state["fwd"], state["rev"] = nn, rev
     out = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query)
     if return_score:
         return out, float(score.to(torch.float64).mean())
@@ -121,13 +191,17 @@ def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False):
 
 
 def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, alpha=0.005, seed=0, index=0,
-                       pyramid=None):
+                       pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL):
     """One sample of the uint8 device volume `real` ([T,H,W,3]; images [H,W,3]) -> (sample, mean final score).  size: the
     sample's (T, H, W) (default real's).  The coarsest guess is real level 0 (resized to the sample's coarsest size) plus
     noise * 255 * N(0, 1) drawn under torch.manual_seed(seed + index); level 0 runs `iters` steps with keys = values = real
     level 0; level l > 0 starts from the previous result resized, runs one step with the blurred keys (real level l-1 resized
     to level l) and values real level l, then iters - 1 steps with keys = values = real level l.  pyramid: a
-    (sizes, levels, keys) triple of patchnn_pyramid_sizes / patchnn_real_levels to reuse between samples."""
+    (sizes, levels, keys) triple of patchnn_pyramid_sizes / patchnn_real_levels to reuse between samples.
+    search = 'patchmatch': the steps of level max(pm_from_level, 1) and above search by PatchMatch (patchnn_refine) with
+    pm_iters iterations, each started from the previous step's fields; between levels both fields go through
+    patchnn_field_resize (the guess's and the keys' grids may differ: retargeting).  Seeds: patchnn_search_state(seed, index).
+    The default 'exact' computes what it always did."""
     image = real.dim() == 3
     vol = real[None] if image else real
     patch = tuple(patch) if patch else default_patch(not image)
@@ -152,13 +226,22 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
         with ops.noise_stream(q.device):
             z = ops.normal_(torch.empty(q.shape, dtype=torch.float32, device=q.device))
         q = torch.round(q.to(torch.float32) + (float(noise) * 255.0) * z).clamp_(0, 255).to(torch.uint8)
+    state = patchnn_search_state(seed, index) if search == "patchmatch" else None
     score = None
     for l in range(L):
         if l > 0:
             q = _resize_u8(q, qsizes[l])
+            if state is not None:
+                qf, qt = (tuple(s - p + 1 for s, p in zip(qsizes[k], patch)) for k in (l - 1, l))
+                rf, rt = (tuple(s - p + 1 for s, p in zip(sizes[k], patch)) for k in (l - 1, l))
+                if state["fwd"] is not None:
+                    state["fwd"] = patchnn_field_resize(state["fwd"], qf, rf, qt, rt)
+                if state["rev"] is not None:
+                    state["rev"] = patchnn_field_resize(state["rev"], rf, qf, rt, qt)
         for it in range(iters):
             k = keys[l] if (l > 0 and it == 0) else levels[l]
-            q, score = patchnn_refine(q, k, levels[l], patch, alpha_abs, return_score=True)
+            q, score = patchnn_refine(q, k, levels[l], patch, alpha_abs, return_score=True, search=search, pm_iters=pm_iters,
+                                      pm_from_level=pm_from_level, level=l, state=state)
     return (q[0] if image else q), score
 
 
@@ -321,12 +404,29 @@ def _refuse_trivial_mask(forms):
 
 
 def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
-                     min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None):
+                     min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None, search='exact',
+                     pm_iters=None, pm_from_level=None):
     """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
     patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample).  mask: the
     path of a hole mask of the real volume; the samples are then completions of the hole (patchnn_inpaint), land in
     <exp-dir>/eval/samples_patchinpaint by default, and patchnn.json also records the mask, its voxels and per level the query
-    and key patches."""
+    and key patches.  search = 'patchmatch': patchnn_synthesize's PatchMatch steps, with pm_iters (default 4) iterations per
+    search from level pm_from_level (default 1) on; patchnn.json then also records search, pm_iters and pm_from_level.  Not
+    with a mask (the subset search has no PatchMatch form), and the two pm_* settings only with it."""
+    if search not in ("exact", "patchmatch"):
+        raise SystemExit("generate_patchnn: --search must be exact or patchmatch, got {!r}".format(search))
+    if search == "exact" and (pm_iters is not None or pm_from_level is not None):
+        raise SystemExit("generate_patchnn: --pm-iters and --pm-from-level need --search patchmatch")
+    if search == "patchmatch":
+        if mask is not None:
+            raise SystemExit("generate_patchnn: --mask searches a subset of the patches, which --search patchmatch does not do; "
+                             "use --search exact")
+        pm_iters = PM_ITERS if pm_iters is None else int(pm_iters)
+        pm_from_level = PM_FROM_LEVEL if pm_from_level is None else int(pm_from_level)
+        if not 0 <= pm_iters <= 1024:
+            raise SystemExit("generate_patchnn: --pm-iters must lie in [0, 1024], got {}".format(pm_iters))
+        if pm_from_level < 1:
+            raise SystemExit("generate_patchnn: --pm-from-level must be >= 1 (level 0 is always exact), got {}".format(pm_from_level))
     given = [a for a in (exp_dir, video_path, image_path) if a is not None]
     if len(given) != 1:
         raise SystemExit("generate_patchnn: give exactly one of --exp-dir, --video-path and --image-path")
@@ -388,7 +488,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
             if mask is not None:
                 smp, score = patchnn_inpaint(vol, hole, patch, ratio, min_size, iters, noise, seed, i, pyramid)
             else:
-                smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid)
+                pm = {"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level} if search == "patchmatch" else {}
+                smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid, **pm)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
         e1.record()
@@ -408,6 +509,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         info.update({"mask": os.path.abspath(mask), "hole_voxels": int(hole.sum()), "alpha": "inf",
                      "active_patches": [int(lv["qsel"].numel()) for lv in pyramid[3]],
                      "valid_keys": [int(lv["rsel"].numel()) for lv in pyramid[3]]})
+    if search == "patchmatch":
+        info.update({"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level})
     with open(os.path.join(out, 'patchnn.json'), 'w') as f:
         json.dump(info, f, indent=1, sort_keys=True)
     print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
@@ -418,7 +521,7 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
 def main(argv=None):
     a = generate_patchnn_parser().parse_args(argv)
     generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
-                     a.alpha, a.noise, a.size, a.save_levels, a.mask)
+                     a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level)
     return 0
 
 

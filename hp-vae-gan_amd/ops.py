@@ -1388,6 +1388,52 @@ def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rs
     return score, nn
 
 
+def patch_match(query_u8, ref_u8, patch, iters, seed=0, ref_weight=None, nn_init=None):
+    """Deterministic PatchMatch (hpvg_patchmatch_u8): an approximate nearest-neighbour field between the dense patch grids of two
+    uint8 device tensors [T,H,W,3] or [H,W,3], at a cost linear in the number of patches.  The rule - hash start or nn_init,
+    `iters` Jacobi iterations of propagation and a shrinking random search, keys (d2, j) or (float32(d2) * ref_weight[j], j) -
+    is written out in include/hpvg.h; a seed gives the same field on every run.  ref_weight: as for patch_nn_weighted.
+    nn_init: int32 device tensor with the query grid's element count (entries are clamped into the key grid).  Returns
+    (d2 int32, nn int32), or (score float32, nn int32) with weights, shaped as the query's patch grid."""
+    (q, r), image = _patch_volumes("patch_match", (("query", query_u8), ("ref", ref_u8)))
+    pa, one = _triple(patch, "patch", "patch_match"), _triple((1, 1, 1), "stride", "patch_match")
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *qg, *rg, pa, one, one, counts)   # refuses bad arguments by name
+    Nq, Nr = counts[0], counts[1]
+    grid = tuple(qg[a] - pa[a] + 1 for a in range(3))
+    rgrid = tuple(rg[a] - pa[a] + 1 for a in range(3))
+    w = ref_weight
+    if w is not None:
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != r.device or \
+                tuple(w.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
+            raise RuntimeError("patch_match: ref_weight must be float32 [%d] or %s on %s, got %s %s on %s"
+                               % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(w, "dtype", type(w)),
+                                  tuple(getattr(w, "shape", ())), getattr(w, "device", None)))
+        w = _c(w)
+        if not bool((torch.isfinite(w) & (w > 0)).all()):   # one device reduction
+            raise RuntimeError("patch_match: every ref_weight must be finite and > 0")
+    if nn_init is not None:
+        if not isinstance(nn_init, torch.Tensor) or nn_init.dtype != torch.int32 or nn_init.numel() != Nq or nn_init.device != q.device:
+            raise RuntimeError("patch_match: nn_init must be int32 with %d entries on %s, got %s %s on %s"
+                               % (Nq, q.device, getattr(nn_init, "dtype", type(nn_init)), tuple(getattr(nn_init, "shape", ())),
+                                  getattr(nn_init, "device", None)))
+        nn_init = _c(nn_init)
+    nbytes = call("hpvg_patchmatch_ws_bytes", *qg, *rg, pa)
+    if nbytes == 0 or not 0 <= int(iters) <= 1024:
+        raise RuntimeError("patch_match: refused (a patch grid side >= 65536, or iters %r outside [0, 1024])" % (iters,))
+    ws = _scratch(nbytes, q.device)
+    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
+    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
+    score = torch.empty(grid, dtype=torch.float32, device=q.device) if w is not None else None
+    call("hpvg_patchmatch_u8", ptr(q), *qg, ptr(r), *rg, pa, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2), ptr(nn), ptr(score),
+         *ws, stream())
+    out = score if w is not None else d2
+    if image:
+        out, nn = out[0], nn[0]
+    return out, nn
+
+
 def _patch_sel(sel, name, N, device):
     """A subset search's list as launch arguments (pointer, count, the tensor kept alive); None is the whole grid.  Checked on
     the device with one reduction: int32, 1-D, non-empty, strictly ascending, within [0, N)."""

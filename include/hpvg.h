@@ -314,6 +314,36 @@ int hpvg_patchnn_subset_u8(const unsigned char* q, int Tq, int Hq, int Wq, const
  * 0 for a patch that avoids the hole.  Geometry refusals as for hpvg_patchnn_u8; no workspace. */
 int hpvg_patch_mask_count_u8(const unsigned char* mask, int T, int H, int W, const int* patch, const int* stride, int* count,
                              void* stream);
+/* Deterministic PatchMatch (Barnes et al. 2009; generate_patchnn --search patchmatch): an APPROXIMATE nearest-neighbour field
+ * whose cost is linear in the number of patches, defined bit for bit.  Volumes as for hpvg_patchnn_u8; both patch grids are
+ * dense (stride 1), raster order (t, y, x); qg = (gT, gH, gW) is the query grid, rg = (kT, kH, kW) the key grid,
+ * Nq = gT gH gW, Nr = kT kH kW, D = 3 patch[0] patch[1] patch[2].
+ *   Key of a pair (i, j): (d2_ij, j), or (float32(d2_ij) * rweight[j], j) with weights; d2_ij is the exact int32 squared
+ * distance (converted round-to-nearest-even, one fp32 multiply).  Keys compare lexicographically, and a candidate replaces the
+ * running best only when its key is STRICTLY smaller.
+ *   h32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16, on 32 bits.
+ *   rnd(i, it, k, ax) = h32(seed + i * 0x9E3779B9 + (it * 64 + k * 4 + ax) * 0x85EBCA6B), everything mod 2^32 (seed too);
+ * i = the flat query index, ax = 0, 1, 2 for t, y, x.
+ *   Start: with nn_init (int32 [Nq] on the device) every entry clamped into [0, Nr); without it the key coordinate along ax is
+ * rnd(i, 0xFFFFFF, 0, ax) % rg[ax].  iters = 0 returns the scored start.
+ *   Iteration it = 0 .. iters - 1 reads ONLY the field of the previous iteration (Jacobi).  For the query patch at grid
+ * coordinate a, starting from its own old match as the running best, in this order:
+ *   1. propagation: for ax = t, y, x and s = -1 then +1: if a + s e_ax lies in the query grid, the candidate is the key
+ *      coordinate of that neighbour's old match minus s e_ax; it is skipped when it leaves the key grid;
+ *   2. random search: R = max(kT, kH, kW); for k = 0, 1, ... while r_k = R >> k >= 1 the candidate is the running best's key
+ *      coordinate plus, per axis, rnd(i, it, k, ax) % (2 r_k + 1) - r_k, each axis clamped into the key grid.
+ * So a patch's key never increases from one iteration to the next.  d2 / nn: int32 [Nq], the final field's exact distance and
+ * index; score: float [Nq] = float32(d2) * rweight[nn], NULL without weights (and optional with them).  The result depends on
+ * the arguments only - not on launch geometry, stream or timing - and no index leaves [0, Nr).  Weights: the contract of
+ * hpvg_patchnn_weighted_u8 (finite, positive, normal products).  One launch for the start and one per iteration on `stream`,
+ * two field buffers in the workspace, no host synchronisation, capturable.
+ * HPVG_ERR_ARG: the geometry refusals of hpvg_patchnn_u8, a grid side >= 65536, iters outside [0, 1024], score without rweight,
+ * a null q, r, d2 or nn.  HPVG_ERR_WORKSPACE: ws null, not 16-byte aligned or shorter than hpvg_patchmatch_ws_bytes(). */
+/* host only: bytes of workspace (two fields of nn, d2 and score); 0 for a geometry hpvg_patchmatch_u8 refuses */
+size_t hpvg_patchmatch_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch);
+int hpvg_patchmatch_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                       const int* patch, const float* rweight, const int* nn_init, int iters, long seed, int* d2, int* nn,
+                       float* score, void* ws, size_t ws_bytes, void* stream);
 /* The copied regions ("chunks") of a nearest-neighbour field (evaluate --chunks).  nn: int32 [Nq] on the device over the query
  * patch grid qgrid = (gT, gH, gW), raster order (t, y, x), holding indices into the key patch grid rgrid = (kT, kH, kW),
  * Nr = kT kH kW; d2: int32 [Nq] or NULL.  qgrid / rgrid / qstride / rstride: host arrays of 3 ints.  Patch i at grid coordinate

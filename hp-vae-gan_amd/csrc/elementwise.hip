@@ -1348,6 +1348,17 @@ int hpvg_bn_plan(int B, int C, long S, int groups, int* out3) {
   return HPVG_OK;
 }
 
+// host only: the vector width (4, 2, 1 floats per load) the per-channel reductions pick for rows of S floats that start at p
+// (hpvg_vec_width), and for `groups` groups of B / groups samples that start at p (bn_vec_width); p is never dereferenced
+int hpvg_vec_width_at(const void* p, long S) {
+  if (S < 1) return HPVG_ERR_ARG;
+  return hpvg_vec_width(p, S);
+}
+int hpvg_bn_vec_width_at(const void* p, int B, int C, long S, int groups) {
+  if (B < 1 || C < 1 || S < 1 || groups < 1 || B % groups) return HPVG_ERR_ARG;
+  return bn_vec_width(p, B, C, S, groups);
+}
+
 // second-order backward of h = LeakyReLU_opt(BN_train(r)) (see bn_lrelu_bwd2_reduce_kernel): g = dL/d(dr) of the first-order
 // backward; outputs (each optional): g_dh = dL/d(dh), g_r = dL/d(r), g_gamma = dL/d(gamma) (+= when accumulate).
 size_t hpvg_bn_bwd2_ws_bytes(int C) { return (size_t)C * 64 * 5 * sizeof(double) + (size_t)C * 5 * sizeof(float); }

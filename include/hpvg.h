@@ -12,6 +12,14 @@
  *   - pointers are DEVICE pointers unless stated; the caller owns every buffer, including workspace;
  *   - never allocates, never synchronises, never throws; work is enqueued on `stream` (a hipStream_t);
  *   - returns 0 (HPVG_OK) or a negative error code.
+ *
+ * Alignment and extent: an fp32 or int32 tensor argument (activations, weights, gradients, statistics, mask words, outputs)
+ * needs 4-byte alignment only - a view that starts anywhere inside a larger buffer (x[n:], out[o:o+n]) is a valid argument.
+ * Where a kernel has a wider load or store form, the launch picks it from the pointer value and the sizes and falls back to
+ * the narrower form otherwise (hpvg_vec_width_at); the result does not depend on the start except through that choice.
+ * Workspaces (`ws`) need 16-byte alignment, as stated per function.  A launch reads and writes nothing outside [p, p + n) of
+ * any tensor argument of n elements: no whole-vector overrun past the last row or plane, before the first, or into the
+ * bytes an allocator leaves behind a tensor (tests/test_offset_launches.py runs every launch inside guard bands).
  */
 #ifndef HPVG_H
 #define HPVG_H
@@ -158,6 +166,12 @@ int hpvg_bn_act_bwd_f32(const float* dh, const float* r, const float* mean, cons
  * folded into the apply kernel (two launches for all groups; else three per group), out[1] = partial blocks per channel
  * and group, out[2] = vector width (floats per load) of the reduction kernels */
 int hpvg_bn_plan(int B, int C, long S, int groups, int* out3);
+/* host only: the vector width (4, 2 or 1 floats per load) the per-channel reductions - the BatchNorm family and
+ * hpvg_channel_sum_f32 - pick for rows of S floats that start at address p: 4 needs p % 16 == 0 and S % 4 == 0, 2 needs
+ * p % 8 == 0 and S % 2 == 0.  A launch over several tensors takes the narrowest of them.  _bn_: the narrowest over the
+ * starts of `groups` groups of B / groups samples.  p is only looked at, never dereferenced. */
+int hpvg_vec_width_at(const void* p, long S);
+int hpvg_bn_vec_width_at(const void* p, int B, int C, long S, int groups);
 /* SECOND-order backward of the same block: the WGAN-GP of a critic that contains BatchNorm (WDiscriminatorBaselines,
  * networks_3d.py:184-210; modules/utils.py:14-18) differentiates the first-order backward once more.  g = dL/d(dr);
  * outputs (each nullable): g_dh = dL/d(dh), g_r = dL/d(r), g_gamma = dL/d(gamma) (+= when accumulate).  torch:

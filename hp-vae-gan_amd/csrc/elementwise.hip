@@ -1123,6 +1123,36 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 __global__ void counter_inc_kernel(int* c) { if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += 1; }
 
+// State digest (snapshot.py): acc[0] += sum_i fmix(((salt + i) * golden) ^ word[i]) mod 2^64, fmix = the splitmix64 finaliser.
+// A sum of position-keyed hashes: commutative, so exact whatever the launch geometry and the order of the atomics.  `head`
+// words (< 4) precede the first 16-byte boundary, nvec uint4 groups follow, then the last n - head - 4 nvec words (< 4).
+__device__ __forceinline__ unsigned long long digest_term(unsigned long long pos, unsigned int word) {
+  unsigned long long z = (pos * 0x9E3779B97F4A7C15ull) ^ (unsigned long long)word;
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void state_digest_kernel(const unsigned int* __restrict__ w, long n, int head, long nvec,
+                                                            unsigned long long salt, unsigned long long* __restrict__ acc) {
+  __shared__ unsigned long long sh[4];
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  unsigned long long part = 0;
+  if (gid < head) part += digest_term(salt + (unsigned long long)gid, w[gid]);
+  const long tail0 = head + 4 * nvec;
+  if (gid < n - tail0) part += digest_term(salt + (unsigned long long)(tail0 + gid), w[tail0 + gid]);
+  const uint4* __restrict__ v = reinterpret_cast<const uint4*>(w + head);
+  for (long g = gid; g < nvec; g += (long)gridDim.x * 256) {
+    const uint4 q = v[g];
+    const unsigned long long p0 = salt + (unsigned long long)(head + 4 * g);
+    part += digest_term(p0, q.x) + digest_term(p0 + 1, q.y) + digest_term(p0 + 2, q.z) + digest_term(p0 + 3, q.w);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
+}
+
 inline int ew_blocks(long n) {
   long nb = (n + 256 * 4 - 1) / (256 * 4);
   if (nb < 1) nb = 1;
@@ -1731,6 +1761,21 @@ int hpvg_adam_step_f32(float* p, const float* g, float* m, float* v, long n, flo
 int hpvg_counter_inc_i32(int* counter, void* stream) {
   if (!counter) return HPVG_ERR_ARG;
   hipLaunchKernelGGL(counter_inc_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter);
+  return hpvg_launch_status();
+}
+// acc[0] += digest of the n 32-bit words at `words` (any 4-byte offset) keyed by their positions salt, salt + 1, ...
+int hpvg_state_digest_u32(const void* words, long n, unsigned long long salt, unsigned long long* acc, void* stream) {
+  if (n < 0 || !acc || (n > 0 && !words) || ((size_t)words & 3)) return HPVG_ERR_ARG;
+  if (n == 0) return HPVG_OK;
+  long head = (long)(((16 - ((size_t)words & 15)) & 15) >> 2);
+  if (head > n) head = n;
+  const long nvec = (n - head) / 4;
+  // 8 groups of 16 bytes per lane and round; at least one workgroup for the head and tail words
+  long nb = (nvec + 256 * 8 - 1) / (256 * 8);
+  if (nb < 1) nb = 1;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(state_digest_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)words, n,
+                     (int)head, nvec, salt, acc);
   return hpvg_launch_status();
 }
 

@@ -1286,6 +1286,30 @@ def counter_inc_(counter):
     call("hpvg_counter_inc_i32", ptr(counter), stream())
 
 
+def state_digest_(t, salt, acc):
+    """acc[0] (int64 device word) += the digest of t's 32-bit words keyed from position `salt` (hpvg_state_digest_u32);
+    returns the number of words.  4-byte and 8-byte dtypes; an 8-byte element counts as two words, low word first."""
+    if t.element_size() not in (4, 8):
+        raise RuntimeError("state_digest: 4-byte and 8-byte dtypes only, got %s" % t.dtype)
+    t = _c(t.detach())
+    n = t.numel() * (t.element_size() // 4)
+    call("hpvg_state_digest_u32", ptr(t) if n else None, n, int(salt) & 0xFFFFFFFFFFFFFFFF, ptr(acc), stream())
+    return n
+
+
+def state_digest(tensors):
+    """64-bit digest (a python int) of the device tensors' bits, in order: each tensor's salt is the number of words digested
+    before it, so the result is that of one call over their concatenation.  Reading the result synchronises the stream."""
+    tensors = list(tensors)
+    if not tensors:
+        return 0
+    acc = torch.zeros(1, dtype=torch.int64, device=tensors[0].device)
+    salt = 0
+    for t in tensors:
+        salt += state_digest_(t, salt, acc)
+    return int(acc.item()) & 0xFFFFFFFFFFFFFFFF
+
+
 # ------------------------------------------------------------------------------------------ the programs' outputs
 def video_to_u8(x):
     """fp32 [B][C][T][H][W] (or an image batch [B][C][H][W]) -> uint8 [B][T][H][W][C] (images: [B][H][W][C]) with write_video's

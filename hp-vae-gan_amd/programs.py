@@ -37,6 +37,16 @@ weights and Noise_Amps, and the loop trains the saved scale AGAIN.  Its iteratio
 (train_video.py:131-145), so Noise_Amps ends one entry longer than the number of scales - the reference's quirk, kept like
 the others.  The optimizer state is not restored (neither does the reference).
 
+Snapshots (snapshot.py; this project's own): --snapshot-interval K writes <experiment>/snapshot.pth after every K-th iteration
+of a stage (3 <= k < niter, after the iteration's preview and drain) and after every stage's checkpoints; --snapshot-exit-after
+N ends the process cleanly after the N-th; --resume EXP_DIR continues that run in its directory.  The three flags are added on
+top of build_parser's (Program.parser) and settled before the device is asked for (snapshot.resolve); they are no settings of
+the experiment and stay out of opt.json.  A resume runs this same setup from the command line the snapshot recorded (seed
+included), appends to scalars.jsonl (cut back to the recorded length) and logbook.txt, leaves opt.json alone, grows the
+generator to the snapshot's stage and either goes on with the next stage (a finished one) or builds the stage the normal way
+and puts the state into it (train.train's `resume`).  Stopped and resumed any number of times the run leaves the checkpoints
+and scalars.jsonl of the run that was never stopped, bit for bit; with the flags absent nothing here does anything new.
+
 Not built: mp4 decoding / encoding (cv2), tensorboard event files and neptune (--tag is only recorded), a CPU path
 (--no-cuda is refused), multi-GPU launch."""
 import argparse
@@ -44,12 +54,13 @@ import glob
 import json
 import os
 import random
+import sys
 import types
 
 import numpy as np
 import torch
 
-from . import checkpoint, datasets, ops, telemetry
+from . import checkpoint, datasets, ops, snapshot, telemetry
 from . import train as hp_train
 from . import utils as hp_utils
 from .modules import networks_2d, networks_3d
@@ -276,21 +287,20 @@ def networks_of(opt):
     return networks_3d if opt.dims == 3 else networks_2d
 
 
-def _stage_data(loader, holder):
-    """Iterate the DataLoader and remember the batch at hand (the previews show `real`)."""
-    for item in loader:
-        holder[0] = item
-        yield item
+def _stage_data(loader, holder, pos=None):
+    """Iterate the DataLoader and remember the batch at hand (the previews show `real`).  pos: the snapshot.LoaderPosition of
+    a run with snapshots (it counts the batches and remembers the epoch's start), else None."""
+    return snapshot.iterate(loader, pos, holder)
 
 
 class _Loop:
     """Re-iterable view of the DataLoader that remembers the batch at hand (train.train restarts an exhausted iterator)."""
 
-    def __init__(self, loader, holder):
-        self.loader, self.holder = loader, holder
+    def __init__(self, loader, holder, pos=None):
+        self.loader, self.holder, self.pos = loader, holder, pos
 
     def __iter__(self):
-        return _stage_data(self.loader, self.holder)
+        return _stage_data(self.loader, self.holder, self.pos)
 
 
 class _Stage:
@@ -306,6 +316,10 @@ class _Stage:
             self.prog.preview(trainer, out, self.holder[0], i)
         if trainer.iteration % opt.print_interval == 0:
             self.prog.drain(self.log)
+        # after the preview and the drain: the BatchNorm buffers a preview moved are in the file
+        k = trainer.iteration
+        if self.prog.snap_interval and k % self.prog.snap_interval == 0 and 3 <= k < opt.niter:
+            self.prog.write_snapshot(trainer, self.log, False)
 
 
 class Program:
@@ -318,7 +332,10 @@ class Program:
     train_fn = staticmethod(hp_train.train)      # trains one stage
 
     def parser(self):
-        return build_parser(self.kind)
+        return snapshot.add_flags(build_parser(self.kind))
+
+    def program_name(self):
+        return self.program or 'train_' + self.kind
 
     def check_flags(self, opt):
         assert opt.vae_levels > 0
@@ -351,7 +368,17 @@ class Program:
     # ---- setup
     def __init__(self, kind, argv=None):
         self.kind = kind
+        # the snapshot flags are settled first and before the device is asked for: --resume brings the whole command line
+        # of the run it continues, and --video-path / --image-path are `required`
+        argv, flags, self.resume_snapshot = snapshot.resolve(sys.argv[1:] if argv is None else argv, self.program_name())
         opt = self.parser().parse_args(argv)
+        for name in ('snapshot_interval', 'snapshot_exit_after', 'resume'):
+            delattr(opt, name)   # the run's own business, not a setting of the experiment (opt.json stays what it was)
+        self.snap_interval, self.snap_exit_after = flags.snapshot_interval, flags.snapshot_exit_after
+        self.snapshots_written = 0
+        self.loader_pos = None
+        self.restore_skip, self.restore_verify = (), True   # test hooks of snapshot.restore
+        seed_given = opt.manualSeed is not None
         if opt.no_cuda:
             raise SystemExit("--no-cuda: hp-vae-gan_amd has no CPU path; every op runs on an MI355X")
         self.path = opt.video_path if kind == 'video' else opt.image_path
@@ -364,7 +391,11 @@ class Program:
             opt.program = self.program
         opt.dims = 3 if kind == 'video' else 2
         opt.hip_graph = not opt.no_hip_graph
-        self.exp_dir = experiment_dir(opt.run_dir, clip_name(self.path), opt.checkname)
+        if self.resume_snapshot is not None:
+            self.exp_dir = os.path.normpath(flags.resume)
+            snapshot.truncate_scalars(os.path.join(self.exp_dir, 'scalars.jsonl'), self.resume_snapshot['scalars_bytes'])
+        else:
+            self.exp_dir = experiment_dir(opt.run_dir, clip_name(self.path), opt.checkname)
         opt.experiment_dir = self.exp_dir
         self.log = Logbook(os.path.join(self.exp_dir, 'logbook.txt'))
         self.scalars = open(os.path.join(self.exp_dir, 'scalars.jsonl'), 'a')
@@ -374,6 +405,7 @@ class Program:
         if opt.manualSeed is None:
             opt.manualSeed = random.randint(1, 10000)
         self.log("Random Seed: {}".format(opt.manualSeed))
+        self.recorded_argv = snapshot.recorded_command_line(argv, opt.manualSeed, seed_given)
         random.seed(opt.manualSeed)
         torch.manual_seed(opt.manualSeed)
         opt.scale_idx = 0
@@ -388,8 +420,9 @@ class Program:
         if opt.stop_scale_time == -1:
             opt.stop_scale_time = opt.stop_scale
         self.opt = opt
-        with open(os.path.join(self.exp_dir, 'opt.json'), 'w') as f:
-            json.dump(json_settings(opt), f, indent=1, sort_keys=True)
+        if self.resume_snapshot is None:
+            with open(os.path.join(self.exp_dir, 'opt.json'), 'w') as f:
+                json.dump(json_settings(opt), f, indent=1, sort_keys=True)
         for k, v in json_settings(opt).items():
             self.log('{}: {}'.format(k, v))
         self.log("Experiment: {}".format(self.exp_dir))
@@ -406,7 +439,7 @@ class Program:
         self.logs = []
 
     # ---- one stage
-    def train_stage(self):
+    def train_stage(self, resume=None):
         opt = self.opt
         if opt.dims == 3:
             opt.fps, opt.td, opt.fps_index = hp_utils.get_fps_td_by_index(opt.scale_idx, opt)
@@ -417,24 +450,77 @@ class Program:
         netD = self.make_discriminator()
         log = telemetry.LossLog(self.loss_columns(netD), capacity=max(64, 2 * opt.print_interval), device=opt.device)
         holder = [None]
-        trainer = self.train_fn(opt, self.netG, _Loop(self.loader, holder), netD=netD, loss_log=log,
-                                callback=_Stage(self, log, holder))
+        self.loader_pos = snapshot.LoaderPosition() if self.snap_interval or resume is not None else None
+        more = {}
+        if resume is not None:   # a mid-stage snapshot: the stage is built the normal way, then the state goes into it
+            def put_back(trainer):
+                self.resumed_trainer = trainer
+                snapshot.restore(self, trainer, log, resume, skip=self.restore_skip, verify=self.restore_verify)
+            more['resume'] = put_back
+        trainer = self.train_fn(opt, self.netG, _Loop(self.loader, holder, self.loader_pos), netD=netD, loss_log=log,
+                                callback=_Stage(self, log, holder), **more)
         if trainer.iteration % opt.print_interval != 0:
             self.drain(log)
         self.end_stage(trainer)
         checkpoint.save_stage(self.exp_dir, opt, trainer)
         self.trainers.append(trainer)
         self.logs.append(log)
+        if self.snap_interval:
+            self.write_snapshot(trainer, log, True)
         return trainer
 
-    def run(self):
+    def write_snapshot(self, trainer, log, stage_done):
+        """Drain the loss log, then write <experiment>/snapshot.pth (snapshot.collect); the logbook line carries the state
+        digest, so two runs can be compared along the way.  --snapshot-exit-after: snapshot.ExitAfter after the N-th."""
         opt = self.opt
-        for scale, grow in stage_plan(opt.scale_idx, opt.resumed_idx, opt.stop_scale):
+        self.drain(log)
+        snap = snapshot.collect(self, trainer, log, stage_done)
+        size = snapshot.write(self.exp_dir, snap)
+        self.snapshots_written += 1
+        self.log("Snapshot: stage {}, iteration {}/{}{}, {} bytes, digest {:016x}".format(
+            opt.scale_idx, trainer.iteration, opt.niter, ' (stage done)' if stage_done else '', size, snap['digest']))
+        if self.snap_exit_after and self.snapshots_written == self.snap_exit_after:
+            raise snapshot.ExitAfter(self.snapshots_written)
+
+    def run(self):
+        try:
+            self.run_stages()
+        except snapshot.ExitAfter:
+            torch.cuda.synchronize()
+            self.log("Stopped after snapshot {} of this process (--snapshot-exit-after): continue with --resume {}".format(
+                self.snapshots_written, self.exp_dir))
+            self.scalars.close()
+            self.log.close()
+        return self
+
+    def run_stages(self):
+        opt = self.opt
+        plan = stage_plan(opt.scale_idx, opt.resumed_idx, opt.stop_scale)
+        snap, pending = self.resume_snapshot, None
+        if snap is not None:
+            # the generator grows to the snapshot's stage; a finished stage is restored here and the loop goes on with the
+            # next one as the uninterrupted run does, an unfinished one is built below and restored inside train_stage
+            for _ in range(snap['stage'] - opt.scale_idx):
+                self.netG.init_next_stage()
+            self.netG.to(opt.device)
+            opt.scale_idx = snap['stage']
+            snapshot.restore_settings(self, snap)
+            self.log("Resumed from {}: stage {}, iteration {}/{}{}, digest {:016x}".format(
+                os.path.join(self.exp_dir, snapshot.FILE), snap['stage'], snap['iteration'], snap['niter'],
+                ' (stage done)' if snap['stage_done'] else '', snap['digest']))
+            if snap['stage_done']:
+                snapshot.restore_finished_stage(self, snap, skip=self.restore_skip, verify=self.restore_verify)
+                plan = [(s, s > snap['stage']) for s, _ in plan if s > snap['stage']]
+            else:
+                pending = snap
+                plan = [(s, s > snap['stage']) for s, _ in plan if s >= snap['stage']]
+        for scale, grow in plan:
             opt.scale_idx = scale
             if grow:
                 self.netG.init_next_stage()
                 self.netG.to(opt.device)
-            self.train_stage()
+            self.train_stage(resume=pending)
+            pending = None
         opt.scale_idx = opt.stop_scale + 1
         torch.cuda.synchronize()
         self.log("Done: {}".format(self.exp_dir))

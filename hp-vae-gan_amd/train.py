@@ -296,16 +296,20 @@ def loss_log_columns(is_gan):
     return ["rec_vae_loss", "kl_loss", "total_loss", "grad_norm"]
 
 
-def train(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
+def train(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None, resume=None):
     """Train stage opt.scale_idx for opt.niter iterations (reference: train(opt, netG)).  Returns the StageTrainer
     (holding netD and the last losses) so that the caller can checkpoint exactly what the reference saves.
     loss_log: a telemetry.LossLog with loss_log_columns(is GAN stage) columns, appended to on every iteration.
-    callback(trainer, out) runs once per iteration that advances trainer.iteration, the capture's warm-up included."""
+    callback(trainer, out) runs once per iteration that advances trainer.iteration, the capture's warm-up included.
+    resume: callable(trainer) run once the trainer is built and before the loop; it puts a mid-stage snapshot back (weights,
+    optimizer state, trainer.iteration = trainer.resumed_at = k: snapshot.restore) and the loop continues from iteration k."""
     if getattr(opt, 'dims', 3) == 3:
         fps, td, fps_index = utils.get_fps_td_by_index(opt.scale_idx, opt)
         opt.fps, opt.td, opt.fps_index = fps, td, fps_index
     trainer = StageTrainer(opt, netG, netD)
     trainer.loss_log = loss_log
+    if resume is not None:
+        resume(trainer)
 
     def inputs(item):
         return item if opt.scale_idx > 0 else (item, item)
@@ -314,24 +318,34 @@ def train(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
 
 def _train_loop(opt, trainer, data, n, inputs, callback):
     """The stage loop of train() and train_baseline(): `n` iterations of trainer.step(*inputs(item)) over `data` (restarted
-    when exhausted), callback(trainer, out) after each, and the switch to hipGraph replay after two eager iterations."""
+    when exhausted), callback(trainer, out) after each, and the switch to hipGraph replay after two eager iterations.  A trainer
+    resumed at iteration k (trainer.resumed_at) runs one eager iteration, with its gradient-penalty alpha drawn where the
+    snapshot says (_graph_alpha), and captures after it when at least two iterations remain; its capture's warm-up runs on
+    the NEXT batch, since the run that was never stopped replayed that iteration on a batch of its own."""
+    resumed = getattr(trainer, 'resumed_at', None) is not None
+    capture_at = trainer.resumed_at + 1 if resumed else 2
     iterator = iter(data)
-    while trainer.iteration < n:
+
+    def take():
+        nonlocal iterator
         try:
-            item = next(iterator)
+            return next(iterator)
         except StopIteration:
             iterator = iter(data)
-            item = next(iterator)
-        args = inputs(item)
+            return next(iterator)
+    while trainer.iteration < n:
+        args = inputs(take())
         out = trainer.step(*args)
         if callback is not None:
             callback(trainer, out)
         # after two eager iterations (noise-amplitude calibration done, every workspace at its final size) the iteration
         # is captured once and replayed as a hipGraph: the host leaves the critical path (opt.hip_graph = False: stay
         # eager).  Capturing runs one more real iteration on this batch first (side-stream warm-up), which counts.
-        if (trainer.iteration == 2 and n - trainer.iteration >= 2 and getattr(opt, 'hip_graph', True)
+        if (trainer.iteration == capture_at and n - trainer.iteration >= 2 and getattr(opt, 'hip_graph', True)
                 and getattr(trainer, '_graph', None) is None and args[0].is_cuda):
             before = trainer.iteration
+            if resumed:
+                args = inputs(take())
             try:
                 trainer.enable_graph(*args)
             except GraphCaptureRefused as e:
@@ -466,7 +480,7 @@ def baseline_loss_log_columns(alpha):
     return cols + ["rec_loss"] if alpha > 0 else cols
 
 
-def train_baseline(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None):
+def train_baseline(opt, netG, data, netD=None, niter=None, loss_log=None, callback=None, resume=None):
     """train() for the SinGAN baselines (reference: train_video_baselines.py:24-213): stage opt.scale_idx with a
     BaselineStageTrainer (opt.Z_init set by the caller), the same eager start, hipGraph switch, GraphCaptureRefused
     handling and hooks.  `data` yields `real` (stage 0) or `(real, real_zero)`; real_zero is not used.  loss_log: a
@@ -475,6 +489,8 @@ def train_baseline(opt, netG, data, netD=None, niter=None, loss_log=None, callba
     opt.fps, opt.td, opt.fps_index = fps, td, fps_index
     trainer = BaselineStageTrainer(opt, netG, netD)
     trainer.loss_log = loss_log
+    if resume is not None:   # (see train)
+        resume(trainer)
 
     def inputs(item):
         return (item[0],) if opt.scale_idx > 0 else (item,)

@@ -30,6 +30,7 @@ from . import checkpoint
 from . import train as hp_train
 from . import utils as hp_utils
 from .modules import networks_3d
+from . import snapshot
 from .programs import Program, trainer_parser
 
 # column of the baselines' loss log -> the reference's tag (train_video_baselines.py:178-184: `rec_loss`, not train_video's
@@ -87,7 +88,7 @@ class BaselineProgram(Program):
         self.opt.Z_init = None   # drawn at the first stage this process trains
 
     def parser(self):
-        return build_baseline_parser()
+        return snapshot.add_flags(build_baseline_parser())
 
     def check_flags(self, opt):
         """None of train_video's: there are no VAE levels."""

@@ -447,6 +447,14 @@ int hpvg_clip_scale_f32(float* g, long n, const float* sqsum, float max_norm, fl
 int hpvg_adam_step_f32(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                        int step, const int* step_dev, void* stream);
 int hpvg_counter_inc_i32(int* counter, void* stream);
+/* ---- state digest (snapshot.py: a resume refuses a state that is not the one saved).  words: n 32-bit words on the device at
+ * any 4-byte offset; acc: one 64-bit device word that the call ADDS to (the caller clears it):
+ *   acc[0] += sum over i in [0, n) of fmix(((salt + i) * 0x9E3779B97F4A7C15) ^ word[i])   mod 2^64, word zero-extended,
+ *   fmix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (splitmix64).
+ * The sum is commutative: exact, a function of the words and the salt alone, independent of launch geometry and timing.  Calls
+ * with salts 0 and n1 over two buffers equal one call over their concatenation.  One kernel node, no workspace, capturable.
+ * n == 0 enqueues nothing.  HPVG_ERR_ARG: n < 0, a null acc, a null or misaligned words with n > 0. */
+int hpvg_state_digest_u32(const void* words, long n, unsigned long long salt, unsigned long long* acc, void* stream);
 
 /* ---- variant models (no trainer of the reference drives them; module-surface completeness): Encode3DVAE_nb / Encode2DVAE_nb
  * (networks_3d.py:110-138, networks_2d.py:115-143), GeneratorVAE_nb (networks_3d.py:409-485), reparameterize_bern

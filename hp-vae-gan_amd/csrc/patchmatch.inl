@@ -79,6 +79,11 @@ __device__ __forceinline__ unsigned pm_rnd(unsigned seed, unsigned i, unsigned i
   return pm_h32(seed + i * 0x9E3779B9u + (it * 64u + k * 4u + ax) * 0x85EBCA6Bu);
 }
 
+__device__ __forceinline__ int pm_mod(int c, int side) {   // the non-negative modulus
+  c %= side;
+  return c < 0 ? c + side : c;
+}
+
 __device__ __forceinline__ unsigned pm_load4(const unsigned char* p) {   // any alignment
   unsigned v;
   __builtin_memcpy(&v, p, 4);
@@ -181,11 +186,13 @@ __device__ __forceinline__ void pm_try(const PmGeom& g, const unsigned char* qp,
 
 // grid: (ceil(gW / 32), ceil(gH / 8), gT); thread (tx, ty) of a workgroup owns one query patch.  start: the launch that scores
 // the start (nn_init clamped, or the hash start) and reads no field; otherwise iteration `it` from src to dst.
-template <bool WEIGHTED, bool QLDS>
+// WRAP (hpvg_patchmatch_wrap_u8): bit ax of qwm / rwm says that axis ax of the query / key grid is a ring; the volumes arrive
+// circularly padded, so everything but the neighbourhood rule is the same code.  Without WRAP the masks are not read.
+template <bool WEIGHTED, bool QLDS, bool WRAP>
 __global__ __launch_bounds__(PM_TX * PM_TY) void patchmatch_kernel(const unsigned char* __restrict__ q, const unsigned char* __restrict__ r,
                                                                     const float* __restrict__ rw, const int* __restrict__ nn_init,
                                                                     PmField src, PmField dst, PmGeom g, unsigned seed, int it,
-                                                                    int start) {
+                                                                    int start, int qwm, int rwm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pm_lds[];
   const int tx = threadIdx.x & (PM_TX - 1), ty = threadIdx.x / PM_TX;
   const int ax0 = blockIdx.x * PM_TX, ay0 = blockIdx.y * PM_TY, at = blockIdx.z;
@@ -238,13 +245,15 @@ __global__ __launch_bounds__(PM_TX * PM_TY) void patchmatch_kernel(const unsigne
     for (int axis = 0; axis < 3; ++axis)
 #pragma unroll
       for (int s = -1; s <= 1; s += 2) {
-        const int na = a[axis] + s;
-        if (na < 0 || na >= gs[axis]) continue;
-        long nj = src.nn[i + s * stride[axis]];
+        int na = a[axis] + s;
+        if (WRAP && ((qwm >> axis) & 1)) na = na < 0 ? gs[axis] - 1 : (na >= gs[axis] ? 0 : na);
+        else if (na < 0 || na >= gs[axis]) continue;
+        long nj = src.nn[i + (na - a[axis]) * stride[axis]];
         nj = nj < 0 ? 0 : (nj >= g.Nr ? g.Nr - 1 : nj);
         int c[3] = {(int)(nj / (g.kW * g.kH)), (int)((nj / g.kW) % g.kH), (int)(nj % g.kW)};
         c[axis] -= s;
-        if (c[axis] < 0 || c[axis] >= ks[axis]) continue;
+        if (WRAP && ((rwm >> axis) & 1)) c[axis] = c[axis] < 0 ? ks[axis] - 1 : (c[axis] >= ks[axis] ? 0 : c[axis]);
+        else if (c[axis] < 0 || c[axis] >= ks[axis]) continue;
         pm_try<WEIGHTED, QLDS>(g, qp, r, rw, best, c[0], c[1], c[2]);
       }
     // the random search around the running best, radius R, R / 2, ... 1
@@ -254,9 +263,12 @@ __global__ __launch_bounds__(PM_TX * PM_TY) void patchmatch_kernel(const unsigne
       int ct = best.t + (int)(pm_rnd(seed, (unsigned)i, (unsigned)it, (unsigned)k, 0u) % span) - rk;
       int cy = best.y + (int)(pm_rnd(seed, (unsigned)i, (unsigned)it, (unsigned)k, 1u) % span) - rk;
       int cx = best.x + (int)(pm_rnd(seed, (unsigned)i, (unsigned)it, (unsigned)k, 2u) % span) - rk;
-      ct = ct < 0 ? 0 : (ct >= g.kT ? g.kT - 1 : ct);
-      cy = cy < 0 ? 0 : (cy >= g.kH ? g.kH - 1 : cy);
-      cx = cx < 0 ? 0 : (cx >= g.kW ? g.kW - 1 : cx);
+      if (WRAP && (rwm & 1)) ct = pm_mod(ct, g.kT);
+      else ct = ct < 0 ? 0 : (ct >= g.kT ? g.kT - 1 : ct);
+      if (WRAP && (rwm & 2)) cy = pm_mod(cy, g.kH);
+      else cy = cy < 0 ? 0 : (cy >= g.kH ? g.kH - 1 : cy);
+      if (WRAP && (rwm & 4)) cx = pm_mod(cx, g.kW);
+      else cx = cx < 0 ? 0 : (cx >= g.kW ? g.kW - 1 : cx);
       pm_try<WEIGHTED, QLDS>(g, qp, r, rw, best, ct, cy, cx);
     }
   }
@@ -266,16 +278,60 @@ __global__ __launch_bounds__(PM_TX * PM_TY) void patchmatch_kernel(const unsigne
     if (dst.score) dst.score[i] = best.sc;
 }
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool WRAP>
 void pm_launch_one(const PmGeom& g, const unsigned char* q, const unsigned char* r, const float* rw, const int* nn_init, PmField src,
-                   PmField dst, unsigned seed, int it, int start, hipStream_t st) {
+                   PmField dst, unsigned seed, int it, int start, int qwm, int rwm, hipStream_t st) {
   const dim3 grid((unsigned)((g.gW + PM_TX - 1) / PM_TX), (unsigned)((g.gH + PM_TY - 1) / PM_TY), (unsigned)g.gT);
   if (g.lds)
-    hipLaunchKernelGGL((patchmatch_kernel<WEIGHTED, true>), grid, dim3(PM_TX * PM_TY), g.lds, st, q, r, rw, nn_init, src, dst, g, seed,
-                       it, start);
+    hipLaunchKernelGGL((patchmatch_kernel<WEIGHTED, true, WRAP>), grid, dim3(PM_TX * PM_TY), g.lds, st, q, r, rw, nn_init, src, dst, g,
+                       seed, it, start, qwm, rwm);
   else
-    hipLaunchKernelGGL((patchmatch_kernel<WEIGHTED, false>), grid, dim3(PM_TX * PM_TY), 0, st, q, r, rw, nn_init, src, dst, g, seed, it,
-                       start);
+    hipLaunchKernelGGL((patchmatch_kernel<WEIGHTED, false, WRAP>), grid, dim3(PM_TX * PM_TY), 0, st, q, r, rw, nn_init, src, dst, g,
+                       seed, it, start, qwm, rwm);
+}
+
+// ring flags as a bit mask (bit ax = axis ax); null: 0; -1 for an entry other than 0 / 1
+inline int pm_wrap_mask(const int* wrap) {
+  int m = 0;
+  for (int ax = 0; wrap && ax < 3; ++ax) {
+    if (wrap[ax] != 0 && wrap[ax] != 1) return -1;
+    m |= wrap[ax] << ax;
+  }
+  return m;
+}
+
+// both entry points: the refusals, the two fields in the workspace, one launch for the start and one per iteration
+int pm_run(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch, int qwm,
+           int rwm, const float* rweight, const int* nn_init, int iters, long seed, int* d2, int* nn, float* score, void* ws,
+           size_t ws_bytes, void* stream) {
+  PmGeom g;
+  if (!q || !r || !d2 || !nn || (score && !rweight) || iters < 0 || iters > 1024 || qwm < 0 || rwm < 0 ||
+      !pm_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch))
+    return HPVG_ERR_ARG;
+  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t part = pnn_align((size_t)g.Nq * 4);
+  PmField f[2], out = {nn, d2, score};
+  for (int k = 0; k < 2; ++k) {
+    char* base = (char*)ws + g.off_field[k];
+    f[k].nn = (int*)base;
+    f[k].d2 = (int*)(base + part);
+    f[k].score = (float*)(base + 2 * part);
+  }
+  const unsigned s32 = (unsigned)(unsigned long)seed;
+  const bool wrap = (qwm | rwm) != 0;
+  // launch 0 scores the start, launch 1 + it is iteration it; launch n writes field n & 1, the last one the outputs
+  for (int n = 0; n <= iters; ++n) {
+    const PmField src = f[(n + 1) & 1], dst = n == iters ? out : f[n & 1];
+    if (wrap) {
+      if (rweight) pm_launch_one<true, true>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, qwm, rwm, st);
+      else pm_launch_one<false, true>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, qwm, rwm, st);
+    } else {
+      if (rweight) pm_launch_one<true, false>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, 0, 0, st);
+      else pm_launch_one<false, false>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, 0, 0, st);
+    }
+  }
+  return hpvg_launch_status();
 }
 
 }  // namespace
@@ -291,27 +347,14 @@ size_t hpvg_patchmatch_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, 
 int hpvg_patchmatch_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr, const int* patch,
                        const float* rweight, const int* nn_init, int iters, long seed, int* d2, int* nn, float* score, void* ws,
                        size_t ws_bytes, void* stream) {
-  PmGeom g;
-  if (!q || !r || !d2 || !nn || (score && !rweight) || iters < 0 || iters > 1024 || !pm_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch))
-    return HPVG_ERR_ARG;
-  if (!ws || ws_bytes < g.bytes || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t part = pnn_align((size_t)g.Nq * 4);
-  PmField f[2], out = {nn, d2, score};
-  for (int k = 0; k < 2; ++k) {
-    char* base = (char*)ws + g.off_field[k];
-    f[k].nn = (int*)base;
-    f[k].d2 = (int*)(base + part);
-    f[k].score = (float*)(base + 2 * part);
-  }
-  const unsigned s32 = (unsigned)(unsigned long)seed;
-  // launch 0 scores the start, launch 1 + it is iteration it; launch n writes field n & 1, the last one the outputs
-  for (int n = 0; n <= iters; ++n) {
-    const PmField src = f[(n + 1) & 1], dst = n == iters ? out : f[n & 1];
-    if (rweight) pm_launch_one<true>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, st);
-    else pm_launch_one<false>(g, q, r, rweight, nn_init, src, dst, s32, n - 1, n == 0, st);
-  }
-  return hpvg_launch_status();
+  return pm_run(q, Tq, Hq, Wq, r, Tr, Hr, Wr, patch, 0, 0, rweight, nn_init, iters, seed, d2, nn, score, ws, ws_bytes, stream);
+}
+
+int hpvg_patchmatch_wrap_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                            const int* patch, const int* qwrap, const int* rwrap, const float* rweight, const int* nn_init, int iters,
+                            long seed, int* d2, int* nn, float* score, void* ws, size_t ws_bytes, void* stream) {
+  return pm_run(q, Tq, Hq, Wq, r, Tr, Hr, Wr, patch, pm_wrap_mask(qwrap), pm_wrap_mask(rwrap), rweight, nn_init, iters, seed, d2, nn,
+                score, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

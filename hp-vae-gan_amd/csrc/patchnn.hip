@@ -36,6 +36,7 @@
 //
 // Vote (the generator's fold): patch_vote_kernel rebuilds a volume from chosen patches as a gather, one thread per output voxel
 // over the query-grid patches that cover it: no atomics, no zero fill, and integer sums, so the result is exact.
+// patch_vote_wrap_kernel is the same gather over a periodic query grid (generate_patchnn --wrap).
 //
 // Tile: 128 x 128 per workgroup of four waves (each 64 x 64 = 2 x 2 MFMA tiles of 32 x 32), K step 64 bytes, both operands
 // staged through LDS with 16-byte global loads (two LDS buffers: the next step's loads are in flight during the products, one
@@ -524,6 +525,57 @@ __global__ __launch_bounds__(256) void patch_vote_kernel(const unsigned char* __
   }
 }
 
+// The vote onto a ring (hpvg_patch_vote_wrap_u8): q is the UNPADDED output with the sides of its periodic grid in nT / nY / nX
+// (the whole side on a ring axis) and stride 1; bit ax of wm: axis ax is a ring.  Along a ring axis of side S the patches that
+// cover coordinate c are g = (c - d) mod S for every offset d = 0 .. p - 1 (S >= p, so they are p different patches); along
+// another axis g = c - d for the d with 0 <= g < n, as in patch_vote_kernel.  One thread per output voxel, d ascending.
+__global__ __launch_bounds__(256) void patch_vote_wrap_kernel(const unsigned char* __restrict__ v, const int* __restrict__ nn,
+                                                               const unsigned char* __restrict__ fallback,
+                                                               unsigned char* __restrict__ out, PnnSide q, PnnSide r, int pt, int ph,
+                                                               int pw, int wm) {
+  const long total = (long)q.T * q.H * q.W;
+  for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
+    const int x = (int)(o % q.W);
+    const int y = (int)((o / q.W) % q.H);
+    const int t = (int)(o / ((long)q.W * q.H));
+    // offsets d in [d0, d1] along each axis; on a ring every offset has its patch
+    const int dt0 = (wm & 1) ? 0 : max(0, t - (q.nT - 1)), dt1 = (wm & 1) ? pt - 1 : min(pt - 1, t);
+    const int dy0 = (wm & 2) ? 0 : max(0, y - (q.nY - 1)), dy1 = (wm & 2) ? ph - 1 : min(ph - 1, y);
+    const int dx0 = (wm & 4) ? 0 : max(0, x - (q.nX - 1)), dx1 = (wm & 4) ? pw - 1 : min(pw - 1, x);
+    int s0 = 0, s1 = 0, s2 = 0, cnt = 0;
+    for (int dt = dt0; dt <= dt1; ++dt) {
+      int gt = t - dt;
+      if (gt < 0) gt += q.T;
+      for (int dy = dy0; dy <= dy1; ++dy) {
+        int gy = y - dy;
+        if (gy < 0) gy += q.H;
+        for (int dx = dx0; dx <= dx1; ++dx) {
+          int gx = x - dx;
+          if (gx < 0) gx += q.W;
+          const int j = nn[((long)gt * q.nY + gy) * q.nX + gx];
+          if (j < 0 || j >= r.N) continue;
+          const int rx = j % r.nX, ry = (j / r.nX) % r.nY, rt = j / (r.nX * r.nY);
+          const unsigned char* b = v + (((long)(rt * r.st + dt) * r.H + ry * r.sy + dy) * r.W + rx * r.sx + dx) * 3;
+          s0 += b[0];
+          s1 += b[1];
+          s2 += b[2];
+          ++cnt;
+        }
+      }
+    }
+    unsigned char* dst = out + o * 3;
+    if (cnt) {
+      dst[0] = (unsigned char)((2 * s0 + cnt) / (2 * cnt));
+      dst[1] = (unsigned char)((2 * s1 + cnt) / (2 * cnt));
+      dst[2] = (unsigned char)((2 * s2 + cnt) / (2 * cnt));
+    } else {
+      dst[0] = fallback[o * 3];
+      dst[1] = fallback[o * 3 + 1];
+      dst[2] = fallback[o * 3 + 2];
+    }
+  }
+}
+
 // One thread per 4-byte word of the packed direction matrix; rows past P and bytes past D are zeros.
 __global__ __launch_bounds__(256) void patchproj_pack_dirs_kernel(const signed char* __restrict__ dirs, signed char* __restrict__ mat,
                                                                    int P, long Ppad, int D, int Dp) {
@@ -824,6 +876,34 @@ int hpvg_patch_vote_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(patch_vote_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, nn, fallback, out, g.q, g.r,
                      g.pt, g.ph, g.pw);
+  return hpvg_launch_status();
+}
+
+int hpvg_patch_vote_wrap_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int* nn, int Tq, int Hq, int Wq, const int* patch,
+                            const int* rstride, const int* wrap, const unsigned char* fallback, unsigned char* out, void* stream) {
+  PnnGeom g;
+  const int one[3] = {1, 1, 1};
+  if (!v || !nn || !fallback || !out || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, one, rstride)) return HPVG_ERR_ARG;
+  int wm = 0;
+  for (int ax = 0; wrap && ax < 3; ++ax) {
+    if (wrap[ax] != 0 && wrap[ax] != 1) return HPVG_ERR_ARG;
+    wm |= wrap[ax] << ax;
+  }
+  // the periodic grid: the whole side on a ring axis (the geometry above has made sure that patch <= side)
+  if (wm & 1) g.q.nT = Tq;
+  if (wm & 2) g.q.nY = Hq;
+  if (wm & 4) g.q.nX = Wq;
+  if ((double)g.q.nT * (double)g.q.nY * (double)g.q.nX >= 2147483648.0) return HPVG_ERR_ARG;
+  g.q.N = (long)g.q.nT * g.q.nY * g.q.nX;
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)Tq * Hq * Wq * 3;
+  const uintptr_t in0[3] = {(uintptr_t)fallback, (uintptr_t)v, (uintptr_t)nn};
+  const size_t inb[3] = {(size_t)Tq * Hq * Wq * 3, (size_t)Tr * Hr * Wr * 3, (size_t)g.q.N * 4};
+  for (int k = 0; k < 3; ++k)
+    if (o0 < in0[k] + inb[k] && in0[k] < o1) return HPVG_ERR_ARG;
+  long blocks = ((long)Tq * Hq * Wq + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(patch_vote_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, nn, fallback, out, g.q, g.r,
+                     g.pt, g.ph, g.pw, wm);
   return hpvg_launch_status();
 }
 

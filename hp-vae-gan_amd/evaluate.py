@@ -1,7 +1,8 @@
 """`python -m hp_vae_gan_amd.evaluate --exp-dir run/<clip>/<checkname>/experiment_<n>` (after `generate`), or
 `--samples S.npy --real R.npy` without an experiment: patch nearest-neighbour coherence / completeness, nn_unique_frac and
 diversity of the samples against the training clip, written to metrics.json; with --chunks also the copied-region statistics of
-the nearest-neighbour field; with --prdc K also the patch sets' precision, recall, density and coverage at k = K."""
+the nearest-neighbour field; with --prdc K also the patch sets' precision, recall, density and coverage at k = K; with --wrap AXES
+also seam_coherence, the coherence of the patches that cross the seam of samples that are rings along those axes."""
 import argparse
 import json
 import math
@@ -12,7 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume, write_frames
+from .programs import default_patch, gpu_device, load_opt, load_u8_frames, parse_wrap_axes, patchnn_wrap_pad, real_volume, write_frames
 
 
 def evaluate_parser():
@@ -46,6 +47,9 @@ def evaluate_parser():
                    'floor(X * D * 255^2), X in the unit of coherence (default: none; saturated regions have radius 0)')
     p.add_argument('--save-prdc', action='store_true', help='with --prdc (without it: nothing): write prdc.npz (count per sample patch, '
                    'real_radius and real_covered on the real grid)')
+    p.add_argument('--wrap', default=None, metavar='AXES', help='the samples are rings along these axes (distinct letters of t, h, w; '
+                   'what `generate_patchnn --wrap` makes): also report seam_coherence, the coherence of the patches that cross a seam '
+                   '(last slice into first).  --stride must be 1 on a ring axis; no t for images')
     return p
 
 
@@ -123,6 +127,22 @@ def swd_score(num, Na, Nb, dirs):
     return sum((n / scale) / math.sqrt(z) for n, z in zip(num, nnz)) / len(num)   # n / scale: Python's correctly rounded int / int
 
 
+def seam_patches(size, patch, stride, wrap):
+    """(flat indices, grid): the patches that cross at least one seam of a (T, H, W) volume that is a ring along the axes flagged
+    in wrap = (wt, wh, ww).  The grid is the periodic one at `stride` - every position of a ring axis (stride 1 there), the
+    positions 0, s, 2 s, ... <= S - p of another - which is the strided grid of the circularly padded volume; a patch crosses
+    the seam of a ring axis iff its coordinate there is > S - p.  Indices: ascending int64 numpy, raster order.  Host only."""
+    coords, grid = [], []
+    for S, p, s, w in zip(size, patch, stride, wrap):
+        if w and int(s) != 1:
+            raise ValueError("seam_patches: the stride along a ring axis must be 1, got %s" % (tuple(stride),))
+        n = int(S) if w else (int(S) - int(p)) // int(s) + 1
+        grid.append(n)
+        coords.append(np.arange(n) > int(S) - int(p) if w else np.zeros(n, bool))
+    cross = coords[0][:, None, None] | coords[1][None, :, None] | coords[2][None, None, :]
+    return np.flatnonzero(cross.reshape(-1)).astype(np.int64), tuple(grid)
+
+
 def pair_count(grid):
     """E: the pairs of 6-neighbours of a patch grid (gT, gH, gW)."""
     gT, gH, gW = (int(e) for e in grid)
@@ -181,12 +201,23 @@ def source_colours(nn, ref_grid):
 
 
 def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0,
-             chunks=False, chunk_tol=None, save_chunks=False, prdc=0, prdc_floor=None, save_prdc=False):
+             chunks=False, chunk_tol=None, save_chunks=False, prdc=0, prdc_floor=None, save_prdc=False, wrap=None):
     """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
     `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions.
     chunks (implied by chunk_tol / save_chunks): also the copied-region statistics of the coherence direction's field.
     prdc = k > 0: also precision / recall / density / coverage of the patch sets (prdc_floor is refused without it, save_prdc
-    does nothing without it)."""
+    does nothing without it).  wrap: the --wrap string (letters of t, h, w): the samples are rings along those axes, and every
+    sample also gets seam_patches (the patches of its periodic grid, at `stride`, that cross a seam) and seam_coherence (the
+    mean over those of the exact nearest distance to the real volume's dense patches, over D * 255^2; None without such
+    patches), searched on the circularly padded sample with ops.patch_nn_subset."""
+    rings = None
+    if wrap is not None:
+        try:
+            rings = parse_wrap_axes(wrap)
+        except SystemExit as e:
+            raise SystemExit("evaluate: {}".format(e))
+        if any(w and int(s) != 1 for w, s in zip(rings, stride)):
+            raise SystemExit("evaluate: --wrap {}: --stride must be 1 along a ring axis, got {}".format(wrap, list(stride)))
     prdc_check(prdc, prdc_floor)
     prdc = int(prdc or 0)
     if exp_dir is None and (samples is None or real is None):
@@ -202,6 +233,8 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
     if max_samples:
         arr = arr[:max_samples]
     video = arr.ndim == 5
+    if rings is not None and rings[0] and not video:
+        raise SystemExit("evaluate: --wrap t needs clips: an image has no time axis")
     out = out or os.path.dirname(os.path.abspath(spath))
     os.makedirs(out, exist_ok=True)
     if exp_dir is not None:
@@ -242,6 +275,11 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         p1.record()
         p1.synchronize()
         prdc_seconds, prdc_saved = p0.elapsed_time(p1) / 1e3, []
+    if rings is not None:
+        seam_idx, _ = seam_patches(vol(samples_dev[0]), patch, stride, rings)
+        seam_sel = torch.from_numpy(seam_idx).to(device=device, dtype=torch.int32)
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        seam_seconds = 0.0
     per_sample = []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     seconds = 0.0
@@ -254,6 +292,16 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         seconds += e0.elapsed_time(e1) / 1e3
         per_sample.append({"coherence": patch_score(d2c, D), "completeness": patch_score(d2r, D),
                            "nn_unique_frac": nn_unique_frac(nnc, coh_counts[1])})
+        if rings is not None:
+            per_sample[-1].update({"seam_patches": int(seam_sel.numel()), "seam_coherence": None})
+            if seam_sel.numel():
+                s0.record()
+                d2s, _ = ops.patch_nn_subset(patchnn_wrap_pad(smp, patch, rings), real_dev, patch, seam_sel, None, qstride=stride)
+                d2s = d2s.reshape(-1)[seam_sel.long()]
+                s1.record()
+                s1.synchronize()
+                seam_seconds += s0.elapsed_time(s1) / 1e3
+                per_sample[-1]["seam_coherence"] = patch_score(d2s, D)
         if chunks:
             c0.record()
             labels, sizes, stats = ops.nnf_chunks(nnc, ref_grid, qstride=stride, d2=None if max_d2 is None else d2c, max_d2=max_d2)
@@ -330,20 +378,26 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
             np.savez(os.path.join(out, 'prdc.npz'), count=np.stack([s[0] for s in prdc_saved]),
                      real_radius=rad_real.cpu().numpy().reshape(rgrid),
                      real_covered=np.stack([s[1].reshape(rgrid) for s in prdc_saved]))
+    seam_text = ""
+    if rings is not None:
+        vals = [p["seam_coherence"] for p in per_sample]
+        metrics.update({"seam_coherence": None if any(v is None for v in vals) else sum(vals) / n, "wrap": wrap,
+                        "seam_seconds": seam_seconds})
+        seam_text = " seam_coherence {}".format("n/a" if metrics["seam_coherence"] is None else "{:.6f}".format(metrics["seam_coherence"]))
     with open(os.path.join(out, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1, sort_keys=True)
-    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{}{} "
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{}{}{} "
           "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
                                                metrics["nn_unique_frac"],
                                                "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
-                                               swd_text, chunk_text, prdc_text, seconds, os.path.join(out, 'metrics.json')))
+                                               swd_text, chunk_text, prdc_text, seam_text, seconds, os.path.join(out, 'metrics.json')))
     return metrics
 
 
 def main(argv=None):
     a = evaluate_parser().parse_args(argv)
     evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed, a.chunks, a.chunk_tol,
-             a.save_chunks, a.prdc, a.prdc_floor, a.save_prdc)
+             a.save_chunks, a.prdc, a.prdc_floor, a.save_prdc, a.wrap)
     return 0
 
 

@@ -2,7 +2,9 @@
 dir`, `--image-path img.png --out dir`): training-free samples of the clip by coarse-to-fine patch nearest neighbours (GPNN /
 VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json.  With `--mask hole.npy` the samples are completions of
 the masked region of the clip (patch inpainting) and every other voxel stays as it is.  With `--search patchmatch` the levels
-above the coarsest search by a deterministic PatchMatch (linear in the patch count) instead of exhaustively."""
+above the coarsest search by a deterministic PatchMatch (linear in the patch count) instead of exhaustively.  With `--wrap AXES`
+(letters of t, h, w) the samples are rings along those axes: `--wrap t` makes clips whose last frame continues into the first
+(seamless loops), `--wrap hw` tileable textures."""
 import argparse
 import json
 import math
@@ -15,7 +17,8 @@ import torch
 from . import ops
 from . import utils as hp_utils
 from . import datasets
-from .programs import default_patch, gpu_device, load_opt, load_u8_frames, real_volume, write_samples
+from .programs import (default_patch, gpu_device, load_opt, load_u8_frames, parse_wrap_axes, patchnn_wrap_pad, real_volume,
+                       wrap_triple as _wrap3, write_samples)
 
 
 # The training-free counterpart of the trained generator: GPNN (Granot et al., "Drop the GAN", CVPR 2022) and its video form
@@ -66,7 +69,16 @@ def generate_patchnn_parser():
                    '--search patchmatch' % PM_ITERS)
     p.add_argument('--pm-from-level', type=int, default=None, help='first pyramid level searched by PatchMatch, >= 1 (default %d; '
                    'level 0 is always exact); only with --search patchmatch' % PM_FROM_LEVEL)
+    p.add_argument('--wrap', default=None, metavar='AXES', help='make the samples rings along these axes: distinct letters of t, h, w '
+                   '(t: a clip that loops without a seam; hw: a texture that tiles).  The patches that cross a seam are searched '
+                   'and voted like any others; the real clip stays as it is.  Not with --mask; no t for an image')
     return p
+
+
+def patchnn_wrap_grid(size, patch, wrap):
+    """The sides of the periodic patch grid of a (T, H, W) volume: the whole side on a ring axis, S - p + 1 elsewhere."""
+    w = _wrap3(wrap) or (0, 0, 0)
+    return tuple(int(s) if f else int(s) - int(p) + 1 for s, p, f in zip(size, patch, w))
 
 
 def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7)):
@@ -155,7 +167,7 @@ def _next_seed(state):
 
 
 def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, search='exact', pm_iters=PM_ITERS,
-                   pm_from_level=PM_FROM_LEVEL, level=None, state=None):
+                   pm_from_level=PM_FROM_LEVEL, level=None, state=None, wrap=None):
     """One GPNN step on uint8 volumes (or images): m = for every key patch the distance to its nearest query patch,
     w = 1 / (float32(m) + float32(alpha_abs)), nn = the weighted nearest key of every query patch, result = the vote of the
     value patches nn (keys and values share one grid) with the query as fallback.  alpha_abs = inf: the plain nearest key,
@@ -164,7 +176,13 @@ def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, se
     ops.patch_match with pm_iters iterations - m is the d2 of patch_match(keys, query) started from state['rev'], the forward
     search is patch_match(query, keys, ref_weight=w) started from state['fwd'] - each under its own seed
     (patchnn_search_state).  state: that dict, updated in place with the fields of this step's searches, exact ones included
-    (None: a fresh one, i.e. hash starts under seeds 0 and 1)."""
+    (None: a fresh one, i.e. hash starts under seeds 0 and 1).
+    wrap = (wt, wh, ww): the query (the guess) is a ring along the flagged axes.  Both searches then run on the circularly padded
+    query (patchnn_wrap_pad), whose dense grid is the query's periodic grid - PatchMatch with that grid's ring flags on the
+    query's side - and the vote goes onto the ring (ops.patch_vote(..., wrap)), into the query's own size.  The fields in
+    `state` live on the periodic grid.  Keys and values are never rings.  None: the step it always was."""
+    wrap = _wrap3(wrap)
+    padded = query if wrap is None else patchnn_wrap_pad(query, patch, wrap)
     if search not in ("exact", "patchmatch"):
         raise ValueError("patchnn_refine: search must be 'exact' or 'patchmatch', got %r" % (search,))
     pm = search == "patchmatch" and (level is None or int(level) >= max(int(pm_from_level), 1))
@@ -173,25 +191,29 @@ def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, se
     rev = None
     if pm:
         if math.isinf(alpha_abs):
-            score, nn = ops.patch_match(query, keys, patch, pm_iters, _next_seed(state), None, state["fwd"])
+            score, nn = ops.patch_match(padded, keys, patch, pm_iters, _next_seed(state), None, state["fwd"], qwrap=wrap)
         else:
-            m, rev = ops.patch_match(keys, query, patch, pm_iters, _next_seed(state), None, state["rev"])
-            score, nn = ops.patch_match(query, keys, patch, pm_iters, _next_seed(state), patchnn_weights(m, alpha_abs), state["fwd"])
+            m, rev = ops.patch_match(keys, padded, patch, pm_iters, _next_seed(state), None, state["rev"], rwrap=wrap)
+            score, nn = ops.patch_match(padded, keys, patch, pm_iters, _next_seed(state), patchnn_weights(m, alpha_abs), state["fwd"],
+                                        qwrap=wrap)
     elif math.isinf(alpha_abs):
-        score, nn = ops.patch_nn(query, keys, patch)
+        score, nn = ops.patch_nn(padded, keys, patch)
     else:
-        m, rev = ops.patch_nn(keys, query, patch)
-        score, nn = ops.patch_nn_weighted(query, keys, patchnn_weights(m, alpha_abs), patch)
+        m, rev = ops.patch_nn(keys, padded, patch)
+        score, nn = ops.patch_nn_weighted(padded, keys, patchnn_weights(m, alpha_abs), patch)
     if state is not None:
         state["fwd"], state["rev"] = nn, rev
-    out = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query)
+    if wrap is None:
+        out = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query)
+    else:
+        out = ops.patch_vote(values, nn, patch, tuple(query.shape[:-1]), query, wrap=wrap)
     if return_score:
         return out, float(score.to(torch.float64).mean())
     return out
 
 
 def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, alpha=0.005, seed=0, index=0,
-                       pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL):
+                       pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL, wrap=None):
     """One sample of the uint8 device volume `real` ([T,H,W,3]; images [H,W,3]) -> (sample, mean final score).  size: the
     sample's (T, H, W) (default real's).  The coarsest guess is real level 0 (resized to the sample's coarsest size) plus
     noise * 255 * N(0, 1) drawn under torch.manual_seed(seed + index); level 0 runs `iters` steps with keys = values = real
@@ -201,7 +223,11 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
     search = 'patchmatch': the steps of level max(pm_from_level, 1) and above search by PatchMatch (patchnn_refine) with
     pm_iters iterations, each started from the previous step's fields; between levels both fields go through
     patchnn_field_resize (the guess's and the keys' grids may differ: retargeting).  Seeds: patchnn_search_state(seed, index).
-    The default 'exact' computes what it always did."""
+    The default 'exact' computes what it always did.
+    wrap = (wt, wh, ww): the sample is a ring along the flagged axes - every step is patchnn_refine(..., wrap=wrap) and the
+    PatchMatch fields live on the guess's periodic grids.  The resize between levels and the coarsest noise stay as they are
+    (not periodic): the steps that follow re-vote every voxel."""
+    wrap = _wrap3(wrap)
     image = real.dim() == 3
     vol = real[None] if image else real
     patch = tuple(patch) if patch else default_patch(not image)
@@ -232,7 +258,7 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
         if l > 0:
             q = _resize_u8(q, qsizes[l])
             if state is not None:
-                qf, qt = (tuple(s - p + 1 for s, p in zip(qsizes[k], patch)) for k in (l - 1, l))
+                qf, qt = (patchnn_wrap_grid(qsizes[k], patch, wrap) for k in (l - 1, l))
                 rf, rt = (tuple(s - p + 1 for s, p in zip(sizes[k], patch)) for k in (l - 1, l))
                 if state["fwd"] is not None:
                     state["fwd"] = patchnn_field_resize(state["fwd"], qf, rf, qt, rt)
@@ -241,7 +267,7 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
         for it in range(iters):
             k = keys[l] if (l > 0 and it == 0) else levels[l]
             q, score = patchnn_refine(q, k, levels[l], patch, alpha_abs, return_score=True, search=search, pm_iters=pm_iters,
-                                      pm_from_level=pm_from_level, level=l, state=state)
+                                      pm_from_level=pm_from_level, level=l, state=state, wrap=wrap)
     return (q[0] if image else q), score
 
 
@@ -405,14 +431,27 @@ def _refuse_trivial_mask(forms):
 
 def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
                      min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None, search='exact',
-                     pm_iters=None, pm_from_level=None):
+                     pm_iters=None, pm_from_level=None, wrap=None):
     """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
     patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample).  mask: the
     path of a hole mask of the real volume; the samples are then completions of the hole (patchnn_inpaint), land in
     <exp-dir>/eval/samples_patchinpaint by default, and patchnn.json also records the mask, its voxels and per level the query
     and key patches.  search = 'patchmatch': patchnn_synthesize's PatchMatch steps, with pm_iters (default 4) iterations per
     search from level pm_from_level (default 1) on; patchnn.json then also records search, pm_iters and pm_from_level.  Not
-    with a mask (the subset search has no PatchMatch form), and the two pm_* settings only with it."""
+    with a mask (the subset search has no PatchMatch form), and the two pm_* settings only with it.  wrap: the --wrap string
+    (letters of t, h, w): the samples are rings along those axes (patchnn_synthesize's wrap); patchnn.json then records it.  Not
+    with a mask, and no t for an image."""
+    rings = None
+    if wrap is not None:
+        try:
+            rings = parse_wrap_axes(wrap)
+        except SystemExit as e:
+            raise SystemExit("generate_patchnn: {}".format(e))
+        if mask is not None:
+            raise SystemExit("generate_patchnn: --wrap makes the whole sample a ring, --mask keeps everything outside a hole: "
+                             "they do not combine")
+        if rings[0] and image_path is not None:
+            raise SystemExit("generate_patchnn: --wrap t needs a clip: an image has no time axis")
     if search not in ("exact", "patchmatch"):
         raise SystemExit("generate_patchnn: --search must be exact or patchmatch, got {!r}".format(search))
     if search == "exact" and (pm_iters is not None or pm_from_level is not None):
@@ -458,6 +497,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         if video_path is not None and real.dim() == 3:
             real = real[None]   # one frame given as a clip
     image = real.dim() == 3
+    if image and rings is not None and rings[0]:
+        raise SystemExit("generate_patchnn: --wrap t needs a clip: an image has no time axis")
     vol = real[None] if image else real
     patch = tuple(patch) if patch else default_patch(not image)
     size = tuple(size) if size else tuple(vol.shape[:3])
@@ -489,6 +530,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
                 smp, score = patchnn_inpaint(vol, hole, patch, ratio, min_size, iters, noise, seed, i, pyramid)
             else:
                 pm = {"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level} if search == "patchmatch" else {}
+                if rings is not None:
+                    pm["wrap"] = rings
                 smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid, **pm)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
@@ -511,6 +554,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
                      "valid_keys": [int(lv["rsel"].numel()) for lv in pyramid[3]]})
     if search == "patchmatch":
         info.update({"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level})
+    if wrap is not None:
+        info["wrap"] = wrap
     with open(os.path.join(out, 'patchnn.json'), 'w') as f:
         json.dump(info, f, indent=1, sort_keys=True)
     print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
@@ -521,7 +566,7 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
 def main(argv=None):
     a = generate_patchnn_parser().parse_args(argv)
     generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
-                     a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level)
+                     a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level, a.wrap)
     return 0
 
 

@@ -1412,14 +1412,28 @@ def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rs
     return score, nn
 
 
-def patch_match(query_u8, ref_u8, patch, iters, seed=0, ref_weight=None, nn_init=None):
+def _wrap_flags(wrap, name, op):
+    """Ring flags (wt, wh, ww), each 0 / 1 (or a bool), as a C int[3]; None stays None (a null pointer: no rings)."""
+    if wrap is None:
+        return None
+    w = tuple(wrap)
+    if len(w) != 3 or any(e not in (0, 1) for e in w):
+        raise RuntimeError("%s: %s must be three flags (t, h, w), each 0 or 1, got %r" % (op, name, wrap))
+    return (ctypes.c_int * 3)(*(int(e) for e in w))
+
+
+def patch_match(query_u8, ref_u8, patch, iters, seed=0, ref_weight=None, nn_init=None, qwrap=None, rwrap=None):
     """Deterministic PatchMatch (hpvg_patchmatch_u8): an approximate nearest-neighbour field between the dense patch grids of two
     uint8 device tensors [T,H,W,3] or [H,W,3], at a cost linear in the number of patches.  The rule - hash start or nn_init,
     `iters` Jacobi iterations of propagation and a shrinking random search, keys (d2, j) or (float32(d2) * ref_weight[j], j) -
     is written out in include/hpvg.h; a seed gives the same field on every run.  ref_weight: as for patch_nn_weighted.
     nn_init: int32 device tensor with the query grid's element count (entries are clamped into the key grid).  Returns
-    (d2 int32, nn int32), or (score float32, nn int32) with weights, shaped as the query's patch grid."""
+    (d2 int32, nn int32), or (score float32, nn int32) with weights, shaped as the query's patch grid.
+    qwrap / rwrap (hpvg_patchmatch_wrap_u8): flags (t, h, w) saying which axes of the query's / ref's PATCH GRID are rings; the
+    volume on a ring side arrives circularly padded by the caller, so its dense grid is the periodic one.  Both None: the plain
+    entry point, exactly as before."""
     (q, r), image = _patch_volumes("patch_match", (("query", query_u8), ("ref", ref_u8)))
+    qw, rw = _wrap_flags(qwrap, "qwrap", "patch_match"), _wrap_flags(rwrap, "rwrap", "patch_match")
     pa, one = _triple(patch, "patch", "patch_match"), _triple((1, 1, 1), "stride", "patch_match")
     qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
     counts = (ctypes.c_int * 3)()
@@ -1450,8 +1464,12 @@ def patch_match(query_u8, ref_u8, patch, iters, seed=0, ref_weight=None, nn_init
     d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
     nn = torch.empty(grid, dtype=torch.int32, device=q.device)
     score = torch.empty(grid, dtype=torch.float32, device=q.device) if w is not None else None
-    call("hpvg_patchmatch_u8", ptr(q), *qg, ptr(r), *rg, pa, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2), ptr(nn), ptr(score),
-         *ws, stream())
+    if qw is None and rw is None:
+        call("hpvg_patchmatch_u8", ptr(q), *qg, ptr(r), *rg, pa, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2), ptr(nn),
+             ptr(score), *ws, stream())
+    else:
+        call("hpvg_patchmatch_wrap_u8", ptr(q), *qg, ptr(r), *rg, pa, qw, rw, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2),
+             ptr(nn), ptr(score), *ws, stream())
     out = score if w is not None else d2
     if image:
         out, nn = out[0], nn[0]
@@ -1627,25 +1645,38 @@ def patch_vote_counts(out_shape, values_shape, patch, qstride=(1, 1, 1), rstride
     return out[0], out[1], out[2]
 
 
-def patch_vote(values_u8, nn, patch, out_shape, fallback_u8, qstride=(1, 1, 1), rstride=(1, 1, 1)):
+def patch_vote(values_u8, nn, patch, out_shape, fallback_u8, qstride=(1, 1, 1), rstride=(1, 1, 1), wrap=None):
     """Rebuild a volume from chosen patches (hpvg_patch_vote_u8; the fold of the patch nearest-neighbour generator): every
     output voxel is the mean, halves rounded up, of the bytes that the patches of the output's grid (qstride) covering it take
     from the patches nn[i] of values_u8's grid (rstride).  values_u8 / fallback_u8: uint8 device tensors [T,H,W,3] or [H,W,3];
     out_shape = fallback's (T, H, W) or (H, W); nn: int32 with one entry per patch of the output's grid.  Entries outside
-    [0, Nr) are skipped, and a voxel with no vote takes fallback's byte.  Returns a new uint8 tensor shaped as fallback_u8."""
+    [0, Nr) are skipped, and a voxel with no vote takes fallback's byte.  Returns a new uint8 tensor shaped as fallback_u8.
+    wrap (hpvg_patch_vote_wrap_u8): flags (t, h, w) saying which axes of the OUTPUT are rings; the output's grid is then the
+    periodic one (a whole side of positions on a ring axis, patches continuing from the last slice into the first), dense
+    (qstride must be (1, 1, 1)), and nn has one entry per patch of it.  None: the plain entry point, exactly as before."""
     (v, fb), image = _patch_volumes("patch_vote", (("values", values_u8), ("fallback", fallback_u8)))
+    wr = _wrap_flags(wrap, "wrap", "patch_vote")
     oshape = tuple(int(e) for e in out_shape)
     if oshape != tuple(fallback_u8.shape[:-1]):
         raise RuntimeError("patch_vote: out_shape %s is not the fallback's %s" % (oshape, tuple(fallback_u8.shape[:-1])))
     pa, qs, rs = _triple(patch, "patch", "patch_vote"), _triple(qstride, "qstride", "patch_vote"), _triple(rstride, "rstride", "patch_vote")
     og, vg = tuple(fb.shape[:3]), tuple(v.shape[:3])
     Nq = patch_vote_counts(og, vg, patch, qstride, rstride)[0]    # refuses bad arguments by name
+    if wr is not None:
+        if tuple(qs) != (1, 1, 1):
+            raise RuntimeError("patch_vote: a ring's grid is dense: wrap needs qstride (1, 1, 1), got %s" % (tuple(qs),))
+        Nq = 1
+        for a in range(3):
+            Nq *= og[a] if wr[a] else og[a] - pa[a] + 1
     if not isinstance(nn, torch.Tensor) or nn.dtype != torch.int32 or nn.numel() != Nq or nn.device != v.device:
         raise RuntimeError("patch_vote: nn must be int32 with %d entries on %s, got %s %s on %s"
                            % (Nq, v.device, getattr(nn, "dtype", type(nn)), tuple(getattr(nn, "shape", ())), getattr(nn, "device", None)))
     nn = _c(nn)
     out = torch.empty_like(fb)
-    call("hpvg_patch_vote_u8", ptr(v), *vg, ptr(nn), *og, pa, qs, rs, ptr(fb), ptr(out), stream())
+    if wr is None:
+        call("hpvg_patch_vote_u8", ptr(v), *vg, ptr(nn), *og, pa, qs, rs, ptr(fb), ptr(out), stream())
+    else:
+        call("hpvg_patch_vote_wrap_u8", ptr(v), *vg, ptr(nn), *og, pa, rs, wr, ptr(fb), ptr(out), stream())
     return out[0] if image else out
 
 

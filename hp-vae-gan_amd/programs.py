@@ -585,3 +585,40 @@ def train_main(kind, argv=None):
     Program(kind, argv).run()
     return 0
 
+
+# Rings (generate_patchnn --wrap, evaluate --wrap): what the two programs share.
+def parse_wrap_axes(text):
+    """--wrap AXES -> the ring flags (wt, wh, ww): a non-empty string of distinct letters of t, h, w.  Anything else ends the
+    program."""
+    if not isinstance(text, str) or not text or any(c not in "thw" for c in text) or len(set(text)) != len(text):
+        raise SystemExit("--wrap takes a non-empty string of distinct letters of t, h, w (e.g. t, hw, thw), got {!r}".format(text))
+    return tuple(int(c in text) for c in "thw")
+
+
+def wrap_triple(wrap):
+    """The ring flags as a triple of 0 / 1, or None for no ring at all (None, or all zero)."""
+    if wrap is None:
+        return None
+    w = tuple(int(bool(e)) for e in wrap)
+    if len(w) != 3:
+        raise ValueError("wrap must be three flags (t, h, w), got %r" % (wrap,))
+    return w if any(w) else None
+
+
+def patchnn_wrap_pad(vol, patch, wrap):
+    """The circular pad of a volume [T,H,W,3] (images [H,W,3]: T = 1) whose axes flagged in wrap = (wt, wh, ww) are rings: the
+    first p - 1 slices appended along every ring axis, in the order t, y, x.  The dense patch grid of the result is the periodic
+    grid of the volume, patch for patch (include/hpvg.h), so any search can run on it unchanged.  torch tensor, any device."""
+    w = wrap_triple(wrap)
+    if w is None:
+        return vol
+    image = vol.dim() == 3
+    out = vol[None] if image else vol
+    for ax in range(3):
+        p = int(patch[ax])
+        if w[ax] and p > 1:
+            if out.shape[ax] < p:
+                raise ValueError("patchnn_wrap_pad: a ring of %d is shorter than the patch side %d" % (out.shape[ax], p))
+            out = torch.cat([out, out.narrow(ax, 0, p - 1)], ax)
+    out = out.contiguous()
+    return out[0] if image else out

@@ -358,6 +358,40 @@ size_t hpvg_patchmatch_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, 
 int hpvg_patchmatch_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
                        const int* patch, const float* rweight, const int* nn_init, int iters, long seed, int* d2, int* nn,
                        float* score, void* ws, size_t ws_bytes, void* stream);
+/* ---- rings (generate_patchnn --wrap: seamless video loops and tileable samples).  A sample volume [T][H][W][3] uint8, a patch
+ * (pt, ph, pw) and ring flags wrap = (wt, wh, ww), each 0 / 1 (host array of 3 ints; NULL = all zero).
+ *   Periodic grid: along an axis of S voxels and patch side p the grid has S positions if the axis is a ring, else S - p + 1;
+ * the patch at grid coordinate g covers the voxel coordinates (g + d) mod S, d = 0 .. p - 1, on a ring axis and g + d
+ * elsewhere.  Raster order (t, y, x).  A flag on an axis with p = 1 is legal; only the neighbourhood rule of the PatchMatch
+ * below changes there.
+ *   Circular pad: the volume with its first p - 1 slices appended along every ring axis, in the order t, y, x.  The dense patch
+ * grid of the padded volume is the periodic grid, patch for patch, so every search runs on padded volumes unchanged.  The real
+ * clip is never a ring: keys and values stay dense, non-wrapping grids.
+ *   The vote onto a ring.  (Tq, Hq, Wq) is the UNPADDED output and the query grid is its periodic grid, dense; nn: int32 with
+ * one entry per periodic-grid patch, indexing v's grid at rstride.  Per output voxel and channel sum and cnt run over all
+ * periodic-grid patches that cover the voxel (modulo S on ring axes), the offset inside the patch is the d above, and
+ * out = (2 sum + cnt) / (2 cnt) in integers.  Entries outside [0, Nr) are skipped; cnt == 0 takes fallback.  A gather, one thread
+ * per voxel: no atomics, no workspace, no host synchronisation.  Refusals (geometry of the unpadded volume, aliasing of out) are
+ * those of hpvg_patch_vote_u8; a flag other than 0 / 1 is HPVG_ERR_ARG.  All flags zero: bit for bit hpvg_patch_vote_u8 at
+ * qstride = (1, 1, 1).  (A vote into the padded volume cannot be folded back afterwards: it returns rounded means, not sums.) */
+int hpvg_patch_vote_wrap_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int* nn, int Tq, int Hq, int Wq, const int* patch,
+                            const int* rstride, const int* wrap, const unsigned char* fallback, unsigned char* out, void* stream);
+/* PatchMatch between rings: hpvg_patchmatch_u8 on volumes q and r that arrive ALREADY circularly padded by the caller; qwrap /
+ * rwrap (host arrays of 3 ints, 0 / 1, NULL = all zero) say which axes of the query / key PATCH GRID are rings.  (The forward
+ * search of a generator step has the padded guess as its query, the reverse search as its reference.)  The rule is that of
+ * hpvg_patchmatch_u8 with these changes only:
+ *   propagation, query side: on a qwrap axis the neighbour a + s e_ax is taken modulo the query grid side and is never skipped
+ * (on a side of 1 the neighbour is the patch itself);
+ *   propagation, key side: on an rwrap axis the candidate "neighbour's old match minus s e_ax" is taken modulo the key grid
+ * side; on other axes it is skipped when it leaves the grid;
+ *   random search: on an rwrap axis the candidate coordinate is taken modulo the key grid side (the non-negative modulus; the
+ * offsets reach R, which may exceed the side) instead of being clamped.
+ * Hash, start, order of candidates, keys and tie rule, Jacobi reads, the weights contract, refusals, launches and
+ * hpvg_patchmatch_ws_bytes() are unchanged; a flag other than 0 / 1 is HPVG_ERR_ARG.  Both flag arrays null or all zero: bit for
+ * bit hpvg_patchmatch_u8. */
+int hpvg_patchmatch_wrap_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
+                            const int* patch, const int* qwrap, const int* rwrap, const float* rweight, const int* nn_init,
+                            int iters, long seed, int* d2, int* nn, float* score, void* ws, size_t ws_bytes, void* stream);
 /* The copied regions ("chunks") of a nearest-neighbour field (evaluate --chunks).  nn: int32 [Nq] on the device over the query
  * patch grid qgrid = (gT, gH, gW), raster order (t, y, x), holding indices into the key patch grid rgrid = (kT, kH, kW),
  * Nr = kT kH kW; d2: int32 [Nq] or NULL.  qgrid / rgrid / qstride / rstride: host arrays of 3 ints.  Patch i at grid coordinate

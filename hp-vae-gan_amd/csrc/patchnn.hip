@@ -68,6 +68,9 @@
 // Precision / recall / density / coverage of patch sets (the evaluate program's --prdc): patchnn_prdc.inl, included at the end,
 // puts two more epilogues on kernel 2's tile: the k smallest distances of every patch within its own volume, and the number
 // of keys whose per-key radius reaches a query.
+//
+// The pyramid's resize (generate_patchnn --antialias / --t-ratio, evaluate --scales): volresize.inl, included at the end, an exact
+// antialiased resize of a uint8 volume in integer arithmetic, one gather kernel of its own.
 #include <limits.h>
 
 #include <type_traits>
@@ -1201,3 +1204,6 @@ int hpvg_nnf_chunks_i32(const int* nn, const int* d2, int max_d2, const int* qgr
 
 // generate_patchnn --search patchmatch: the deterministic approximate search (its own kernel; shares the geometry above)
 #include "patchmatch.inl"
+
+// generate_patchnn --antialias / --t-ratio, evaluate --scales: the exact antialiased volume resize (its own gather kernel)
+#include "volresize.inl"

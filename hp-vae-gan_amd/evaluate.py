@@ -2,7 +2,8 @@
 `--samples S.npy --real R.npy` without an experiment: patch nearest-neighbour coherence / completeness, nn_unique_frac and
 diversity of the samples against the training clip, written to metrics.json; with --chunks also the copied-region statistics of
 the nearest-neighbour field; with --prdc K also the patch sets' precision, recall, density and coverage at k = K; with --wrap AXES
-also seam_coherence, the coherence of the patches that cross the seam of samples that are rings along those axes."""
+also seam_coherence, the coherence of the patches that cross the seam of samples that are rings along those axes; with --scales K
+also coherence / completeness at K coarser scales of an antialiased pyramid (the patch metrics alone are blind to layout)."""
 import argparse
 import json
 import math
@@ -50,7 +51,58 @@ def evaluate_parser():
     p.add_argument('--wrap', default=None, metavar='AXES', help='the samples are rings along these axes (distinct letters of t, h, w; '
                    'what `generate_patchnn --wrap` makes): also report seam_coherence, the coherence of the patches that cross a seam '
                    '(last slice into first).  --stride must be 1 on a ring axis; no t for images')
+    p.add_argument('--scales', type=_scales_k, default=0, metavar='K', help='also report coherence and completeness at K coarser '
+                   'scales: for k = 1..K every sample and the real volume are resized, each from its own full size, to (T, round(H R^k), '
+                   'round(W R^k)) by the exact antialiased resize and searched with the same patch and --stride (default 0: off)')
+    p.add_argument('--scale-ratio', type=_scale_ratio, default=None, metavar='R', help='with --scales (required): the size ratio '
+                   'between two scales, in (0, 1) (default {})'.format(SCALE_RATIO))
     return p
+
+
+SCALE_RATIO = 0.5   # --scale-ratio
+
+
+def _scales_k(text):
+    v = int(text)
+    if v < 0:
+        raise argparse.ArgumentTypeError("must be >= 0 (0: off), got %s" % text)
+    return v
+
+
+def _scale_ratio(text):
+    v = float(text)
+    if not 0.0 < v < 1.0:
+        raise argparse.ArgumentTypeError("must lie in (0, 1), got %s" % text)
+    return v
+
+
+def scale_sizes(size, K, ratio=SCALE_RATIO):
+    """[(T, H_k, W_k)] for k = 1..K of a (T, H, W) volume: H_k = floor(H ratio^k + 0.5), W_k alike; T is kept.  Host only."""
+    T, H, W = (int(e) for e in size)
+    return [(T, int(math.floor(H * float(ratio) ** k + 0.5)), int(math.floor(W * float(ratio) ** k + 0.5))) for k in range(1, int(K) + 1)]
+
+
+def scales_check(K, ratio=None, sizes=(), patch=None):
+    """Refuse what --scales cannot score, as the program's exit: --scale-ratio without --scales, K < 0, a ratio outside (0, 1)
+    and, once the volumes' sizes and the patch are known, a K whose coarsest volume is smaller than the patch (the message
+    names the largest K that fits).  Returns the ratio in force (None when off)."""
+    K = int(K or 0)
+    if K < 0:
+        raise SystemExit("evaluate: --scales K must be >= 0, got {}".format(K))
+    if K == 0:
+        if ratio is not None:
+            raise SystemExit("evaluate: --scale-ratio needs --scales K")
+        return None
+    ratio = SCALE_RATIO if ratio is None else float(ratio)
+    if not 0.0 < ratio < 1.0:
+        raise SystemExit("evaluate: --scale-ratio must lie in (0, 1), got {}".format(ratio))
+    if patch is not None:
+        fits = lambda k: all(all(s >= p for s, p in zip(scale_sizes(size, k, ratio)[-1], patch)) for size in sizes)   # noqa: E731
+        if not fits(K):
+            best = max([k for k in range(1, K) if fits(k)], default=0)
+            raise SystemExit("evaluate: --scales {}: the volume at scale {} is smaller than the patch {}; the largest K that fits "
+                             "is {}".format(K, K, list(patch), best))
+    return ratio
 
 
 def _nonneg_float(text):
@@ -201,7 +253,8 @@ def source_colours(nn, ref_grid):
 
 
 def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1), max_samples=None, out=None, swd=0, swd_seed=0,
-             chunks=False, chunk_tol=None, save_chunks=False, prdc=0, prdc_floor=None, save_prdc=False, wrap=None):
+             chunks=False, chunk_tol=None, save_chunks=False, prdc=0, prdc_floor=None, save_prdc=False, wrap=None, scales=0,
+             scale_ratio=None):
     """Score `samples` against the real volume; writes metrics.json (and, with exp_dir, the real volume used as real.npy) into
     `out` and returns the metrics.  swd > 0: also the sliced Wasserstein patch distance over that many directions.
     chunks (implied by chunk_tol / save_chunks): also the copied-region statistics of the coherence direction's field.
@@ -209,7 +262,13 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
     does nothing without it).  wrap: the --wrap string (letters of t, h, w): the samples are rings along those axes, and every
     sample also gets seam_patches (the patches of its periodic grid, at `stride`, that cross a seam) and seam_coherence (the
     mean over those of the exact nearest distance to the real volume's dense patches, over D * 255^2; None without such
-    patches), searched on the circularly padded sample with ops.patch_nn_subset."""
+    patches), searched on the circularly padded sample with ops.patch_nn_subset.
+    scales = K > 0 (scale_ratio, default 0.5, is refused without it): for k = 1..K every sample and the real volume are resized
+    from their own full sizes by ops.volume_resize_u8 to scale_sizes() and coherence / completeness are computed there with the
+    same patch and stride; every per_sample entry gains `scales` (a list of scale, size, coherence, completeness) and the
+    metrics `scales` (the means and Nq / Nr per scale), scale_ratio and scales_seconds."""
+    scales = int(scales or 0)
+    scale_ratio = scales_check(scales, scale_ratio)
     rings = None
     if wrap is not None:
         try:
@@ -254,6 +313,17 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
     coh_counts = ops.patch_nn_counts(vol(samples_dev[0]), vol(real_dev), patch, qstride=stride)
     com_counts = ops.patch_nn_counts(vol(real_dev), vol(samples_dev[0]), patch, qstride=stride)
     D = coh_counts[2]
+    if scales:
+        scales_check(scales, scale_ratio, (vol(samples_dev[0]), vol(real_dev)), patch)
+        as_vol = (lambda t: t) if video else (lambda t: t[None])
+        ssizes, rsizes = scale_sizes(vol(samples_dev[0]), scales, scale_ratio), scale_sizes(vol(real_dev), scales, scale_ratio)
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        k0.record()
+        real_scaled = [ops.volume_resize_u8(as_vol(real_dev), s) for s in rsizes]
+        k1.record()
+        k1.synchronize()
+        scales_seconds = k0.elapsed_time(k1) / 1e3
+        scale_counts = [ops.patch_nn_counts(s, r, patch, qstride=stride) for s, r in zip(ssizes, rsizes)]
     chunks = bool(chunks or chunk_tol is not None or save_chunks)
     if chunks:
         ref_grid = tuple(v - p + 1 for v, p in zip(vol(real_dev), patch))   # the real side is dense
@@ -302,6 +372,17 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
                 s1.synchronize()
                 seam_seconds += s0.elapsed_time(s1) / 1e3
                 per_sample[-1]["seam_coherence"] = patch_score(d2s, D)
+        if scales:
+            k0.record()
+            rows = []
+            for k, (ss, rk) in enumerate(zip(ssizes, real_scaled)):
+                sk = ops.volume_resize_u8(as_vol(smp), ss)
+                rows.append((k + 1, ss, ops.patch_nn(sk, rk, patch, qstride=stride)[0], ops.patch_nn(rk, sk, patch, qstride=stride)[0]))
+            k1.record()
+            k1.synchronize()
+            scales_seconds += k0.elapsed_time(k1) / 1e3
+            per_sample[-1]["scales"] = [{"scale": k, "size": list(ss if video else ss[1:]), "coherence": patch_score(dc, D),
+                                         "completeness": patch_score(dr, D)} for k, ss, dc, dr in rows]
         if chunks:
             c0.record()
             labels, sizes, stats = ops.nnf_chunks(nnc, ref_grid, qstride=stride, d2=None if max_d2 is None else d2c, max_d2=max_d2)
@@ -384,20 +465,29 @@ def evaluate(exp_dir=None, samples=None, real=None, patch=None, stride=(1, 1, 1)
         metrics.update({"seam_coherence": None if any(v is None for v in vals) else sum(vals) / n, "wrap": wrap,
                         "seam_seconds": seam_seconds})
         seam_text = " seam_coherence {}".format("n/a" if metrics["seam_coherence"] is None else "{:.6f}".format(metrics["seam_coherence"]))
+    scales_text = ""
+    if scales:
+        metrics["scales"] = [{"scale": k + 1, "size": list(ssizes[k] if video else ssizes[k][1:]),
+                              "real_size": list(rsizes[k] if video else rsizes[k][1:]),
+                              "coherence": sum(p["scales"][k]["coherence"] for p in per_sample) / n,
+                              "completeness": sum(p["scales"][k]["completeness"] for p in per_sample) / n,
+                              "Nq": scale_counts[k][0], "Nr": scale_counts[k][1]} for k in range(scales)]
+        metrics.update({"scale_ratio": scale_ratio, "scales_seconds": scales_seconds})
+        scales_text = "".join(" coherence@{} {:.6f}".format(s["scale"], s["coherence"]) for s in metrics["scales"])
     with open(os.path.join(out, 'metrics.json'), 'w') as f:
         json.dump(metrics, f, indent=1, sort_keys=True)
-    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{}{}{} "
+    print("evaluate: {} samples, patch {} stride {}: coherence {:.6f} completeness {:.6f} nn_unique_frac {:.4f} diversity {}{}{}{}{}{} "
           "({:.3f} s in patch_nn) -> {}".format(n, list(patch), list(stride), metrics["coherence"], metrics["completeness"],
                                                metrics["nn_unique_frac"],
                                                "n/a" if metrics["diversity"] is None else "{:.4f}".format(metrics["diversity"]),
-                                               swd_text, chunk_text, prdc_text, seam_text, seconds, os.path.join(out, 'metrics.json')))
+                                               swd_text, chunk_text, prdc_text, seam_text, scales_text, seconds, os.path.join(out, 'metrics.json')))
     return metrics
 
 
 def main(argv=None):
     a = evaluate_parser().parse_args(argv)
     evaluate(a.exp_dir, a.samples, a.real, a.patch, a.stride, a.max_samples, a.out, a.swd, a.swd_seed, a.chunks, a.chunk_tol,
-             a.save_chunks, a.prdc, a.prdc_floor, a.save_prdc, a.wrap)
+             a.save_chunks, a.prdc, a.prdc_floor, a.save_prdc, a.wrap, a.scales, a.scale_ratio)
     return 0
 
 

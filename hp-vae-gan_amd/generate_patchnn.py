@@ -4,7 +4,9 @@ VGPNN); writes samples.npy, one GIF / PNG per sample and patchnn.json.  With `--
 the masked region of the clip (patch inpainting) and every other voxel stays as it is.  With `--search patchmatch` the levels
 above the coarsest search by a deterministic PatchMatch (linear in the patch count) instead of exhaustively.  With `--wrap AXES`
 (letters of t, h, w) the samples are rings along those axes: `--wrap t` makes clips whose last frame continues into the first
-(seamless loops), `--wrap hw` tileable textures."""
+(seamless loops), `--wrap hw` tileable textures.  With `--antialias` every resize of the run is the exact antialiased integer
+resize (ops.volume_resize_u8: the coarse levels are low-passed, not subsampled), and with `--t-ratio R` the pyramid also
+scales T (a spatio-temporal pyramid)."""
 import argparse
 import json
 import math
@@ -23,10 +25,10 @@ from .programs import (default_patch, gpu_device, load_opt, load_u8_frames, pars
 
 # The training-free counterpart of the trained generator: GPNN (Granot et al., "Drop the GAN", CVPR 2022) and its video form
 # VGPNN (Haim et al., ECCV 2022) on the exact patch engine of `evaluate`.  Everything is a uint8 volume [T,H,W,3]; an image is
-# the volume with T = 1.  Coarse to fine over a spatial pyramid of the real volume (T is kept; a spatio-temporal pyramid is
-# not built), every level repeats one step: search, for each patch of the current guess, the key patch that minimises
-# d2 / (alpha_abs + the key's distance to ITS nearest guess patch) (the completeness normalisation: key patches the guess
-# does not use yet become cheap), then vote the value patches of the winners into the next guess.
+# the volume with T = 1.  Coarse to fine over a pyramid of the real volume (spatial by default: T is kept; --t-ratio scales T
+# too, VGPNN's spatio-temporal pyramid), every level repeats one step: search, for each patch of the current guess, the key
+# patch that minimises d2 / (alpha_abs + the key's distance to ITS nearest guess patch) (the completeness normalisation: key
+# patches the guess does not use yet become cheap), then vote the value patches of the winners into the next guess.
 PM_ITERS = 4        # --pm-iters: a warm-started search at the finest level is within 1.05 of the exact mean d2 after 4
 PM_FROM_LEVEL = 1   # --pm-from-level
 PM_SEED_STRIDE = 1000003
@@ -72,6 +74,14 @@ def generate_patchnn_parser():
     p.add_argument('--wrap', default=None, metavar='AXES', help='make the samples rings along these axes: distinct letters of t, h, w '
                    '(t: a clip that loops without a seam; hw: a texture that tiles).  The patches that cross a seam are searched '
                    'and voted like any others; the real clip stays as it is.  Not with --mask; no t for an image')
+    p.add_argument('--antialias', action='store_true', help='every resize of the run (real levels, blurred keys, the guess '
+                   'between levels, the coarsest guess under --size, the resize of --mask) is the exact antialiased integer resize: '
+                   'a coarse voxel averages everything it stands for under a triangle filter; upsizing stays linear interpolation')
+    p.add_argument('--t-ratio', type=float, default=1.0, metavar='R', help='also scale T between two levels of the pyramid: the level '
+                   'k steps below the finest has min(T, max(F, round(T R^k))) frames, F = --min-frames; R in (0, 1], 1.0 keeps T.  '
+                   'Not for an image, and not with --mask (the mask resize keeps T)')
+    p.add_argument('--min-frames', type=int, default=None, metavar='F', help='no level of a --t-ratio pyramid has fewer frames '
+                   '(default: patch T + 1; at least patch T); only with --t-ratio below 1')
     return p
 
 
@@ -81,10 +91,29 @@ def patchnn_wrap_grid(size, patch, wrap):
     return tuple(int(s) if f else int(s) - int(p) + 1 for s, p, f in zip(size, patch, w))
 
 
-def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7)):
+def patchnn_level_frames(T, k, t_ratio=1.0, min_frames=None, patch_t=3):
+    """Frames of the level k steps below the finest of a T-frame volume: min(T, max(F, floor(T t_ratio^k + 0.5))) with
+    F = min_frames (default patch_t + 1); T itself for t_ratio == 1.0.  Refuses t_ratio outside (0, 1], min_frames < patch_t and
+    min_frames with t_ratio == 1.0.  Host only."""
+    T, t_ratio = int(T), float(t_ratio)
+    if not 0.0 < t_ratio <= 1.0:
+        raise ValueError("patchnn_pyramid_sizes: t_ratio must lie in (0, 1], got %r" % (t_ratio,))
+    if t_ratio == 1.0:
+        if min_frames is not None:
+            raise ValueError("patchnn_pyramid_sizes: min_frames needs a t_ratio below 1")
+        return T
+    F = int(patch_t) + 1 if min_frames is None else int(min_frames)
+    if F < int(patch_t):
+        raise ValueError("patchnn_pyramid_sizes: min_frames must be at least the patch's T = %d, got %d" % (int(patch_t), F))
+    return min(T, max(F, int(math.floor(T * t_ratio ** k + 0.5))))
+
+
+def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7), t_ratio=1.0, min_frames=None):
     """[(T, H, W)] of the pyramid of a (T, H, W) volume from coarse to fine: level l of L has (H, W) scaled by ratio^(L-1-l) and
     rounded (halves up), the finest is the volume itself and T is kept.  L is the largest count whose coarsest level has
-    min(H, W) >= min_size (at least 1).  Refuses a coarsest level smaller than the patch.  Host only."""
+    min(H, W) >= min_size (at least 1).  Refuses a coarsest level smaller than the patch.  Host only.
+    t_ratio < 1 (a spatio-temporal pyramid): the level k = L-1-l steps below the finest has patchnn_level_frames(T, k, t_ratio,
+    min_frames, patch T) frames; L is still decided by the spatial sides.  t_ratio == 1.0: exactly the sizes above."""
     T, H, W = (int(e) for e in shape)
     ratio = float(ratio)
     if not 0.0 < ratio < 1.0:
@@ -92,8 +121,11 @@ def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7)):
     if min(T, H, W) < 1:
         raise ValueError("patchnn_pyramid_sizes: bad volume %s" % ((T, H, W),))
 
+    patchnn_level_frames(T, 0, t_ratio, min_frames, patch[0])   # the refusals, whatever L turns out to be
+
     def at(k):
-        return T, int(math.floor(H * ratio ** k + 0.5)), int(math.floor(W * ratio ** k + 0.5))
+        return (patchnn_level_frames(T, k, t_ratio, min_frames, patch[0]), int(math.floor(H * ratio ** k + 0.5)),
+                int(math.floor(W * ratio ** k + 0.5)))
     L = 1
     while min(at(L)[1:]) >= max(int(min_size), 1):
         L += 1
@@ -104,22 +136,26 @@ def patchnn_pyramid_sizes(shape, ratio, min_size, patch=(3, 7, 7)):
     return sizes
 
 
-def _resize_u8(vol, size):
-    """uint8 [T,H,W,3] -> uint8 [*size, 3]: the trilinear align-corners resize (ops.UpsampleAC, fp32), rounded and clamped."""
+def _resize_u8(vol, size, antialias=False):
+    """uint8 [T,H,W,3] -> uint8 [*size, 3]: the trilinear align-corners resize (ops.UpsampleAC, fp32), rounded and clamped.
+    antialias: the exact antialiased integer resize instead (ops.volume_resize_u8, one launch)."""
     size = tuple(int(e) for e in size)
     if tuple(vol.shape[:3]) == size:
         return vol.contiguous()
+    if antialias:
+        return ops.volume_resize_u8(vol, size)
     x = vol.permute(3, 0, 1, 2)[None].to(torch.float32).contiguous()
     with torch.no_grad():
         y = ops.UpsampleAC.apply(x, size, None, 0.0)
     return torch.round(y).clamp_(0, 255).to(torch.uint8)[0].permute(1, 2, 3, 0).contiguous()
 
 
-def patchnn_real_levels(real, sizes):
+def patchnn_real_levels(real, sizes, antialias=False):
     """(levels, keys) of the real volume [T,H,W,3]: levels[l] is the full-size volume resized to sizes[l]; keys[l] (l > 0) is
-    levels[l-1] resized to sizes[l], the blurred keys of the first step of level l (keys[0] is levels[0])."""
-    levels = [_resize_u8(real, s) for s in sizes]
-    keys = [levels[0]] + [_resize_u8(levels[l - 1], sizes[l]) for l in range(1, len(sizes))]
+    levels[l-1] resized to sizes[l], the blurred keys of the first step of level l (keys[0] is levels[0]).  antialias: both by
+    the exact antialiased resize (_resize_u8)."""
+    levels = [_resize_u8(real, s, antialias) for s in sizes]
+    keys = [levels[0]] + [_resize_u8(levels[l - 1], sizes[l], antialias) for l in range(1, len(sizes))]
     return levels, keys
 
 
@@ -213,7 +249,8 @@ def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, se
 
 
 def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, alpha=0.005, seed=0, index=0,
-                       pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL, wrap=None):
+                       pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL, wrap=None, antialias=False,
+                       t_ratio=1.0, min_frames=None):
     """One sample of the uint8 device volume `real` ([T,H,W,3]; images [H,W,3]) -> (sample, mean final score).  size: the
     sample's (T, H, W) (default real's).  The coarsest guess is real level 0 (resized to the sample's coarsest size) plus
     noise * 255 * N(0, 1) drawn under torch.manual_seed(seed + index); level 0 runs `iters` steps with keys = values = real
@@ -226,27 +263,31 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
     The default 'exact' computes what it always did.
     wrap = (wt, wh, ww): the sample is a ring along the flagged axes - every step is patchnn_refine(..., wrap=wrap) and the
     PatchMatch fields live on the guess's periodic grids.  The resize between levels and the coarsest noise stay as they are
-    (not periodic): the steps that follow re-vote every voxel."""
+    (not periodic): the steps that follow re-vote every voxel.
+    antialias: every resize (real levels, blurred keys, coarsest guess, the guess between levels) is ops.volume_resize_u8.
+    t_ratio / min_frames: the pyramid scales T as well (patchnn_pyramid_sizes); a sample of another size scales its own T by the
+    same rule.  A given `pyramid` must have been made with the same three settings."""
     wrap = _wrap3(wrap)
     image = real.dim() == 3
     vol = real[None] if image else real
     patch = tuple(patch) if patch else default_patch(not image)
     if pyramid is None:
-        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
-        pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch, t_ratio, min_frames)
+        pyramid = (sizes,) + patchnn_real_levels(vol, sizes, antialias)
     sizes, levels, keys = pyramid
     L = len(sizes)
     if size is None or tuple(size) == tuple(vol.shape[:3]):
         qsizes = sizes
     else:
         St, Sh, Sw = (int(e) for e in size)
-        qsizes = [(St, int(math.floor(Sh * ratio ** (L - 1 - l) + 0.5)), int(math.floor(Sw * ratio ** (L - 1 - l) + 0.5)))
+        qsizes = [(patchnn_level_frames(St, L - 1 - l, t_ratio, min_frames, patch[0]),
+                   int(math.floor(Sh * ratio ** (L - 1 - l) + 0.5)), int(math.floor(Sw * ratio ** (L - 1 - l) + 0.5)))
                   for l in range(L)]
         if any(s < p for s, p in zip(qsizes[0], patch)):
             raise ValueError("patchnn_synthesize: the sample's coarsest level %s is smaller than the patch %s" % (qsizes[0], patch))
     alpha_abs = float(alpha) * 3 * patch[0] * patch[1] * patch[2] * 255 * 255
     iters = max(int(iters), 1)
-    q = _resize_u8(levels[0], qsizes[0])
+    q = _resize_u8(levels[0], qsizes[0], antialias)
     if noise:
         torch.manual_seed(int(seed) + int(index))
         with ops.noise_stream(q.device):
@@ -256,7 +297,7 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
     score = None
     for l in range(L):
         if l > 0:
-            q = _resize_u8(q, qsizes[l])
+            q = _resize_u8(q, qsizes[l], antialias)
             if state is not None:
                 qf, qt = (patchnn_wrap_grid(qsizes[k], patch, wrap) for k in (l - 1, l))
                 rf, rt = (tuple(s - p + 1 for s, p in zip(sizes[k], patch)) for k in (l - 1, l))
@@ -344,7 +385,7 @@ def patchnn_inpaint_step(query, keys, values, mask, patch, qsel, rsel, return_sc
 
 
 def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, seed=0, index=0, pyramid=None,
-                    return_levels=False):
+                    return_levels=False, antialias=False):
     """One completion of the hole `mask` (bool [T,H,W], images [H,W]; True = hole) of the uint8 device volume `real` ([T,H,W,3];
     images [H,W,3]) -> (sample, mean d2 of the last step's queries[, every level's result]).  Sizes, real levels and blurred
     keys are patchnn_synthesize's.  The coarsest guess is real level 0 with the hole set to the per-channel mean of the known
@@ -352,7 +393,9 @@ def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, n
     under torch.manual_seed(seed + index) as patchnn_synthesize draws it.  Every step is patchnn_inpaint_step with the level's
     lists (patchnn_inpaint_plan): the plain nearest neighbour - a completeness term would pull every key of the clip into the
     hole.  Between levels the hole is the previous result resized and everything else real level l.  pyramid: a
-    (sizes, levels, keys) or (sizes, levels, keys, plan) tuple to reuse between samples."""
+    (sizes, levels, keys) or (sizes, levels, keys, plan) tuple to reuse between samples.  antialias: the real levels, the keys
+    and the resize between levels are ops.volume_resize_u8, whose footprint is exactly the mask resize's connection rule: M_l
+    covers every voxel that level l's resize of the full-size volume read, B_l every voxel the blurred keys read."""
     image = real.dim() == 3
     vol = real[None] if image else real
     if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != tuple(real.shape[:-1]) or \
@@ -364,7 +407,7 @@ def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, n
     patch = tuple(patch) if patch else default_patch(not image)
     if pyramid is None:
         sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
-        pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+        pyramid = (sizes,) + patchnn_real_levels(vol, sizes, antialias)
     sizes, levels, keys = pyramid[:3]
     plan = pyramid[3] if len(pyramid) > 3 else patchnn_inpaint_plan(mask, sizes, patch)
     iters = max(int(iters), 1)
@@ -382,7 +425,7 @@ def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, n
     score, results = None, []
     for l, lv in enumerate(plan):
         if l > 0:
-            q = torch.where(lv["mask"][..., None], _resize_u8(q, sizes[l]), levels[l])
+            q = torch.where(lv["mask"][..., None], _resize_u8(q, sizes[l], antialias), levels[l])
         for it in range(iters):
             first = l > 0 and it == 0
             last = l == len(plan) - 1 and it == iters - 1
@@ -431,7 +474,7 @@ def _refuse_trivial_mask(forms):
 
 def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
                      min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None, search='exact',
-                     pm_iters=None, pm_from_level=None, wrap=None):
+                     pm_iters=None, pm_from_level=None, wrap=None, antialias=False, t_ratio=1.0, min_frames=None):
     """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
     patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample).  mask: the
     path of a hole mask of the real volume; the samples are then completions of the hole (patchnn_inpaint), land in
@@ -440,7 +483,24 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
     search from level pm_from_level (default 1) on; patchnn.json then also records search, pm_iters and pm_from_level.  Not
     with a mask (the subset search has no PatchMatch form), and the two pm_* settings only with it.  wrap: the --wrap string
     (letters of t, h, w): the samples are rings along those axes (patchnn_synthesize's wrap); patchnn.json then records it.  Not
-    with a mask, and no t for an image."""
+    with a mask, and no t for an image.  antialias: every resize is ops.volume_resize_u8.  t_ratio < 1 (with min_frames): the
+    pyramid scales T too; not for an image and not with a mask.  patchnn.json records antialias when it is set, and t_ratio and
+    min_frames (the value in force) when t_ratio is below 1."""
+    t_ratio = 1.0 if t_ratio is None else float(t_ratio)
+    if not 0.0 < t_ratio <= 1.0:
+        raise SystemExit("generate_patchnn: --t-ratio must lie in (0, 1], got {}".format(t_ratio))
+    if t_ratio == 1.0:
+        if min_frames is not None:
+            raise SystemExit("generate_patchnn: --min-frames needs --t-ratio below 1")
+    else:
+        if image_path is not None:
+            raise SystemExit("generate_patchnn: --t-ratio needs a clip: an image has no time axis")
+        if mask is not None:
+            raise SystemExit("generate_patchnn: --t-ratio does not combine with --mask: the mask resize (patchnn_mask_resize) "
+                             "keeps T and refuses another")
+        if min_frames is not None and int(min_frames) < (int(patch[0]) if patch else default_patch(True)[0]):
+            raise SystemExit("generate_patchnn: --min-frames must be at least the patch's T = {}, got {}".format(
+                int(patch[0]) if patch else default_patch(True)[0], min_frames))
     rings = None
     if wrap is not None:
         try:
@@ -499,16 +559,18 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
     image = real.dim() == 3
     if image and rings is not None and rings[0]:
         raise SystemExit("generate_patchnn: --wrap t needs a clip: an image has no time axis")
+    if image and t_ratio != 1.0:
+        raise SystemExit("generate_patchnn: --t-ratio needs a clip: an image has no time axis")
     vol = real[None] if image else real
     patch = tuple(patch) if patch else default_patch(not image)
     size = tuple(size) if size else tuple(vol.shape[:3])
     try:
-        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch)
+        sizes = patchnn_pyramid_sizes(vol.shape[:3], ratio, min_size, patch, t_ratio, min_frames)
     except ValueError as e:
         raise SystemExit("generate_patchnn: {}".format(e))
     if image and size[0] != 1:
         raise SystemExit("generate_patchnn: an image's --size has T = 1")
-    pyramid = (sizes,) + patchnn_real_levels(vol, sizes)
+    pyramid = (sizes,) + patchnn_real_levels(vol, sizes, antialias)
     if mask is not None:
         hole = pick_mask(forms, vol.shape[:3])
         _refuse_trivial_mask([hole])
@@ -527,11 +589,15 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         e0.record()
         try:
             if mask is not None:
-                smp, score = patchnn_inpaint(vol, hole, patch, ratio, min_size, iters, noise, seed, i, pyramid)
+                smp, score = patchnn_inpaint(vol, hole, patch, ratio, min_size, iters, noise, seed, i, pyramid, antialias=antialias)
             else:
                 pm = {"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level} if search == "patchmatch" else {}
                 if rings is not None:
                     pm["wrap"] = rings
+                if antialias:
+                    pm["antialias"] = True
+                if t_ratio != 1.0:
+                    pm.update({"t_ratio": t_ratio, "min_frames": min_frames})
                 smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid, **pm)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
@@ -556,6 +622,10 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         info.update({"search": search, "pm_iters": pm_iters, "pm_from_level": pm_from_level})
     if wrap is not None:
         info["wrap"] = wrap
+    if antialias:
+        info["antialias"] = True
+    if t_ratio != 1.0:
+        info.update({"t_ratio": t_ratio, "min_frames": patch[0] + 1 if min_frames is None else int(min_frames)})
     with open(os.path.join(out, 'patchnn.json'), 'w') as f:
         json.dump(info, f, indent=1, sort_keys=True)
     print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
@@ -566,7 +636,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
 def main(argv=None):
     a = generate_patchnn_parser().parse_args(argv)
     generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
-                     a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level, a.wrap)
+                     a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level, a.wrap, a.antialias, a.t_ratio,
+                     a.min_frames)
     return 0
 
 

@@ -1680,6 +1680,42 @@ def patch_vote(values_u8, nn, patch, out_shape, fallback_u8, qstride=(1, 1, 1), 
     return out[0] if image else out
 
 
+def volume_resize_check(src_size, out_size):
+    """(Dmax, reads) of a volume_resize_u8 call from (T, H, W) = src_size to out_size: the largest denominator over the outputs
+    and the largest number of source voxels one output reads (hpvg_volume_resize_check; host only).  Raises on a refusal."""
+    out = (ctypes.c_long * 2)()
+    call("hpvg_volume_resize_check", *_triple(src_size, "src_size", "volume_resize"), *_triple(out_size, "out_size", "volume_resize"), out)
+    return out[0], out[1]
+
+
+def volume_resize_u8(vol_u8, size):
+    """The exact antialiased resize of a uint8 device volume [T,H,W,3] to (T, H, W) = size (hpvg_volume_resize_u8): per axis the
+    integer weights max(0, R - |i (O - 1) - o (S - 1)|), R = max(O - 1, S - 1) - linear align-corners interpolation when
+    upsizing, the triangle filter over everything an output voxel stands for when downsizing - and one rounding (halves up) of
+    the separable weighted mean.  An image [H,W,3] is the volume with T = 1 and takes a size of 2 entries (or 3 with T = 1).
+    An equal size returns a contiguous copy.  Returns a new uint8 tensor."""
+    v = vol_u8
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or v.dim() not in (3, 4) or v.shape[-1] != 3:
+        raise RuntimeError("volume_resize_u8: the volume must be uint8 [T,H,W,3] or [H,W,3], got %s %s"
+                           % (getattr(v, "dtype", type(v)), tuple(getattr(v, "shape", ()))))
+    image = v.dim() == 3
+    size = tuple(int(e) for e in size)
+    if len(size) not in ((2, 3) if image else (3,)) or (image and len(size) == 3 and size[0] != 1):
+        raise RuntimeError("volume_resize_u8: size must be (T, H, W)%s, got %s" % (" or (H, W) with T = 1" if image else "", size))
+    if image and len(size) == 2:
+        size = (1,) + size
+    src = _c(v[None] if image else v)
+    ptr(src)   # refuses a host tensor by name
+    sg = tuple(src.shape[:3])
+    volume_resize_check(sg, size)   # refuses bad sizes by name
+    if sg == size:
+        out = src.clone()
+    else:
+        out = torch.empty(size + (3,), dtype=torch.uint8, device=src.device)
+        call("hpvg_volume_resize_u8", ptr(src), *sg, ptr(out), *size, stream())
+    return out[0] if image else out
+
+
 # one hpvg_patchproj_hist_u8 launch fills at most this many bytes of histogram: the atomics' footprint stays within the 256 MB
 # last-level cache, and the benchmarked case (512 directions at 3 x 7 x 7: 231 MB) is still one launch.  More directions go in
 # chunks of whole 128-direction tiles (one direction at a time where a single histogram row passes the cap), each chunk packing

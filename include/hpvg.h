@@ -392,6 +392,25 @@ int hpvg_patch_vote_wrap_u8(const unsigned char* v, int Tr, int Hr, int Wr, cons
 int hpvg_patchmatch_wrap_u8(const unsigned char* q, int Tq, int Hq, int Wq, const unsigned char* r, int Tr, int Hr, int Wr,
                             const int* patch, const int* qwrap, const int* rwrap, const float* rweight, const int* nn_init,
                             int iters, long seed, int* d2, int* nn, float* score, void* ws, size_t ws_bytes, void* stream);
+/* ---- the pyramid's resize (generate_patchnn --antialias / --t-ratio, evaluate --scales): an exact, antialiased resize of a
+ * uint8 volume src [Ts][Hs][Ws][3] to out [To][Ho][Wo][3], separable in definition, with a single rounding.
+ *   Weights, per axis of S source and O output positions: R = max(O - 1, S - 1) and w(o, i) = max(0, R - |i (O - 1) - o (S - 1)|),
+ * an integer; an axis with S == O is the identity (w = 1 for i == o, else 0).  So O == 1 averages the whole axis, S == 1
+ * copies, O > S is linear align-corners interpolation, and O < S is the triangle filter of half-width (S - 1) / (O - 1) source
+ * voxels around the align-corners centre o (S - 1) / (O - 1), normalised by the weights that fall inside the volume.  w > 0
+ * exactly where |i (O - 1) - o (S - 1)| < R: the connection rule of the generator's mask resize (patchnn_mask_resize).
+ *   Output, per voxel and channel: N = sum_{t,h,w} wt wh ww v, D = (sum wt)(sum wh)(sum ww), out = (2 N + D) / (2 D) in integer
+ * arithmetic (the weighted mean, halves rounded up).  Exact 64-bit sums: the result is a function of the inputs alone,
+ * independent of launch geometry and of how the sums are split.  Example: the axis 7 -> 4 on [0, 60, 120, 180, 240, 255, 255]
+ * gives [20, 120, 229, 255]; the weights of output 1 are [0, 3, 6, 3, 0, 0, 0].
+ *   HPVG_ERR_ARG: a side < 1.  HPVG_ERR_UNSUPPORTED: a volume of 2^31 voxels or more (the limit of the other uint8 volume
+ * entry points), or 511 Dmax >= 2^63 with Dmax the largest D over the outputs (the numerator 2 N + D must fit 64 bits). */
+/* host only: the refusals above; out2 (nullable) = Dmax and the largest number of source voxels one output reads */
+int hpvg_volume_resize_check(int Ts, int Hs, int Ws, int To, int Ho, int Wo, long* out2);
+/* The same refusals, before any launch; a null src or out, or out overlapping src (a gather: src is read while out is written)
+ * is HPVG_ERR_ARG.  One launch on `stream`, no workspace, no atomics, no host synchronisation. */
+int hpvg_volume_resize_u8(const unsigned char* src, int Ts, int Hs, int Ws, unsigned char* out, int To, int Ho, int Wo,
+                          void* stream);
 /* The copied regions ("chunks") of a nearest-neighbour field (evaluate --chunks).  nn: int32 [Nq] on the device over the query
  * patch grid qgrid = (gT, gH, gW), raster order (t, y, x), holding indices into the key patch grid rgrid = (kT, kH, kW),
  * Nr = kT kH kW; d2: int32 [Nq] or NULL.  qgrid / rgrid / qstride / rstride: host arrays of 3 ints.  Patch i at grid coordinate

@@ -859,6 +859,187 @@ __global__ __launch_bounds__(256, 2) void conv_narrow2_kernel(const ConvFwdArgs 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Narrow-output convolution with the TIME taps in N (3x3x3, Cout <= 4, Cin even, no prologue / mask).  conv_narrow2_kernel
+// makes one tile per output plane with K = (c, dt): every input plane is an A operand for three output planes - three
+// times the MFMAs a 64 -> 1 layer needs (9 of 32 columns used) and three fetches of every input plane.  Here one workgroup
+// owns (sample, row block, column band) and walks the INPUT planes t = 0 .. T-1; per plane and output channel o
+//     P[pos][(dt,dh,dw)] = sum_c x[c][t][pos] * w[o][c][dt][dh][dw]                (GEMM: M = window positions, K = Cin,
+// one 32-column tile holds the 27 taps of o), P goes through LDS, and the 9-term shifted sum S_dt of slice dt is added to the
+// accumulator of output plane tau = t + 1 - dt.  The three planes in flight live in registers of the thread that owns
+// the position (ring rA: tau = t - 1, rB: tau = t, rC: tau = t + 1); plane tau is finished with bias and LeakyReLU and
+// stored once, after input plane min(tau + 1, T - 1).  Fixed order (S_0, + S_1, + S_2, + bias), no atomics, no workspace.
+// Loads as in conv_narrow2_kernel: a lane's 16-byte load of four consecutive positions feeds four MFMAs, windows lie inside
+// the image, clamped rows are zeroed by select, no address outside the tensor is formed.  The weight fragments are read
+// from the narrow pack as it is (wn[kstep = 3 c' + dt][ntile][lane]; this kernel's lane (half, n = (dt, j)) reads the element
+// of pack column 9 o + j of k-step 3 s + dt, half-wave `half`): a few KB that stay in L1 / L2.
+struct NarrowTGeom {
+  int RS, Th, nth, nb, npos, G, pitch;
+  int ws[16], ob[16], on[16];  // per band: window start column, first output column, number of output columns
+};
+constexpr int NARROWT_PPT = 4;                  // outputs per thread: Th * (widest band) <= 256 * NARROWT_PPT
+constexpr size_t NARROWT_LDS_MAX = 76 * 1024;   // two workgroups per CU
+
+template <int COUT>
+__global__ __launch_bounds__(256, 2) void conv_narrowt_kernel(const ConvFwdArgs a, const NarrowTGeom g) {
+  typedef f32x4u AV;
+  constexpr int JB = 4, GP = 32 * JB, KC = 8, PPT = NARROWT_PPT;
+  constexpr int NTO = (9 * COUT + 31) / 32;   // column tiles of the pack
+  extern __shared__ __attribute__((aligned(16))) float P[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, l31 = lane & 31;
+  const long HW = (long)a.H * a.W;
+  const int RS = g.RS, pitch = g.pitch;
+  const int Ch = a.Cin >> 1;                  // k-steps: half-wave h of step s holds channel h * Ch + s
+
+  int r = hpvg_xcd_remap(blockIdx.x, gridDim.x);
+  const int band = r % g.nb; r /= g.nb;
+  const int th = r % g.nth;
+  const int b = r / g.nth;
+  const int h0 = th * g.Th, wsb = g.ws[band], ob = g.ob[band], on = g.on[band];
+  // loads: uniform base (sample, channel step, plane, window) + a 32-bit lane offset (half-wave's channel range, row, column;
+  // one sample is < 4 GB) - no per-load vector address arithmetic
+  const char* xb = reinterpret_cast<const char*>(a.x + (long)b * a.Cin * a.T * HW + wsb);
+  const unsigned lhalf = (unsigned)((long)half * Ch * a.T * HW);
+  const long cstep = a.T * HW * 4;            // bytes between channels
+
+  // this lane's column n = l31 = (dt, j): element of the pack per output channel (columns 27 .. 31 compute nothing that is kept)
+  const int dtn = l31 < 27 ? l31 / 9 : 0, j9 = l31 < 27 ? l31 - 9 * dtn : 0;
+  int woff[COUT];
+#pragma unroll
+  for (int o = 0; o < COUT; ++o) woff[o] = (dtn * NTO + ((o * 9 + j9) >> 5)) * 64 + half * 32 + ((o * 9 + j9) & 31);
+  constexpr int wstep = 3 * NTO * 64;         // floats between k-steps 3 s + dt and 3 (s + 1) + dt of the pack
+
+  // the outputs this thread owns: idx = tid + 256 p of the band's Th x on outputs
+  const int nout = g.Th * on;
+  int ohh[PPT], occ[PPT];
+  bool own[PPT];
+  float rA[PPT][COUT], rB[PPT][COUT], rC[PPT][COUT];
+#pragma unroll
+  for (int p = 0; p < PPT; ++p) {
+    const int idx = tid + 256 * p;
+    const bool in = idx < nout;
+    ohh[p] = in ? idx / on : 0;
+    occ[p] = in ? idx - ohh[p] * on : 0;
+    own[p] = in && h0 + ohh[p] < a.H;
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) rA[p][o] = rB[p][o] = rC[p][o] = 0.f;
+  }
+  auto store_plane = [&](const float (&rr)[PPT][COUT], int tau) {
+#pragma unroll
+    for (int p = 0; p < PPT; ++p) {
+      if (!own[p]) continue;
+      const long sp = (long)tau * HW + (long)(h0 + ohh[p]) * a.W + ob + occ[p];
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) {
+        float v = rr[p][o];
+        if (a.bias) v += a.bias[o];
+        if (a.out_lrelu) v = hpvg_lrelu(v);
+        a.y[((long)b * COUT + o) * a.T * HW + sp] = v;
+      }
+    }
+  };
+
+  for (int t = 0; t < a.T; ++t) {
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) {
+      const float* wq = a.wp + woff[o];
+      for (int grp = wave; grp < g.G; grp += 4) {
+        const int p = GP * grp + JB * l31;
+        const int pc = p < g.npos ? p : g.npos - JB;
+        const int row = pc / RS, col = pc - row * RS;
+        const int gh = h0 - 1 + row;
+        const bool valid = p < g.npos && gh >= 0 && gh < a.H;
+        const int ghc = gh < 0 ? 0 : (gh >= a.H ? a.H - 1 : gh);
+        const char* xt = xb + (long)t * HW * 4;                            // uniform
+        const unsigned lofs = (lhalf + (unsigned)(ghc * a.W + col)) * 4u;
+        f32x16 acc[JB];
+#pragma unroll
+        for (int j = 0; j < JB; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+        AV av[2][KC];
+        float bv[2][KC];
+        auto load_chunk = [&](AV (&A)[KC], float (&Bf)[KC], int s0) {
+#pragma unroll
+          for (int j = 0; j < KC; ++j) {
+            const int s = s0 + j;
+            if (s < Ch) {                                         // uniform
+              A[j] = *reinterpret_cast<const AV*>(xt + s * cstep + lofs);
+              Bf[j] = wq[s * wstep];
+            }
+          }
+        };
+        auto mma_chunk = [&](const AV (&A)[KC], const float (&Bf)[KC], int s0) {
+#pragma unroll
+          for (int j = 0; j < KC; ++j) {
+            if (s0 + j < Ch) {
+#pragma unroll
+              for (int jj = 0; jj < JB; ++jj)
+                acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(valid ? A[j][jj] : 0.f, Bf[j], acc[jj], 0, 0, 0);
+            }
+          }
+        };
+        load_chunk(av[0], bv[0], 0);
+        for (int s0 = 0; s0 < Ch; s0 += 2 * KC) {
+          load_chunk(av[1], bv[1], s0 + KC);
+          __builtin_amdgcn_sched_barrier(0);
+          mma_chunk(av[0], bv[0], s0);
+          __builtin_amdgcn_sched_barrier(0);
+          load_chunk(av[0], bv[0], s0 + 2 * KC);
+          __builtin_amdgcn_sched_barrier(0);
+          mma_chunk(av[1], bv[1], s0 + KC);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // C/D layout: column n = lane & 31, row i = (e & 3) + 8 * (e >> 2) + 4 * half; row i of MFMA jj = position GP*grp + JB*i + jj
+        if (l31 < 27) {
+#pragma unroll
+          for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) P[l31 * pitch + GP * grp + JB * ((e & 3) + 8 * (e >> 2) + 4 * half) + jj] = acc[jj][e];
+        }
+      }
+      __syncthreads();
+      // shifted 9-term sums of the three time slices (taps outside the image skipped: the window holds no padding columns)
+#pragma unroll
+      for (int p = 0; p < PPT; ++p) {
+        if (!own[p]) continue;
+        // (opaque copies: without them the 27 LDS addresses and 3 column tests of each of the thread's outputs are hoisted
+        // out of the plane loop as loop invariants - ~120 registers, which spill)
+        int hh = ohh[p], cc = occ[p];
+        asm volatile("" : "+v"(hh), "+v"(cc));
+        const int gw = ob + cc;
+        const float* Pp = P + hh * RS + (gw - wsb);
+        float sdt[3];
+#pragma unroll
+        for (int dt = 0; dt < 3; ++dt) {
+          float v = 0.f;
+#pragma unroll
+          for (int dh = 0; dh < 3; ++dh)
+#pragma unroll
+            for (int dw = 0; dw < 3; ++dw) {
+              const int gwt = gw + dw - 1;
+              if (gwt >= 0 && gwt < a.W) v += Pp[(dt * 9 + dh * 3 + dw) * pitch + dh * RS + (dw - 1)];
+            }
+          sdt[dt] = v;
+        }
+        rC[p][o] = sdt[0];
+        rB[p][o] += sdt[1];
+        rA[p][o] += sdt[2];
+      }
+      __syncthreads();
+    }
+    if (t >= 1) store_plane(rA, t - 1);      // its last contribution (slice 2 of plane t) is in
+#pragma unroll
+    for (int p = 0; p < PPT; ++p)
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) { rA[p][o] = rB[p][o]; rB[p][o] = rC[p][o]; }
+  }
+  store_plane(rA, a.T - 1);                  // no plane T: the last output plane is complete after plane T - 1
+}
+
 // B fragments of the narrow kernel; transpose_flip as in conv_pack_kernel
 __global__ void conv_pack_narrow_kernel(const float* __restrict__ w, const float* __restrict__ inv_scale, float* __restrict__ wn,
                                         int Cin_k, int Cout_k, int KT, int NT, int ksteps, int transpose_flip, long total) {
@@ -978,6 +1159,8 @@ inline int conv_check(const CShape& c) {
 struct CKnobs {
   bool sk_off;         // HPVG_CONV_SK=0: the one-workgroup-per-tile schedule even with a workspace
   bool narrow2_off;    // HPVG_NARROW2=0: the first-generation narrow kernel for every tail
+  int narrowt;         // HPVG_NARROWT (in force; hpvg_conv_narrowt_config rewrites it): conv_narrowt_kernel 0 = by size, 1 = never,
+                       // 2 = wherever it can run
   // HPVG_WINO2R=0 keeps the first-generation two-axis kernel (every wave all 16 points of one block: conv_wino2d_kernel);
   // default: the points split over the waves by row (conv_wino2r_kernel: half the input-transform instructions and U loads
   // per MFMA)
@@ -1002,6 +1185,8 @@ CKnobs& cknobs() {
     CKnobs k{};
     k.sk_off = num("HPVG_CONV_SK", 1) == 0;
     k.narrow2_off = num("HPVG_NARROW2", 1) == 0;
+    const long nt = num("HPVG_NARROWT", 0);
+    k.narrowt = nt == 1 || nt == 2 ? (int)nt : 0;
     k.w2r = num("HPVG_WINO2R", 1) != 0;
     k.w2d_off = num("HPVG_WINO2D", 1) == 0;
     k.w2_split_off = num("HPVG_W2_SPLIT", 1) == 0;
@@ -1355,6 +1540,79 @@ bool plan_narrow2(int B, int Cin, int Cout, int T, int H, int W, int KT, Narrow2
   return true;
 }
 
+// tile plan of conv_narrowt_kernel; returns false when the shape cannot run on it.  A tile is (Th + 2) rows x RS columns of a
+// column window inside [0, W), the bands as in plan_narrow2; P holds 27 columns whatever Cout is, and a thread owns at most
+// NARROWT_PPT outputs of a band.  A workgroup is matrix-core bound and walks all T planes, so the launch takes as long as the
+// busiest CU: ceil(workgroups / CUs) workgroups of Cout * (MFMA rounds of the slowest wave + a fixed epilogue) per plane.
+bool plan_narrowt(int B, int Cin, int Cout, int T, int H, int W, int KT, NarrowTGeom* out, long* nwg) {
+  if (KT != 3 || (Cin & 1) || Cin < 2 || Cout > 4 || W < 4) return false;
+  if ((long)Cin * T * H * W >= (1L << 30)) return false;   // the kernel's 32-bit lane offsets span one sample
+  constexpr int GP = 128;
+  double best = 1e300;
+  bool found = false;
+  auto bands = [&](int RS, NarrowTGeom* q) -> int {
+    int nb = 0, o = 0;
+    while (o < W) {
+      if (nb == 16) return 0;
+      int n, ws;
+      if (nb == 0) { n = (RS == W) ? W : RS - 1; ws = 0; }
+      else if (W - o <= RS - 1) { n = W - o; ws = W - RS; }
+      else { n = RS - 2; ws = o - 1; }
+      if (n < 1) return 0;
+      if (q) { q->ws[nb] = ws; q->ob[nb] = o; q->on[nb] = n; }
+      o += n;
+      ++nb;
+    }
+    return nb;
+  };
+  for (int RS = 4; RS <= 256 && RS <= W; RS += 4) {
+    const int nb = bands(RS, nullptr);
+    if (nb == 0) continue;
+    const int on_max = RS == W ? W : RS - 1;
+    for (int Th = 1; Th <= H; ++Th) {
+      const int nth = hpvg_cdiv(H, Th);
+      if (Th != hpvg_cdiv(H, nth)) continue;
+      if (Th * on_max > 256 * NARROWT_PPT) break;
+      const int npos = (Th + 2) * RS;
+      const int G = hpvg_cdiv(npos, GP);
+      const int pitch = (G * GP) | 1;
+      if ((size_t)27 * pitch * sizeof(float) > NARROWT_LDS_MAX) break;
+      const long n = (long)B * nth * nb;
+      // (ties - small levels, where one workgroup per CU is never reached - go to the least total work: the least halo)
+      const double cost = (double)hpvg_cdiv(n, (long)HPVG_NUM_CU) * (hpvg_cdiv(G, 4) * GP + 40.0) + 1e-3 * (double)(n * G);
+      if (cost < best) {
+        best = cost;
+        found = true;
+        NarrowTGeom q{};
+        q.RS = RS; q.Th = Th; q.nth = nth; q.nb = nb; q.npos = npos; q.G = G; q.pitch = pitch;
+        bands(RS, &q);
+        *out = q;
+        *nwg = n;
+      }
+    }
+  }
+  if (!found) return false;
+  // every output column needs its in-image neighbours inside the band's window, and every window lies inside the image
+  for (int k = 0; k < out->nb; ++k) {
+    const int lo = out->ob[k] - 1 < 0 ? 0 : out->ob[k] - 1;
+    const int hi = out->ob[k] + out->on[k] > W - 1 ? W - 1 : out->ob[k] + out->on[k];
+    if (out->on[k] < 1 || lo < out->ws[k] || hi >= out->ws[k] + out->RS) return false;
+    if (out->ws[k] < 0 || out->ws[k] + out->RS > W) return false;
+  }
+  return true;
+}
+inline size_t narrowt_lds(const NarrowTGeom& g) { return (size_t)27 * g.pitch * sizeof(float); }
+// Where conv_narrowt_kernel is taken, by size where it was measured to win against conv_narrow2_kernel (DESIGN.md section 4,
+// profiles/critic_backward_kernel_stats.txt).  A workgroup spends ~12 us per plane and output channel whatever the launch,
+// so the kernel needs the chip filled: 64 -> 1 at 180 workgroups and more x1.0-1.58 (x1.37 at the finest video level, B = 2),
+// at 144 and fewer x0.27-0.89.  With Cout = 3 it makes three passes over every plane and loses everywhere (x0.15-0.44): those
+// layers stay on the second generation.
+inline bool conv_use_narrowt(const CKnobs& k, const CShape& c, bool ok, long nwg) {
+  if (!ok || k.narrowt == 1) return false;
+  if (k.narrowt == 2) return true;
+  return c.Cout == 1 && c.T >= 7 && nwg >= 180;
+}
+
 // --------------------------------------------------------------------------------------------------------------- plan memo
 // (memo_lookup: hpvg_host.h)  Every plan of one launch shape, filled at its first launch or query: a search costs 10-100 us of
 // host time and shapes repeat every iteration.  direct / wino: [0] one workgroup per tile, [1] stream-K.  A narrow shape has
@@ -1367,6 +1625,9 @@ struct CPlans {
   Narrow2Geom n2;
   long n2_tiles;
   bool n2_ok;
+  NarrowTGeom nt;     // conv_narrowt_kernel (3x3x3 only)
+  long nt_wgs;
+  bool nt_ok;
 };
 const CPlans& conv_plans(const CKnobs& k, const CShape& c) {
   return memo_lookup<CPlans>(k.gen, c.B, c.Cin, c.Cout, c.T, c.H, c.W, c.KT, [&] {
@@ -1374,6 +1635,7 @@ const CPlans& conv_plans(const CKnobs& k, const CShape& c) {
     if (conv_is_narrow(c.Cin, c.Cout)) {
       pl.direct[0] = pl.direct[1] = plan_narrow_search(c);
       pl.n2_ok = plan_narrow2(c.B, c.Cin, c.Cout, c.T, c.H, c.W, c.KT, &pl.n2, &pl.n2_tiles);
+      pl.nt_ok = plan_narrowt(c.B, c.Cin, c.Cout, c.T, c.H, c.W, c.KT, &pl.nt, &pl.nt_wgs);
       return pl;
     }
     for (int sk = 0; sk < 2; ++sk) {
@@ -1433,7 +1695,8 @@ inline bool conv_use_wino2d(const CKnobs& k, const W2Geom& q) {
 struct CDecision {
   int kind;           // hpvg_conv_fwd_kernel_kind's numbering: 0 conv_mfma_kernel, 1 conv_wino_kernel, 2 the two-axis
                       // kernels (plans->w2), 3 the narrow kernels
-  int narrow_gen;     // kind 3: 2 = conv_narrow2_kernel (plans->n2), 1 = conv_narrow_kernel (on plan's tiles)
+  int narrow_gen;     // kind 3: 3 = conv_narrowt_kernel (plans->nt), 2 = conv_narrow2_kernel (plans->n2), 1 = conv_narrow_kernel
+                      // (on plan's tiles)
   const CPlans* plans;
   const Plan* plan;   // kinds 0, 1, 3; L == 0: no tile fits the shape
   bool streamk;
@@ -1449,6 +1712,7 @@ CDecision conv_decide(const CShape& c, bool prologue, bool fp32_out_mask, const 
     d.kind = 3;
     d.plan = &pl.direct[0];
     d.narrow_gen = !k.narrow2_off && !prologue && !fp32_out_mask && pl.n2_ok ? 2 : 1;
+    if (!prologue && !fp32_out_mask && conv_use_narrowt(k, c, pl.nt_ok, pl.nt_wgs)) d.narrow_gen = 3;
     d.ntl = d.S = conv_ntiles(c, *d.plan);
     return d;
   }
@@ -1610,6 +1874,19 @@ template <int KT>
 int launch_narrow(const ConvFwdArgs& a, const CDecision& d, hipStream_t s) {
   const int ksteps = hpvg_cdiv(a.Cin * KT, 2);
   const bool one = 9 * a.Cout <= 32;
+  if constexpr (KT == 3) {
+    if (d.narrow_gen == 3) {
+      const NarrowTGeom& g = d.plans->nt;
+      const dim3 grid((unsigned)d.plans->nt_wgs);
+      const size_t lds = narrowt_lds(g);
+      switch (a.Cout) {
+        case 1: return launch_lds<conv_narrowt_kernel<1>>(grid, dim3(256), lds, s, a, g);
+        case 2: return launch_lds<conv_narrowt_kernel<2>>(grid, dim3(256), lds, s, a, g);
+        case 3: return launch_lds<conv_narrowt_kernel<3>>(grid, dim3(256), lds, s, a, g);
+        default: return launch_lds<conv_narrowt_kernel<4>>(grid, dim3(256), lds, s, a, g);
+      }
+    }
+  }
   if (d.narrow_gen == 2) {
     const Narrow2Geom& g = d.plans->n2;
     const dim3 grid((unsigned)d.plans->n2_tiles);
@@ -1833,6 +2110,32 @@ int hpvg_conv_narrow_plan(int B, int Cin, int Cout, int T, int H, int W, int KT,
   out[0] = g.RS; out[1] = g.Th; out[2] = g.nth; out[3] = g.nb; out[4] = g.npos; out[5] = g.G; out[6] = g.pitch;
   for (int k = 0; k < g.nb; ++k) { out[7 + 3 * k] = g.ws[k]; out[8 + 3 * k] = g.ob[k]; out[9 + 3 * k] = g.on[k]; }
   return HPVG_OK;
+}
+
+// host only: the tile plan of conv_narrowt_kernel (narrow output, time taps in N) whether or not the launch picks it:
+// out[0..8] = RS, Th, nth, nb, npos, G, pitch, lds_bytes, 1 when a plain launch of this shape runs on it in the mode in
+// force (else 0), then nb triples (window start, first output column, output columns).  HPVG_ERR_UNSUPPORTED when the kernel
+// cannot run the shape (not 3x3x3, Cout > 4, odd Cin, W < 4, not a narrow layer).
+int hpvg_conv_narrowt_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out) {
+  const CShape c{B, Cin, Cout, T, H, W, KT};
+  if (!out || conv_check(c) != HPVG_OK) return HPVG_ERR_ARG;
+  const CPlans& pl = conv_plans(cknobs(), c);   // (not narrow: nt_ok stays false)
+  if (!pl.nt_ok) return HPVG_ERR_UNSUPPORTED;
+  const NarrowTGeom& g = pl.nt;
+  out[0] = g.RS; out[1] = g.Th; out[2] = g.nth; out[3] = g.nb; out[4] = g.npos; out[5] = g.G; out[6] = g.pitch;
+  out[7] = (int)narrowt_lds(g);
+  out[8] = conv_decide_query(c).narrow_gen == 3 ? 1 : 0;
+  for (int k = 0; k < g.nb; ++k) { out[9 + 3 * k] = g.ws[k]; out[10 + 3 * k] = g.ob[k]; out[11 + 3 * k] = g.on[k]; }
+  return HPVG_OK;
+}
+
+// Run-time form of HPVG_NARROWT (tests and A/B tools): 0 = conv_narrowt_kernel by size, 1 = never, 2 = wherever it can run;
+// a negative argument leaves the setting alone.  Returns the mode in force.
+int hpvg_conv_narrowt_config(int mode) {
+  CKnobs& k = cknobs();
+  if (mode > 2) return HPVG_ERR_ARG;
+  if (mode >= 0) k.narrowt = mode;
+  return k.narrowt;
 }
 
 #ifdef HPVG_TRACE

@@ -347,6 +347,14 @@ class inputs_only:
 
 
 # ------------------------------------------------------------------------------------------ conv family
+# Conv.backward hands the LeakyReLU mask operands (activations of the forward pass) to ConvBwdData / LReLUMaskMul.  Under
+# create_graph=True (the gradient penalty) an operand that requires grad gives the new node an edge to the forward Conv
+# that produced it; no gradient is ever returned along it (LeakyReLU's second derivative is zero), but the engine still
+# runs that producer - on a materialised tensor of zeros - when the penalty is back-propagated: a whole backward pass of
+# D(x_hat) for nothing.  Detached operands carry the same values and no edge.  Not a user flag: the tests run both forms.
+DETACH_MASKS = True
+
+
 class LReLUMaskMul(Function):
     """dy * (h > 0 ? 1 : 0.2) - leaky_relu_backward on the activated tensor (reference: networks_3d.py:21)."""
 
@@ -418,10 +426,14 @@ class Conv(Function):
     def backward(ctx, dy):
         x, w, y, b, in_bits = ctx.saved_tensors
         dy = _c(dy)
+        if DETACH_MASKS:
+            x_mask, y_mask = x.detach(), (y.detach() if y is not None else None)
+        else:
+            x_mask, y_mask = x, y
         if ctx.own_mask:
-            dy = LReLUMaskMul.apply(dy, y)
+            dy = LReLUMaskMul.apply(dy, y_mask)
         params = not inputs_only.active
-        dx = ConvBwdData.apply(dy, w, x if ctx.in_act else None, in_bits) if ctx.needs_input_grad[0] else None
+        dx = ConvBwdData.apply(dy, w, x_mask if ctx.in_act else None, in_bits) if ctx.needs_input_grad[0] else None
         want_w = ctx.needs_input_grad[1] and params
         want_b = ctx.has_bias and ctx.needs_input_grad[2] and params
         if want_w and want_b:

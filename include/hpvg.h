@@ -104,6 +104,16 @@ int hpvg_conv_wino_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, i
 /* host only: tile plan of the narrow-output kernel (Cout <= 4): out[0..6] = RS, Th, nth, nb, npos, G, pitch, then nb triples
  * (window start, first output column, output columns); out needs 7 + 3*16 ints */
 int hpvg_conv_narrow_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out55);
+/* The 3x3x3 narrow-output layers with an even Cin have a second kernel behind the same entry points: one workgroup walks the
+ * input planes of its (sample, row block, column band) with the time taps in the GEMM's N axis, so every input plane is
+ * read and multiplied once instead of once per output plane it reaches.  Which kernel a launch runs is decided by size.
+ * hpvg_conv_narrowt_plan (host only): its tile plan whether or not the launch picks it: out[0..8] = RS, Th, nth, nb, npos, G,
+ * pitch, lds_bytes, 1 when a plain launch of this shape runs on it in the mode in force, then nb triples (window start,
+ * first output column, output columns); out needs 9 + 3*16 ints; HPVG_ERR_UNSUPPORTED where the kernel cannot run.
+ * hpvg_conv_narrowt_config (host only; environment: HPVG_NARROWT): 0 = by size, 1 = never, 2 = wherever it can run; a negative
+ * argument leaves the setting as it is; returns the mode in force. */
+int hpvg_conv_narrowt_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out57);
+int hpvg_conv_narrowt_config(int mode);
 /* dW (natural layout) of the conv above: aten::convolution_backward weight half, reached from
  * total_loss.backward() / errD_total.backward() (train_video.py:182,200). accumulate!=0: dw += result. */
 size_t hpvg_conv_bwd_weight_ws_bytes(int B, int Cin, int Cout, int T, int H, int W, int KT);

@@ -20,6 +20,10 @@
  * Workspaces (`ws`) need 16-byte alignment, as stated per function.  A launch reads and writes nothing outside [p, p + n) of
  * any tensor argument of n elements: no whole-vector overrun past the last row or plane, before the first, or into the
  * bytes an allocator leaves behind a tensor (tests/test_offset_launches.py runs every launch inside guard bands).
+ * A uint8 or int8 tensor argument (volumes, images, masks, frames, projection directions, byte outputs) may have ANY byte
+ * alignment - sample i of a [N][T][H][W][3] array is a valid argument, odd start included - and nothing outside [p, p + n) of
+ * its n bytes is read or written: no whole-word read before the first byte or past the last, no store beyond the last byte
+ * (tests/test_byte_offset_launches.py runs every such launch at every byte residue inside guard bands).
  */
 #ifndef HPVG_H
 #define HPVG_H

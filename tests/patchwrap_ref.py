@@ -7,8 +7,7 @@ import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
 from patchmatch_ref import START_IT, patch_matrix, rnd
-from test_patchgen import brute_weighted
-from test_patchnn import brute
+from patch_ref import brute, brute_weighted
 
 NONE = (0, 0, 0)
 

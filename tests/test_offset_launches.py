@@ -17,7 +17,8 @@ is NaN or still the sentinel, and no input's guard was written.
 (b) BatchNorm family and channel sum: the vector width comes from the pointer (hpvg_vec_width_at); launches of one case with the
     same width are bit-equal, every launch is checked against float64 (ew_ref, TAU / TAU_STAT); V = 4, 2, 1 must each be
     chosen by the pointer on an S % 4 == 0 shape.
-(c) pointwise, losses, resize, copies: bit-equal to the base, base against float64 where ew_ref has a reference.
+(c) pointwise, losses, resize, copies, the variant models' kernels (csrc/variants.hip): bit-equal to the base, base against
+    float64 where ew_ref / variant_ref has a reference.
 (d) the producer itself: one critic step on SplitBatch's `fake` and on fake.clone() agree bit for bit.
 
 The module prints, per section, the launches compared bit for bit, the launches compared with float64 and the worst
@@ -925,6 +926,72 @@ def test_box_copy_store_forms(ops, hplib, lib, BC):
                   "box_copy crop BC=%d" % BC)
     assert torch.equal(r["dst"], src)
     _RAN["box"].add(BC)
+
+
+@pytest.mark.parametrize("shape,size", EW_SHAPES, ids=EW_IDS)
+def test_variant_kernels_at_every_offset(ops, hplib, lib, shape, size):
+    """The kernels of csrc/variants.hip (Gate, GlobalAvgPool, CodeTimesMap, ReparamBern, KLBern) through the C ABI with every
+    input and output in turn at offset 1, 2, 3: bit-equal to the base, guards intact, every element stored; the base against
+    the float64 references of tests/variant_ref.py (S = 105 / 35: odd, so rows start at every residue)."""
+    import variant_ref as V
+    g = _gen("variants", shape)
+    B, C = shape[0], shape[1]
+    S = E.spatial(shape[2:])
+    key = "%dd" % (len(shape) - 2)
+    f32 = torch.float32
+    p = hplib.ptr
+    f, dout, dz = (_randn(g, B, C, S) for _ in range(3))
+    logit, ext, zmap = 2 * _randn(g, B, S), _randn(g, B, S), _randn(g, B, S)
+    code = _randn(g, B, C)
+    x = torch.rand(B, S, generator=g, device=DEV) * 0.98 + 0.01
+    eps = torch.rand(B, S, generator=g, device=DEV)
+    gout = torch.tensor([0.83], device=DEV)
+    L = ctypes.c_long(B * S)
+    tag = "variants %s: " % (shape,)
+
+    def launch(name, *args):
+        hplib.call(name, *args, hplib.stream())
+
+    r = all_equal("c", sweep("c", tag + "gate_fwd", {"f": f, "logit": logit}, {"out": ((B, C, S), f32, None), "bern": ((B, S), f32, None)},
+                             lambda T: launch("hpvg_gate_fwd_f32", p(T["f"]), p(T["logit"]), p(T["out"]), p(T["bern"]), B, C, S)),
+                  tag + "gate_fwd")
+    ref = V.gate_fwd64(f, logit)
+    check("c", r["out"], *ref["out"], tag + "gate out", "gate.out", key)
+    check("c", r["bern"], *ref["bern"], tag + "gate bern", "gate.bern", key)
+    bern = r["bern"].clone()
+    for dname, d, e in (("both", dout, ext), ("dout", dout, None), ("dbern_ext", None, ext)):
+        r = all_equal("c", sweep("c", tag + "gate_bwd " + dname, {"dout": d, "f": f, "bern": bern, "ext": e},
+                                 {"df": ((B, C, S), f32, None), "dlogit": ((B, S), f32, None)},
+                                 lambda T: launch("hpvg_gate_bwd_f32", p(T["dout"]), p(T["f"]), p(T["bern"]), p(T["ext"]), p(T["df"]),
+                                                  p(T["dlogit"]), B, C, S)), tag + "gate_bwd " + dname)
+        bref = V.gate_bwd64(d, f, bern, e)
+        check("c", r["df"], *bref["df"], tag + "gate df " + dname, "gate.df", key)
+        check("c", r["dlogit"], *bref["dlogit"], tag + "gate dlogit " + dname, "gate.dlogit", key)
+    for wname, w, scale in (("pool", None, 1.0 / S), ("weighted", zmap, 1.0)):
+        r = all_equal("c", sweep("c", tag + "rowsum " + wname, {"x": dz, "w": w}, {"out": ((B, C), f32, None)},
+                                 lambda T: launch("hpvg_rowsum_f32", p(T["x"]), p(T["w"]), p(T["out"]), scale, B, C, S)),
+                      tag + "rowsum " + wname)
+        check("c", r["out"], *V.rowsum64(dz, w, scale), tag + "rowsum " + wname, "rowsum." + wname, key)
+        r = all_equal("c", sweep("c", tag + "outer " + wname, {"g": code, "w": w}, {"out": ((B, C, S), f32, None)},
+                                 lambda T: launch("hpvg_outer_f32", p(T["g"]), p(T["w"]), p(T["out"]), scale, B, C, S)),
+                      tag + "outer " + wname)
+        check("c", r["out"], *V.outer64(code, w, scale, S), tag + "outer " + wname, "outer." + wname, key)
+    r = all_equal("c", sweep("c", tag + "colsum", {"a": dz, "v": code}, {"out": ((B, S), f32, None)},
+                             lambda T: launch("hpvg_colsum_f32", p(T["a"]), p(T["v"]), p(T["out"]), B, C, S)), tag + "colsum")
+    check("c", r["out"], *V.colsum64(dz, code), tag + "colsum", "colsum", key)
+    r = all_equal("c", sweep("c", tag + "reparam_bern_fwd", {"x": x, "eps": eps}, {"z": ((B, S), f32, None)},
+                             lambda T: launch("hpvg_reparam_bern_fwd_f32", p(T["x"]), p(T["eps"]), p(T["z"]), L)), tag + "reparam_bern_fwd")
+    check("c", r["z"], *V.reparam_bern_fwd64(x, eps), tag + "reparam_bern", "rbern.fwd", key)
+    r = all_equal("c", sweep("c", tag + "reparam_bern_bwd", {"dz": ext, "x": x}, {"dx": ((B, S), f32, None)},
+                             lambda T: launch("hpvg_reparam_bern_bwd_f32", p(T["dz"]), p(T["x"]), p(T["dx"]), L)), tag + "reparam_bern_bwd")
+    check("c", r["dx"], *V.reparam_bern_bwd64(ext, x), tag + "reparam_bern backward", "rbern.bwd", key)
+    r = all_equal("c", sweep("c", tag + "kl_bern_fwd", {"x": x}, {"out": ((1,), f32, None)},
+                             lambda T: launch("hpvg_kl_bern_fwd_f32", p(T["x"]), p(T["out"]), *ops._reduce_ws(T["x"].device), L)),
+                  tag + "kl_bern_fwd")
+    check_scalar("c", r["out"], *V.kl_bern_fwd64(x), tag + "kl_bern", "klbern.fwd", key)
+    r = all_equal("c", sweep("c", tag + "kl_bern_bwd", {"gout": gout, "x": x}, {"dx": ((B, S), f32, None)},
+                             lambda T: launch("hpvg_kl_bern_bwd_f32", p(T["gout"]), p(T["x"]), p(T["dx"]), L)), tag + "kl_bern_bwd")
+    check("c", r["dx"], *V.kl_bern_bwd64(0.83, x), tag + "kl_bern backward", "klbern.bwd", key)
 
 
 # ================================================================================================ (d) the producer itself

@@ -4,6 +4,7 @@ pick their kernel by (hpvg_vec_width_at, hpvg_bn_vec_width_at), and the table of
 `fake = x[B:]` (ops.SplitBatch in modules/_nets.py forward_pair) starts off a 16-byte boundary."""
 import ctypes
 
+import numpy as np
 import pytest
 import torch
 
@@ -89,6 +90,126 @@ def test_out_like_sentinel_and_guard_check_can_fail(off, dtype):
         v2.view(-1)[4] = float("nan")
         with pytest.raises(AssertionError, match="NaN in the output"):
             OB.assert_written(v2, "poisoned")
+
+
+# ------------------------------------------------------------------------------------------------ the byte helper
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.int8])
+@pytest.mark.parametrize("off", OB.BYTE_OFFSETS)
+def test_embed_u8_placement_residue_and_guards(off, dtype):
+    g = torch.Generator().manual_seed(70 + off)
+    shape = (3, 5, 7, 3)                                  # 315 bytes: not a multiple of 4
+    t = torch.randint(0, 256, shape, generator=g, dtype=torch.int16).to(torch.uint8).view(dtype)
+    for fill in OB.BYTE_FILLS:
+        v = OB.embed_u8(t, off, fill)
+        buf, start, n, bits = v._offset_buf
+        guard = OB.byte_guard_for(shape)
+        assert guard >= 2 * 5 * 7 * 3 and guard >= 64 and guard % 16 == 0
+        assert buf.dtype == torch.uint8 and buf.data_ptr() % 16 == 0 and buf.numel() == guard + off + n + guard
+        assert start == guard + off and n == 315 and bits == fill
+        assert v.data_ptr() == buf.data_ptr() + start and v.data_ptr() % 16 == off % 16
+        assert v.is_contiguous() and tuple(v.shape) == shape and v.dtype == dtype and torch.equal(v, t)
+        assert bool((buf[:start] == fill).all()) and bool((buf[start + n:] == fill).all())
+        assert OB.guards_intact(v)
+
+
+def test_byte_offsets_cover_every_residue():
+    assert OB.BYTE_OFFSETS == (0, 1, 2, 3, 7, 13)
+    assert {o % 4 for o in OB.BYTE_OFFSETS} == {0, 1, 2, 3}
+    assert sum(1 for o in OB.BYTE_OFFSETS if o % 8 in (1, 3, 5, 7) and o % 16 in (1, 3, 5, 7, 9, 11, 13, 15)) >= 2
+    assert {7 % 8, 13 % 8} == {7, 5} and OB.BYTE_FILLS == (0x00, 0xFF) and OB.BYTE_SENTINELS == (0x5A, 0xA5)
+
+
+def test_byte_guard_size_follows_the_plane():
+    assert OB.byte_guard_for((3, 5, 7, 3)) == 224                 # two planes of 105 bytes = 210, in 16-byte groups
+    assert OB.byte_guard_for((4, 9, 11, 3)) == 608                # 2 * 9 * 11 * 3 = 594
+    assert OB.byte_guard_for((2, 3, 5, 7, 3)) == 224              # [B, T, H, W, C]: the plane is H * W * C
+    assert OB.byte_guard_for((1, 2, 2, 3)) == 64                  # never fewer than 64
+    assert OB.byte_guard_for((9, 10, 3)) == 544                   # an image: the whole of it, twice (540)
+    assert OB.byte_guard_for((4, 9, 11)) == 800                   # a mask [T, H, W]: no smaller than two planes (198)
+    assert OB.byte_guard_for((7, 54)) == 768
+    assert OB.embed_u8(torch.zeros(5, dtype=torch.uint8), 3, 0, guard=9)._offset_buf[1] == 16 + 3
+
+
+@pytest.mark.parametrize("off", OB.BYTE_OFFSETS)
+def test_out_like_u8_sentinel_and_guard_check_can_fail(off):
+    shape = (3, 5, 7, 3)
+    for sentinel in OB.BYTE_SENTINELS:
+        v = OB.out_like_u8(shape, off, sentinel)
+        buf, start, n, bits = v._offset_buf
+        assert bits == sentinel and v.data_ptr() % 16 == off % 16 and n == 315 and bool((buf == sentinel).all())
+        v.fill_(3)
+        assert OB.guards_intact(v)
+        for pos in (start - 1, start + n):                        # one byte before the payload, one byte after it
+            buf[pos] = sentinel ^ 0xFF
+            assert not OB.guards_intact(v)
+            buf[pos] = sentinel
+            assert OB.guards_intact(v)
+
+
+# numpy stand-ins of byte kernels on the raw buffer: p = the payload's start, n its length.  The sound one touches [p, p + n)
+# alone; each defect is one of the four mistakes a byte kernel makes at its ends.
+def _np_kernel(defect):
+    def launch(ins, outs):
+        src, p, n, _ = ins["x"]._offset_buf
+        dst, q, m, _ = outs["y"]._offset_buf
+        s, d = src.numpy(), dst.numpy()
+        assert n == m
+        # y[i] = x[i] + 1 (mod 256); total = the sum of the bytes the kernel read
+        lo, hi = p, p + n
+        if defect == "reads one byte before the start":
+            lo = p - 1
+        elif defect == "reads a whole 4-byte word at the end":
+            hi = p + (n + 3) // 4 * 4
+            assert hi > p + n
+        total = int(s[lo:hi].astype(np.int64).sum())
+        stores = n
+        if defect == "stores one byte past the end":
+            stores = n + 1
+        elif defect == "skips the last byte":
+            stores = n - 1
+        d[q:q + min(stores, n)] = s[p:p + min(stores, n)] + np.uint8(1)
+        if stores > n:
+            d[q + n] = 0
+        return {"total": torch.tensor([total])}
+    return launch
+
+
+BYTE_DEFECTS = ["reads one byte before the start", "reads a whole 4-byte word at the end", "stores one byte past the end",
+                "skips the last byte"]
+
+
+def _byte_case():
+    g = torch.Generator().manual_seed(99)
+    x = torch.randint(0, 256, (3, 5, 7, 3), generator=g, dtype=torch.int16).to(torch.uint8)     # 315 bytes
+    want = {"y": x + 1, "total": torch.tensor([int(x.to(torch.int64).sum())])}
+    assert int(want["y"].min()) == 0                              # the wrap-around occurs
+    return x, want
+
+
+@pytest.mark.parametrize("off", OB.BYTE_OFFSETS)
+def test_byte_rule_passes_a_sound_kernel(off):
+    x, want = _byte_case()
+    res = OB.byte_rule(_np_kernel(None), {"x": x}, {"y": x.shape}, want, offs={"x": off, "y": (off * 5) % 16})
+    assert torch.equal(res["y"], want["y"])
+
+
+@pytest.mark.parametrize("off", OB.BYTE_OFFSETS)
+@pytest.mark.parametrize("defect", BYTE_DEFECTS)
+def test_byte_rule_catches_every_seeded_defect(defect, off):
+    """Each defect fails the pair of runs at every offset: the 0x00 run alone would pass the two over-reads (a sum does not see
+    a zero), the 0xFF run catches them; the store past the end breaks a guard; the skipped byte holds the sentinel, which equals
+    the wanted byte in at most one of the two runs."""
+    x, want = _byte_case()
+    with pytest.raises(AssertionError, match="guard band|differs from the reference"):
+        OB.byte_rule(_np_kernel(defect), {"x": x}, {"y": x.shape}, want, offs={"x": off, "y": off})
+    if defect.startswith("reads"):
+        # the run with zero guards does pass: it is the SECOND run that makes the rule
+        keep = OB.BYTE_FILLS
+        OB.BYTE_FILLS = (0x00, 0x00)
+        try:
+            OB.byte_rule(_np_kernel(defect), {"x": x}, {"y": x.shape}, want, offs={"x": off, "y": off})
+        finally:
+            OB.BYTE_FILLS = keep
 
 
 # ------------------------------------------------------------------------------------------------ the size rules' pointer half

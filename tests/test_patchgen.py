@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
 from hp_vae_gan_amd import generate_patchnn, ops  # noqa: E402
+from patch_ref import brute_weighted, vote_ref  # noqa: E402,F401
 from test_patchnn import BAD, _case, _patches, _rand, brute  # noqa: E402
 
 ERR_ARG, ERR_WORKSPACE = -1, -2
@@ -30,28 +31,6 @@ WEIGHTED_CASES = ["lane1", "lane8", "ragged", "ragged_strided", "merge", "nq1", 
 
 
 # ------------------------------------------------------------------------------------------------------------ yardsticks
-def brute_weighted(q, r, w, patch, qstride=ONE, rstride=ONE):
-    """(score float32, nn int64) shaped as the query grid: min_j float32(d2_ij) * w[j] and the first j that attains it."""
-    if q.ndim == 3:
-        q, r = q[None], r[None]
-    Q, grid = _patches(q, patch, qstride)
-    R, _ = _patches(r, patch, rstride)
-    w = np.asarray(w, np.float32).reshape(-1)
-    assert w.shape == (len(R),)
-    rn = (R * R).sum(1)
-    score = np.empty(len(Q), np.float32)
-    nn = np.empty(len(Q), np.int64)
-    for i0 in range(0, len(Q), 1024):
-        Qc = Q[i0:i0 + 1024]
-        dist = (Qc * Qc).sum(1)[:, None] + rn[None, :] - 2.0 * (Qc @ R.T)     # exact integers in float64
-        s = dist.astype(np.float32) * w[None, :]
-        assert s.dtype == np.float32
-        j = s.argmin(1)
-        nn[i0:i0 + 1024] = j
-        score[i0:i0 + 1024] = s[np.arange(len(Qc)), j]
-    return score.reshape(grid), nn.reshape(grid)
-
-
 def _weights(n, seed):
     return np.random.default_rng(seed).uniform(0.25, 4.0, size=n).astype(np.float32).clip(0.25, np.nextafter(np.float32(4), np.float32(0)))
 
@@ -64,28 +43,6 @@ def _wcase(name):
     w = _weights(Nr, 100 + WEIGHTED_CASES.index(name))
     score, nn = brute_weighted(q, r, w, patch, qs, rs)
     return q, r, patch, qs, rs, w, score, nn, nn0
-
-
-def vote_ref(values, nn, patch, fallback, qstride=ONE, rstride=ONE):
-    """numpy vote: values / fallback uint8 [T,H,W,3], nn flat indices into values' grid (entries outside [0, Nr) are skipped)."""
-    pt, ph, pw = patch
-    win = sliding_window_view(values, tuple(patch) + (3,))[:, :, :, 0][::rstride[0], ::rstride[1], ::rstride[2]]
-    V = win.reshape(-1, pt, ph, pw, 3).astype(np.int64)
-    T, H, W = fallback.shape[:3]
-    total = np.zeros((T, H, W, 3), np.int64)
-    cnt = np.zeros((T, H, W, 1), np.int64)
-    i = 0
-    for t0 in range(0, T - pt + 1, qstride[0]):
-        for y0 in range(0, H - ph + 1, qstride[1]):
-            for x0 in range(0, W - pw + 1, qstride[2]):
-                j = int(nn.reshape(-1)[i])
-                i += 1
-                if 0 <= j < len(V):
-                    total[t0:t0 + pt, y0:y0 + ph, x0:x0 + pw] += V[j]
-                    cnt[t0:t0 + pt, y0:y0 + ph, x0:x0 + pw] += 1
-    assert i == nn.size
-    out = (2 * total + cnt) // (2 * np.maximum(cnt, 1))
-    return np.where(cnt > 0, out, fallback).astype(np.uint8), cnt[..., 0]
 
 
 def _dev(a):

@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from hp_vae_gan_amd import lib as hplib  # noqa: E402
 from hp_vae_gan_amd import generate_patchnn, ops  # noqa: E402
+from patch_ref import brute_subset, count_ref  # noqa: E402
 from test_patchgen import vote_ref  # noqa: E402
 from test_patchnn import BAD, _patches, _rand  # noqa: E402
 
@@ -31,29 +32,6 @@ ONE = (1, 1, 1)
 
 
 # ------------------------------------------------------------------------------------------------------------ yardsticks
-def brute_subset(q, r, patch, qsel=None, rsel=None, qstride=ONE, rstride=ONE):
-    """(d2, nn) int64 shaped as the query grid: brute force between the selected rows, nn in r's grid, -1 / -1 elsewhere."""
-    if q.ndim == 3:
-        q, r = q[None], r[None]
-    Q, grid = _patches(q, patch, qstride)
-    R, _ = _patches(r, patch, rstride)
-    qi = np.arange(len(Q)) if qsel is None else np.asarray(qsel, np.int64)
-    ri = np.arange(len(R)) if rsel is None else np.asarray(rsel, np.int64)
-    Qs, Rs = Q[qi], R[ri]
-    dist = (Qs * Qs).sum(1)[:, None] + (Rs * Rs).sum(1)[None, :] - 2.0 * (Qs @ Rs.T)     # exact integers in float64
-    j = dist.argmin(1)
-    d2 = np.full(len(Q), -1, np.int64)
-    nn = np.full(len(Q), -1, np.int64)
-    d2[qi] = dist[np.arange(len(qi)), j]
-    nn[qi] = ri[j]
-    return d2.reshape(grid), nn.reshape(grid)
-
-
-def count_ref(mask, patch, stride=ONE):
-    win = sliding_window_view(mask != 0, tuple(patch))[::stride[0], ::stride[1], ::stride[2]]
-    return win.sum((3, 4, 5)).astype(np.int64)
-
-
 def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 

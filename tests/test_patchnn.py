@@ -18,37 +18,13 @@ from numpy.lib.stride_tricks import sliding_window_view
 
 from hp_vae_gan_amd import lib as hplib
 from hp_vae_gan_amd import evaluate, ops
+from patch_ref import _patches, brute  # noqa: F401
 
 ERR_ARG = -1
 I3 = ctypes.c_int * 3
 
 
 # ------------------------------------------------------------------------------------------------------------ yardstick
-def _patches(vol, patch, stride):
-    """float64 [N][D] patch matrix of a uint8 [T][H][W][3] volume, patches in (t, y, x) raster order of the strided grid."""
-    win = sliding_window_view(vol, tuple(patch) + (3,))[:, :, :, 0]
-    win = win[::stride[0], ::stride[1], ::stride[2]]
-    grid = win.shape[:3]
-    return win.reshape(grid[0] * grid[1] * grid[2], -1).astype(np.float64), grid
-
-
-def brute(q, r, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
-    if q.ndim == 3:
-        q, r = q[None], r[None]
-    Q, grid = _patches(q, patch, qstride)
-    R, _ = _patches(r, patch, rstride)
-    rn = (R * R).sum(1)
-    d2 = np.empty(len(Q), np.int64)
-    nn = np.empty(len(Q), np.int64)
-    for i0 in range(0, len(Q), 1024):
-        Qc = Q[i0:i0 + 1024]
-        dist = (Qc * Qc).sum(1)[:, None] + rn[None, :] - 2.0 * (Qc @ R.T)
-        j = dist.argmin(1)
-        nn[i0:i0 + 1024] = j
-        d2[i0:i0 + 1024] = dist[np.arange(len(Qc)), j]
-    return d2.reshape(grid), nn.reshape(grid)
-
-
 def _rand(shape, seed):
     return np.random.default_rng(seed).integers(0, 256, size=tuple(shape) + (3,), dtype=np.uint8)
 

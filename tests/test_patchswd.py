@@ -18,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from patch_ref import ref_hist, ref_num  # noqa: E402
 from test_patchnn import _case as _nn_case  # noqa: E402
 from test_patchnn import _patches, _rand  # noqa: E402
 
@@ -30,27 +31,6 @@ ONE = (1, 1, 1)
 
 
 # ------------------------------------------------------------------------------------------------------------ yardstick
-def ref_hist(vol, patch, S, stride=ONE):
-    """(int32 [P][NB] histograms, N) of a uint8 volume's patch projections on the rows of S, from the definition."""
-    if vol.ndim == 3:
-        vol = vol[None]
-    X = _patches(vol, patch, stride)[0].astype(np.int64) - 128
-    N, D = X.shape
-    assert S.shape[1] == D
-    proj = X @ S.T.astype(np.int64) + 128 * D
-    assert proj.min() >= 0 and proj.max() <= 256 * D
-    return np.stack([np.bincount(proj[:, p], minlength=256 * D + 1) for p in range(S.shape[0])]).astype(np.int32), N
-
-
-def ref_num(hA, Na, hB, Nb):
-    """Python-integer numerators sum_b |Nb cA(b) - Na cB(b)| of two [P][NB] histograms."""
-    out = []
-    for a, b in zip(hA, hB):
-        cA, cB = np.cumsum(a.astype(np.int64)).astype(object), np.cumsum(b.astype(np.int64)).astype(object)
-        out.append(int(np.abs(int(Nb) * cA - int(Na) * cB).sum()))
-    return out
-
-
 def _dirs(P, D, seed):
     """Random {-1, 0, +1} directions, none all-zero (row p gets a +1 at k = p % D where the draw left it empty)."""
     S = np.random.default_rng(seed).integers(-1, 2, size=(P, D), dtype=np.int8)

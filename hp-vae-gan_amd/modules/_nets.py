@@ -21,17 +21,40 @@ def _kernel_shape(dims):
     return (3,) * dims
 
 
+WIDE_KER_SIZES = (5, 7)   # beside 3 (and 1): the tap-generic conv family (ops.conv_fwd_raw decides by the weight's tap side)
+
+
+def _wide_ok(ker_size, padding, stride):
+    """ker_size 5 / 7: stride 1 and any padding up to 'same' (less = the 'same' conv followed by a crop)"""
+    return ker_size in WIDE_KER_SIZES and stride == 1 and 0 <= padding <= ker_size // 2
+
+
+def crop_wide(y, ker_size, padding, what):
+    """The padding < ker_size // 2 conv from the 'same' one: drop ker_size // 2 - padding voxels per side (ops.CropBorder).
+    A volume the crop would empty is refused by name."""
+    c = ker_size // 2 - padding
+    if c == 0:
+        return y
+    if any(int(n) - 2 * c < 1 for n in y.shape[2:]):
+        raise ValueError("%s: ker_size=%d with padding=%d leaves nothing of a %s input (needs more than %d per side)" % (
+            what, ker_size, padding, "x".join(str(int(n)) for n in y.shape[2:]), 2 * c))
+    return ops.CropBorder.apply(y, c)
+
+
 class Conv(nn.Module):
-    """nn.Conv3d / nn.Conv2d(k=3, s=1, p=1) with bias (reference: networks_3d.py:51,175,341)."""
+    """nn.Conv3d / nn.Conv2d(k=3, s=1, p=1) with bias (reference: networks_3d.py:51,175,341); ker_size 5 / 7 likewise, on the
+    tap-generic kernels."""
 
     def __init__(self, dims, in_channel, out_channel, ker_size=3, padding=1, stride=1):
         super().__init__()
-        if stride != 1 or not ((ker_size == 3 and padding in (0, 1)) or (ker_size == 1 and padding == 0)):
-            raise NotImplementedError("the MI355X path implements ker_size=3 with padding in {0, 1} and ker_size=1 with padding 0, stride=1")
+        if not _wide_ok(ker_size, padding, stride) and (
+                stride != 1 or not ((ker_size == 3 and padding in (0, 1)) or (ker_size == 1 and padding == 0))):
+            raise NotImplementedError("the MI355X path implements ker_size=3 with padding in {0, 1}, ker_size=1 with padding 0 and "
+                                      "ker_size in {5, 7} with 0 <= padding <= ker_size // 2, stride=1")
         self.dims = dims
         self.ker_size = ker_size
         # a 1x1(x1) convolution (Encode3DVAE1x1, networks_3d.py:141-160) = the 3x3(x3) 'same' conv of its centre-embedded weight
-        self.padding = padding if ker_size == 3 else 1
+        self.padding = padding if ker_size != 1 else 1
         self.weight = nn.Parameter(torch.empty(out_channel, in_channel, *((ker_size,) * dims)))
         self.bias = nn.Parameter(torch.empty(out_channel))
         init.kaiming_uniform_(self.weight, a=math.sqrt(5))
@@ -45,6 +68,12 @@ class Conv(nn.Module):
     def forward(self, x, act=False, in_act=False, in_bits=None):
         """in_act: x is the activated output of a spectral-norm block that left its LeakyReLU backward to this conv
         (ops.Conv: the mask rides in this layer's backward-data epilogue); in_bits: its 1-bit form from the producer."""
+        if self.ker_size in WIDE_KER_SIZES:
+            if self.halo is not None:
+                raise NotImplementedError("row slabs exchange one boundary row per conv: ker_size=%d is not implemented on them" % self.ker_size)
+            same = self.padding == self.ker_size // 2
+            y = ops.Conv.apply(x, self.weight, self.bias, act, in_act, False, in_bits if same else None)
+            return crop_wide(y, self.ker_size, self.padding, "Conv(%d -> %d)" % (self.weight.shape[1], self.weight.shape[0]))
         w = self.weight if self.ker_size == 3 else embed_center(self.weight, self.dims)
         if self.halo is not None:
             assert self.padding == 1, "row slabs are implemented for the 'same' convolutions of the HP-VAE-GAN path"
@@ -71,10 +100,13 @@ class SNConv(nn.Module):
 
     def __init__(self, dims, in_channel, out_channel, ker_size=3, padding=1, stride=1):
         super().__init__()
-        if stride != 1 or not ((ker_size == 3 and padding == 1) or (ker_size == 1 and padding == 0)):
-            raise NotImplementedError("the MI355X path implements ker_size=3 / padding=1 (reference defaults) and ker_size=1 / padding=0, stride=1")
+        if not _wide_ok(ker_size, padding, stride) and (
+                stride != 1 or not ((ker_size == 3 and padding == 1) or (ker_size == 1 and padding == 0))):
+            raise NotImplementedError("the MI355X path implements ker_size=3 / padding=1 (reference defaults), ker_size=1 / padding=0 and "
+                                      "ker_size in {5, 7} with 0 <= padding <= ker_size // 2, stride=1")
         self.dims = dims
         self.ker_size = ker_size
+        self.padding = padding
         weight = torch.empty(out_channel, in_channel, *((ker_size,) * dims))
         init.kaiming_uniform_(weight, a=math.sqrt(5))
         bias = torch.empty(out_channel)
@@ -100,6 +132,14 @@ class SNConv(nn.Module):
         (the LeakyReLU backward of a chain of activated convs rides in the consumer's backward-data epilogue).
         Returns (y, bits): bits = the 1-bit mask of y for the consumer (None on row slabs or without mask_by_consumer)."""
         w = weight if weight is not None else self.effective_weight()
+        if self.ker_size in WIDE_KER_SIZES:
+            if self.halo is not None:
+                raise NotImplementedError("row slabs exchange one boundary row per conv: ker_size=%d is not implemented on them" % self.ker_size)
+            if self.padding != self.ker_size // 2:
+                # (the 1-bit mask would describe the uncropped output: the consumer reads the mask from the activation itself)
+                y = ops.Conv.apply(x, w, self.bias, act, in_act, mask_by_consumer, in_bits)
+                return crop_wide(y, self.ker_size, self.padding, "SNConv(%d -> %d)" % (w.shape[1], w.shape[0])), None
+            return ops.Conv.apply_bits(x, w, self.bias, act, in_act, mask_by_consumer, in_bits)
         if self.ker_size == 1:
             w = embed_center(w, self.dims)
         if self.halo is not None:
@@ -534,6 +574,14 @@ class GeneratorVAE_nb(GeneratorHPVAEGAN):
         raise NotImplementedError("the merged rec + rand pass is built for GeneratorHPVAEGAN")
 
 
+def _baselines_ker_size(opt, name):
+    """The SinGAN baselines pad every volume by num_layer + 2 (or num_layer) voxels per side for their VALID convolutions: that
+    is the shrinkage of 3-tap convs only, here as in the reference."""
+    if int(opt.ker_size) != 3:
+        raise NotImplementedError("%s: the SinGAN baselines' hard-wired pads of num_layer + 2 voxels fit ker_size=3 only "
+                                  "(in the reference too), got ker_size=%d" % (name, int(opt.ker_size)))
+
+
 def weights_init(m):
     """N(0, 0.02) conv weights, N(1, 0.02) BatchNorm scale, zero BatchNorm shift (reference: networks_3d.py:9-15;
     applied to the SinGAN baselines only)."""
@@ -552,6 +600,7 @@ class GeneratorSG(nn.Module):
 
     def __init__(self, opt):
         super().__init__()
+        _baselines_ker_size(opt, "GeneratorSG")
         self.opt = opt
         N = int(opt.nfc)
         self.pad = opt.num_layer + 2
@@ -607,6 +656,7 @@ class GeneratorCSG(nn.Module):
 
     def __init__(self, opt):
         super().__init__()
+        _baselines_ker_size(opt, "GeneratorCSG")
         self.opt = opt
         N = int(opt.nfc)
         self.pad = opt.num_layer
@@ -656,6 +706,7 @@ class WDiscriminatorBaselines(nn.Module):
 
     def __init__(self, opt):
         super().__init__()
+        _baselines_ker_size(opt, "WDiscriminatorBaselines")
         self.opt = opt
         N = int(opt.nfc)
         self.pad = opt.num_layer + 2

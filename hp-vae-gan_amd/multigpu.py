@@ -194,6 +194,12 @@ class HipBackend:
         """plan = slab.SlabPlan or None: row slabs on the generator levels the plan covers (halo swaps on their convs,
         BatchNorm sums per `level_sync(level)`) and on every conv of the discriminator."""
         from .modules._nets import BatchNorm, Conv, SNConv
+        if plan is not None:
+            wide = [m.ker_size for net in (netG, netD) if net is not None for m in net.modules()
+                    if isinstance(m, (Conv, SNConv)) and m.ker_size > 3]
+            if wide:
+                raise NotImplementedError("row slabs (8-rank mode) exchange one boundary row per conv: ker_size=%d > 3 is not "
+                                          "implemented on them; use the 2- or 4-rank schedule" % max(wide))
         netG.slab = plan
         for k, block in enumerate(netG.body):
             on = plan is not None and plan.covers(k + 1)

@@ -24,7 +24,8 @@ class KernelTimer:
 
     def __init__(self, match):
         """match(desc) -> a family name (str) for launches to time, else None.  desc: {"op": "conv" | "wgrad", "Cin", "Cout",
-        "KT", and for convs "flip", "var"} in the kernel's view."""
+        "KT", and for convs "flip", "var"} in the kernel's view; launches of the tap-generic family (5 or 7 taps per axis)
+        also carry "K", the tap side."""
         self.match = match
         self.events = []
 
@@ -103,16 +104,25 @@ def geom(x):
     return B, C, T, H, W
 
 
+TAP_SIDES = (3, 5, 7)    # 3: the tuned family (hpvg_conv_*); 5 and 7: the tap-generic family (hpvg_convk_*)
+
+
+def _side(w_shape):
+    """Tap side K of a cubic conv weight [Co][Ci][K][K](, [K]); anything but a cube of side 3, 5 or 7 is refused."""
+    nd = len(w_shape) - 2
+    if nd not in (2, 3):
+        raise RuntimeError("bad weight shape %s" % (tuple(w_shape),))
+    k = int(w_shape[2])
+    if tuple(w_shape[2:]) != (k,) * nd or k not in TAP_SIDES:
+        raise RuntimeError("only %s kernels with K in {3, 5, 7} are supported on the MI355X path, got %s" % (
+            "KxKxK" if nd == 3 else "KxK", tuple(w_shape),))
+    return k
+
+
 def _kt(w_shape):
-    if len(w_shape) == 5:
-        if tuple(w_shape[2:]) != (3, 3, 3):
-            raise RuntimeError("only 3x3x3 kernels are supported on the MI355X path, got %s" % (tuple(w_shape),))
-        return 3
-    if len(w_shape) == 4:
-        if tuple(w_shape[2:]) != (3, 3):
-            raise RuntimeError("only 3x3 kernels are supported on the MI355X path, got %s" % (tuple(w_shape),))
-        return 1
-    raise RuntimeError("bad weight shape %s" % (tuple(w_shape),))
+    """KT of the C ABI: the tap side for 3-D weights, 1 for 2-D."""
+    k = _side(w_shape)
+    return k if len(w_shape) == 5 else 1
 
 
 # ------------------------------------------------------------------------------------------ raw launches
@@ -146,6 +156,8 @@ def pack_weight(w, flip, geom_k=None):
     w = _c(w)
     Co, Ci = w.shape[0], w.shape[1]
     KT = _kt(w.shape)
+    if _side(w.shape) != 3:
+        return w      # the tap-generic launches take the natural layout (they pack into their workspace per launch)
     cin_k, cout_k = (Co, Ci) if flip else (Ci, Co)
     has2d = _wants_2d(geom_k, cin_k, cout_k, KT)
     key = (w.data_ptr(), bool(flip), tuple(w.shape))
@@ -173,7 +185,7 @@ def prepack_weights(ws, flips=(False, True), geom_k=None):
     pack_weight.  geom_k = (B, T, H, W) of the launches that will read them (see pack_weight)."""
     items = []
     for w in ws:
-        if w.dim() < 4 or w.shape[0] != w.shape[1] or w.shape[0] <= 4 or not w.is_contiguous():
+        if w.dim() < 4 or w.shape[0] != w.shape[1] or w.shape[0] <= 4 or not w.is_contiguous() or _side(w.shape) != 3:
             continue
         for f in flips:
             key = (w.data_ptr(), bool(f), tuple(w.shape))
@@ -217,8 +229,30 @@ def conv_fwd_raw(x, w, bias, out_lrelu=False, flip=False, in_affine=None, in_lre
     cin_k, cout_k = (Co_l, Ci_l) if flip else (Ci_l, Co_l)
     if C != cin_k:
         raise RuntimeError("conv: input has %d channels, weight expects %d" % (C, cin_k))
-    wp = pack_weight(w, flip, (B, T, H, W))
     shape = (B, cout_k, T, H, W) if x.dim() == 5 else (B, cout_k, H, W)
+    K = _side(w.shape)
+    if K != 3:
+        # the tap-generic family: natural-layout weight, fp32 out_mask only (no 1-bit mask forms, no BatchNorm prologue)
+        if in_affine is not None or in_lrelu:
+            raise NotImplementedError("conv: the fused BatchNorm prologue exists for 3-tap weights only")
+        if (x.dim() == 5) != (w.dim() == 5):
+            raise RuntimeError("conv: a %d-D activation with a %d-D weight" % (x.dim(), w.dim()))
+        if mask_bits is not None and out_mask is None:
+            raise RuntimeError("conv: a %d-tap conv takes the fp32 out_mask, not mask_bits" % K)
+        if out_mask is not None and tuple(out_mask.shape) != tuple(shape):
+            raise RuntimeError("conv: out_mask has shape %s, the output %s" % (tuple(out_mask.shape), tuple(shape)))
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        timed = None
+        if _kernel_timer is not None:
+            timed = _kernel_timer.begin({"op": "conv", "Cin": cin_k, "Cout": cout_k, "KT": KT, "K": K, "flip": flip,
+                                         "var": "mask" if out_mask is not None else "plain"})
+        ws = _scratch(call("hpvg_convk_fwd_ws_bytes", B, cin_k, cout_k, T, H, W, KT, K), x.device)
+        call("hpvg_convk_fwd_f32", ptr(x), ptr(_c(w)), ptr(bias), ptr(y), 1 if out_lrelu else 0,
+             ptr(_c(out_mask)) if out_mask is not None else None, 1 if flip else 0, *ws, B, cin_k, cout_k, T, H, W, KT, K, stream())
+        if timed is not None:
+            _kernel_timer.end(timed, (B, cin_k, cout_k, T, H, W))
+        return (y, None) if want_bits else y
+    wp = pack_weight(w, flip, (B, T, H, W))
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     sc = sh = None
     if in_affine is not None:
@@ -276,6 +310,17 @@ def conv_bwd_weight_raw(dy, x, w_shape, into=None):
     KT = _kt(w_shape)
     if (Co, Ci) != (w_shape[0], w_shape[1]):
         raise RuntimeError("conv_bwd_weight: channel mismatch")
+    K = _side(w_shape)
+    if K != 3:
+        if (dy.dim() == 5) != (len(w_shape) == 5) or tuple(x.shape[2:]) != tuple(dy.shape[2:]) or x.shape[0] != B:
+            raise RuntimeError("conv_bwd_weight: dy %s, x %s, weight %s" % (tuple(dy.shape), tuple(x.shape), tuple(w_shape)))
+        ws = _scratch(call("hpvg_convk_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT, K), dy.device)
+        dw = into if into is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=dy.device)
+        timed = _kernel_timer.begin({"op": "wgrad", "Cin": Ci, "Cout": Co, "KT": KT, "K": K, "bias": False}) if _kernel_timer is not None else None
+        call("hpvg_convk_bwd_weight_f32", ptr(dy), ptr(x), ptr(dw), 1 if into is not None else 0, *ws, B, Ci, Co, T, H, W, KT, K, stream())
+        if timed is not None:
+            _kernel_timer.end(timed, (B, Ci, Co, T, H, W))
+        return None if into is not None else dw
     ws = _scratch(call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT), dy.device)
     dw = into if into is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=dy.device)
     timed = _kernel_timer.begin({"op": "wgrad", "Cin": Ci, "Cout": Co, "KT": KT, "bias": False}) if _kernel_timer is not None else None
@@ -294,7 +339,7 @@ def conv_bwd_weight_bias_raw(dy, x, w_shape, into_w, into_b):
     B, Co, T, H, W = geom(dy)
     Ci = x.shape[1]
     KT = _kt(w_shape)
-    if load().hpvg_conv_bwd_weight_fuses_bias(B, Ci, Co, T, H, W, KT) != 1:
+    if _side(w_shape) != 3 or load().hpvg_conv_bwd_weight_fuses_bias(B, Ci, Co, T, H, W, KT) != 1:
         return False
     ws = _scratch(call("hpvg_conv_bwd_weight_ws_bytes", B, Ci, Co, T, H, W, KT), dy.device)
     timed = _kernel_timer.begin({"op": "wgrad", "Cin": Ci, "Cout": Co, "KT": KT, "bias": True}) if _kernel_timer is not None else None

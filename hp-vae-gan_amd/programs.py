@@ -125,6 +125,18 @@ def trainer_parser(name, description, video=True):
     return p
 
 
+def check_tap_flags(ker_size, padd_size):
+    """End the program on a --ker-size the convolutions do not have, or a --padd-size that does not keep the generator's levels
+    'same' for a --ker-size of 5 or 7 (--ker-size 1 and 3 are taken as before)."""
+    if ker_size in (1, 3):
+        return
+    if ker_size not in (5, 7):
+        raise SystemExit("--ker-size {}: the convolutions run 3, 5 or 7 taps per axis (and 1)".format(ker_size))
+    if padd_size != ker_size // 2:
+        raise SystemExit("--ker-size {} needs --padd-size ker_size // 2 = {} (got {}): every generator level adds its block's "
+                         "output to its input, so the block must keep the size".format(ker_size, ker_size // 2, padd_size))
+
+
 def build_parser(kind):
     """The reference's parser of train_video.py (kind 'video') or train_image.py ('image'): same names, types, defaults and
     `required`; plus --run-dir and --no-hip-graph."""
@@ -337,6 +349,11 @@ class Program:
     def program_name(self):
         return self.program or 'train_' + self.kind
 
+    def check_taps(self, opt):
+        """--ker-size / --padd-size, before anything is set up: 5 and 7 taps run with the padding that keeps the generator's
+        levels 'same' (the residual of every level adds the block's output to its input)."""
+        check_tap_flags(opt.ker_size, opt.padd_size)
+
     def check_flags(self, opt):
         assert opt.vae_levels > 0
         if self.kind == 'image' and opt.data_rep < opt.batch_size:
@@ -372,6 +389,7 @@ class Program:
         # of the run it continues, and --video-path / --image-path are `required`
         argv, flags, self.resume_snapshot = snapshot.resolve(sys.argv[1:] if argv is None else argv, self.program_name())
         opt = self.parser().parse_args(argv)
+        self.check_taps(opt)
         for name in ('snapshot_interval', 'snapshot_exit_after', 'resume'):
             delattr(opt, name)   # the run's own business, not a setting of the experiment (opt.json stays what it was)
         self.snap_interval, self.snap_exit_after = flags.snapshot_interval, flags.snapshot_exit_after

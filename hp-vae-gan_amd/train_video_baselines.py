@@ -90,6 +90,11 @@ class BaselineProgram(Program):
     def parser(self):
         return snapshot.add_flags(build_baseline_parser())
 
+    def check_taps(self, opt):
+        if opt.ker_size != 3:
+            raise SystemExit("--ker-size {}: the SinGAN baselines' hard-wired pads of num_layer + 2 voxels fit ker_size=3 only "
+                             "(in the reference too)".format(opt.ker_size))
+
     def check_flags(self, opt):
         """None of train_video's: there are no VAE levels."""
 

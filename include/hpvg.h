@@ -150,6 +150,36 @@ int hpvg_conv_bwd_weight_wino_plan(int B, int Cin, int Cout, int T, int H, int W
 /* host only: tile plan of the two-axis Winograd weight-gradient kernel: out[0..9] as above, out[10] = 1 when the shape runs it by
  * default (size rule) */
 int hpvg_conv_bwd_weight_wino2_plan(int B, int Cin, int Cout, int T, int H, int W, int KT, int* out11);
+/* ---- tap-generic convolution: nn.Conv3d / nn.Conv2d with ker_size K in {3, 5, 7}, stride 1, zero padding K / 2 (the
+ * reference's --ker-size, train_video.py:275; networks_3d.py:51,63,175 with opt.ker_size != 3).  KT = K: K x K x K taps,
+ * KT = 1: K x K taps (T = 1).  Both run on the exact-fp32 matrix cores; the Python layer routes weights of tap side 5 and 7
+ * here and never a 3-tap weight (K = 3 is accepted so that the family can be held against the tuned one).
+ *   Forward / backward-data.  w: the LAYER weight in its natural layout, [Cout][Cin][KT][K][K] in the kernel's view for
+ * flip == 0.  flip != 0 runs the backward-data conv of a layer weight [Cin][Cout][KT][K][K] (kernel view: Cin = the layer's
+ * Cout, Cout = the layer's Cin): the conv with W'[o][c][tap] = w[c][o][ntaps - 1 - tap].  y = conv(x, W) + bias (nullable),
+ * then LeakyReLU(0.2) when out_lrelu, then y *= (out_mask > 0 ? 1 : 0.2) when out_mask (shaped like y) is given.  No fused
+ * BatchNorm prologue and no 1-bit mask form.  Any Cin >= 1 and Cout >= 1.
+ *   ws: hpvg_convk_fwd_ws_bytes() bytes, 16-byte aligned, required: each call first writes the weight there in MFMA fragment
+ * order (a launch of its own on `stream`) and the conv reads it; nothing is kept between calls, so the result is a function
+ * of the arguments alone and two calls with the same inputs give the same bits.
+ *   Weight gradient.  dw[o][c][tap] (+)= sum_{b,pos} dy[b][o][pos] * x[b][c][pos + off(tap)], zero outside the volume; dw in
+ * the natural layout [Cout][Cin][KT][K][K]; accumulate != 0: dw += result.  Partial sums over position ranges go through ws
+ * (hpvg_convk_bwd_weight_ws_bytes() bytes, 16-byte aligned) and are added in a fixed order by a second launch: no float
+ * atomics.
+ *   Both: no allocation, no host synchronisation, capturable; tensors need 4-byte alignment only; nothing outside a tensor
+ * is read or written.  HPVG_ERR_ARG: K not in {3, 5, 7}, KT not in {1, K}, a size < 1, KT == 1 with T != 1, a null x / w / y
+ * (dy / x / dw).  HPVG_ERR_WORKSPACE: ws null, not 16-byte aligned, or shorter than the _ws_bytes() of the same arguments.
+ * HPVG_ERR_UNSUPPORTED: T * H * W >= 2^31, or 2^24 spatial tiles and more.  _ws_bytes(): 0 for arguments the call refuses. */
+size_t hpvg_convk_fwd_ws_bytes(int B, int Cin, int Cout, int T, int H, int W, int KT, int K);
+int hpvg_convk_fwd_f32(const float* x, const float* w, const float* bias, float* y, int out_lrelu, const float* out_mask, int flip,
+                       void* ws, size_t ws_bytes, int B, int Cin, int Cout, int T, int H, int W, int KT, int K, void* stream);
+/* host only: how many 32-channel M tiles a workgroup of the forward kernel takes when Cout > 32: 0 = by size (two once that
+ * grid has more workgroups than the chip has CUs, else one), 1 = always one, 2 = always two; any other argument leaves the setting as it is;
+ * returns the mode in force.  Every output's sum has the same order in both forms: the bits do not depend on it. */
+int hpvg_convk_fwd_mt_config(int mode);
+size_t hpvg_convk_bwd_weight_ws_bytes(int B, int Cin, int Cout, int T, int H, int W, int KT, int K);
+int hpvg_convk_bwd_weight_f32(const float* dy, const float* x, float* dw, int accumulate, void* ws, size_t ws_bytes, int B, int Cin,
+                              int Cout, int T, int H, int W, int KT, int K, void* stream);
 /* out[c] = sum_{b,s} x[b][c][s]: conv bias gradient.  accumulate != 0: out[c] += (the caller passes the parameter's
  * gradient buffer, which removes autograd's AccumulateGrad add kernel) */
 size_t hpvg_channel_sum_ws_bytes(int C);

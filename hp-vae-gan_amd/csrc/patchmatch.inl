@@ -50,7 +50,7 @@ inline bool pm_geom(PmGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, c
   g.Hq = Hq; g.Wq = Wq; g.Hr = Hr; g.Wr = Wr;
   g.gT = p.q.nT; g.gH = p.q.nY; g.gW = p.q.nX;
   g.kT = p.r.nT; g.kH = p.r.nY; g.kW = p.r.nX;
-  g.pt = p.pt; g.ph = p.ph; g.pw = p.pw;
+  g.pt = p.p.pt; g.ph = p.p.ph; g.pw = p.p.pw;
   g.run = 3 * g.pw; g.nw = g.run >> 2; g.tail = g.run & 3;
   g.lrow = ((PM_TX + g.pw - 1) * 3 + 3) & ~3;
   g.lrows = PM_TY + g.ph - 1;

@@ -43,6 +43,8 @@
 // barrier per step).  LDS rows are 80 bytes apart, so the 16 rows a quarter-wave reads lie on 16 different 16-byte bank slots.
 // A and B fragments are read the same way from row-major [row][k] images (lane l: row l & 31, 16 bytes at k = 16 * (l >> 5)),
 // so whatever order the instruction gives the 32 k values, both operands use the same one and the dot product is unaffected.
+// That loop exists once, as pnn_tile_products: every search kernel here and in patchnn_prdc.inl is an epilogue around it, told
+// who holds which row by pnn_lane / pnn_acc_row / pnn_row_norms.  Host: pnn_patch, pnn_pack_side, pnn_splits, pnn_ws.
 //
 // Exact sliced Wasserstein patch distance (the evaluate program's --swd): the same packed patch matrix against a small int8
 // matrix of directions S[P][D] with entries in {-1, 0, +1}.  proj = sum_k S[p][k] * (byte[i][k] - 128) lies in
@@ -50,7 +52,7 @@
 //   4. patchproj_pack_dirs_kernel: S -> the GEMM's second operand [P padded to 128][D padded to 64, zeros], in the k order of
 //      the patch pack (byte e of a row is byte e of the patch, (dt, dy, dx, c) raster), so the argument above keeps holding.
 //   5. patchproj_zero_kernel: clears hist[P][NB] (the entry point never relies on the caller for that).
-//   6. patchproj_hist_kernel: the NT GEMM of kernel 2 (same tile, LDS pitch and double buffering) whose epilogue never stores
+//   6. patchproj_hist_kernel: the NT GEMM of kernel 2 (pnn_tile_products on the direction tile) whose epilogue never stores
 //      the N x P products: every accumulator element of a real patch (row < N: the tile padding's zero rows would land in
 //      bin 128 D) and a real direction (p < P) increments hist[p][acc + 128 D] with a vector global atomic add.  Integer adds
 //      are associative and commutative, so the histogram is independent of the launch geometry and of timing.
@@ -96,10 +98,11 @@ struct PnnSide {
   long Npad;        // padded to PNN_TILE
 };
 
+struct PnnPatch { int pt, ph, pw, D, Dp; };  // D bytes per patch, Dp padded to PNN_BK
+
 struct PnnGeom {
   PnnSide q, r;
-  int pt, ph, pw;
-  int D, Dp;
+  PnnPatch p;
   long mq, mr;        // rows of the two packed matrices: the grids' patches, or the lengths of the subset search's lists
   long mqpad, mrpad;  // padded to PNN_TILE
   size_t off_qmat, off_rmat, off_qn, off_rn, off_keys, bytes;
@@ -128,14 +131,22 @@ inline bool pnn_patch_ok(const int* patch) {
   return d * 65025.0 < 2147483648.0;
 }
 
+inline bool pnn_patch(PnnPatch& p, const int* patch) {
+  if (!pnn_patch_ok(patch)) return false;
+  p.pt = patch[0]; p.ph = patch[1]; p.pw = patch[2];
+  p.D = 3 * p.pt * p.ph * p.pw;
+  p.Dp = (p.D + PNN_BK - 1) / PNN_BK * PNN_BK;
+  return true;
+}
+
 // the workspace of a search over mq query rows and mr reference rows
 inline void pnn_layout(PnnGeom& g, long mq, long mr) {
   g.mq = mq; g.mr = mr;
   g.mqpad = (mq + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
   g.mrpad = (mr + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
   size_t o = 0;
-  g.off_qmat = o; o = pnn_align(o + (size_t)g.mqpad * g.Dp);
-  g.off_rmat = o; o = pnn_align(o + (size_t)g.mrpad * g.Dp);
+  g.off_qmat = o; o = pnn_align(o + (size_t)g.mqpad * g.p.Dp);
+  g.off_rmat = o; o = pnn_align(o + (size_t)g.mrpad * g.p.Dp);
   g.off_qn = o; o = pnn_align(o + (size_t)g.mqpad * 4);
   g.off_rn = o; o = pnn_align(o + (size_t)g.mrpad * 4);
   g.off_keys = o; o = pnn_align(o + (size_t)g.mqpad * 8);
@@ -147,11 +158,8 @@ inline long pnn_sel_rows(bool given, long n, long N) { return !given ? N : (n < 
 
 inline bool pnn_geom(PnnGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const int* patch, const int* qstride,
                      const int* rstride) {
-  if (!pnn_patch_ok(patch)) return false;
+  if (!pnn_patch(g.p, patch)) return false;
   if (!pnn_side(g.q, Tq, Hq, Wq, patch, qstride) || !pnn_side(g.r, Tr, Hr, Wr, patch, rstride)) return false;
-  g.pt = patch[0]; g.ph = patch[1]; g.pw = patch[2];
-  g.D = 3 * g.pt * g.ph * g.pw;
-  g.Dp = (g.D + PNN_BK - 1) / PNN_BK * PNN_BK;
   pnn_layout(g, g.q.N, g.r.N);
   return true;
 }
@@ -159,23 +167,19 @@ inline bool pnn_geom(PnnGeom& g, int Tq, int Hq, int Wq, int Tr, int Hr, int Wr,
 // one volume against P directions: the packed patches, then the packed directions
 struct PpjGeom {
   PnnSide s;
-  int pt, ph, pw;
-  int D, Dp;
+  PnnPatch p;
   long Ppad;  // P padded to PNN_TILE
   long NB;    // 256 D + 1 bins
   size_t off_mat, off_dirs, bytes;
 };
 
 inline bool ppj_geom(PpjGeom& g, int T, int H, int W, const int* patch, const int* stride, int P) {
-  if (!pnn_patch_ok(patch) || P < 1 || !pnn_side(g.s, T, H, W, patch, stride)) return false;
-  g.pt = patch[0]; g.ph = patch[1]; g.pw = patch[2];
-  g.D = 3 * g.pt * g.ph * g.pw;
-  g.Dp = (g.D + PNN_BK - 1) / PNN_BK * PNN_BK;
+  if (!pnn_patch(g.p, patch) || P < 1 || !pnn_side(g.s, T, H, W, patch, stride)) return false;
   g.Ppad = ((long)P + PNN_TILE - 1) / PNN_TILE * PNN_TILE;
-  g.NB = 256L * g.D + 1;
+  g.NB = 256L * g.p.D + 1;
   size_t o = 0;
-  g.off_mat = o; o = pnn_align(o + (size_t)g.s.Npad * g.Dp);
-  g.off_dirs = o; o = pnn_align(o + (size_t)g.Ppad * g.Dp);
+  g.off_mat = o; o = pnn_align(o + (size_t)g.s.Npad * g.p.Dp);
+  g.off_dirs = o; o = pnn_align(o + (size_t)g.Ppad * g.p.Dp);
   g.bytes = o;
   return true;
 }
@@ -250,6 +254,68 @@ __device__ __forceinline__ void pnn_store_tile(signed char* sa, signed char* sb,
   }
 }
 
+// Where a thread sits in the tile: wave (wr, wc) owns rows wr * 64.. and columns wc * 64.. of the 128 x 128 products; lane
+// (lr, lh) holds column lr of each 32-wide MFMA tile and the rows pnn_acc_row(m, g, lh) of its 32-high ones.
+struct PnnLane { int wr, wc, lr, lh; };
+
+__device__ __forceinline__ PnnLane pnn_lane() {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  return {wave >> 1, wave & 1, lane & 31, lane >> 5};
+}
+
+// the row, within the wave's 64, that accumulator register g of MFMA tile m holds in a lane of half lh
+__device__ __forceinline__ int pnn_acc_row(int m, int g, int lh) { return m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh; }
+
+// this lane's 32 row norms out of the tile's 128 in LDS: qrow[m][g >> 2][g & 3] belongs to row pnn_acc_row(m, g, lh)
+__device__ __forceinline__ void pnn_row_norms(const int* qn_tile, int wr, int lh, i32x4 (&qrow)[2][4]) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) qrow[m][b] = *(const i32x4*)(qn_tile + wr * 64 + m * 32 + 8 * b + 4 * lh);
+}
+
+// One 128 x 128 tile of products: acc[m][n] of this wave's 64 x 64 quarter, rows arow0.. of A against rows brow0.. of B.  Two
+// LDS buffers, the next step's global loads in flight during the products, one barrier per step; the closing barrier also covers
+// buffer 0's last reads before the next call's first store: a workgroup walks on to its next column tile without another one.
+__device__ __forceinline__ void pnn_tile_products(const signed char* __restrict__ A, const signed char* __restrict__ B, long arow0,
+                                                  long brow0, int Dp, signed char (&lds)[2][2][PNN_TILE * PNN_LDS_ROW],
+                                                  i32x16 (&acc)[2][2]) {
+  const int tid = threadIdx.x;
+  const PnnLane t = pnn_lane();
+  const int nk = Dp / PNN_BK;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
+
+  i32x4 ra[2], rb[2];
+  pnn_load_tile(A, B, arow0, brow0, Dp, 0, tid, ra, rb);
+  pnn_store_tile(lds[0][0], lds[0][1], tid, ra, rb);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nk) pnn_load_tile(A, B, arow0, brow0, Dp, (kt + 1) * PNN_BK, tid, ra, rb);
+    const signed char* sa = lds[cur][0] + (t.wr * 64 + t.lr) * PNN_LDS_ROW + t.lh * 16;
+    const signed char* sb = lds[cur][1] + (t.wc * 64 + t.lr) * PNN_LDS_ROW + t.lh * 16;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      i32x4 fa[2], fb[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) fa[m] = *(const i32x4*)(sa + m * 32 * PNN_LDS_ROW + ks * 32);
+#pragma unroll
+      for (int n = 0; n < 2; ++n) fb[n] = *(const i32x4*)(sb + n * 32 * PNN_LDS_ROW + ks * 32);
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
+    }
+    if (kt + 1 < nk) pnn_store_tile(lds[cur ^ 1][0], lds[cur ^ 1][1], tid, ra, rb);
+    __syncthreads();
+  }
+}
+
 // grid: (row tiles, column splits).  Workgroup (x, y) owns query rows [128 x, 128 x + 128) and walks the column tiles
 // [y * tiles_per_split, (y + 1) * tiles_per_split) of the reference side.  WEIGHTED: the running minimum is the fp32 score
 // float(d2) * rw[j] instead of the int32 d2 - |q|^2 (rw: [Nr], not padded).  Its epilogue holds 64 more values in flight: left
@@ -262,12 +328,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTED ? 
     const float* __restrict__ rw, unsigned long long* __restrict__ keys, long Nq, long Nr, int Dp, int ncol_tiles,
     int tiles_per_split) {
   __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
+  const int tid = threadIdx.x;
+  const auto [wr, wc, lr, lh] = pnn_lane();
   const long arow0 = (long)blockIdx.x * PNN_TILE;
   const int jt0 = blockIdx.y * tiles_per_split;
   const int jt1 = min(jt0 + tiles_per_split, ncol_tiles);
-  const int nk = Dp / PNN_BK;
 
   typename std::conditional<WEIGHTED, float, int>::type best[2][16];
   int bj[2][16];
@@ -290,37 +355,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTED ? 
   for (int jt = jt0; jt < jt1; ++jt) {
     const long brow0 = (long)jt * PNN_TILE;
     i32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
-
-    i32x4 ra[2], rb[2];
-    pnn_load_tile(A, B, arow0, brow0, Dp, 0, tid, ra, rb);  // (the K loop's closing barrier covers buffer 0's last reads)
-    pnn_store_tile(lds[0][0], lds[0][1], tid, ra, rb);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) pnn_load_tile(A, B, arow0, brow0, Dp, (kt + 1) * PNN_BK, tid, ra, rb);
-      const signed char* sa = lds[cur][0] + (wr * 64 + lr) * PNN_LDS_ROW + lh * 16;
-      const signed char* sb = lds[cur][1] + (wc * 64 + lr) * PNN_LDS_ROW + lh * 16;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        i32x4 fa[2], fb[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) fa[m] = *(const i32x4*)(sa + m * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-        for (int n = 0; n < 2; ++n) fb[n] = *(const i32x4*)(sb + n * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
-      }
-      if (kt + 1 < nk) pnn_store_tile(lds[cur ^ 1][0], lds[cur ^ 1][1], tid, ra, rb);
-      __syncthreads();
-    }
+    pnn_tile_products(A, B, arow0, brow0, Dp, lds, acc);
 
     // epilogue: this lane's column of each 32-wide tile against its running minima.  Columns are visited in ascending
     // order (jt, then n), so a strict < keeps the smallest index among equals.  qn is added once, after the merge.
@@ -345,12 +380,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTED ? 
       // weighted: the score depends on the row's norm too, so the whole exact d2 is formed here, converted (v_cvt_f32_i32
       // rounds to nearest even) and multiplied once.  A padded column gets the weight +inf: its score is +inf, or NaN where
       // d2 == 0, and neither passes the strict <; nor does a NaN weight.  No per-element branch.
-      // this lane's 32 row norms: register g of tile m is row m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh
       i32x4 qrow[2][4];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) qrow[m][b] = *(const i32x4*)(qns + wr * 64 + m * 32 + 8 * b + 4 * lh);
+      pnn_row_norms(qns, wr, lh, qrow);
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         const long j = brow0 + wc * 64 + n * 32 + lr;
@@ -371,49 +402,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTED ? 
     }
   }
 
-  // merge the 32 lanes (columns) of each row, then one atomic per row and wave
-  if constexpr (!WEIGHTED) {
+  // merge the 32 lanes (columns) of each row, then one atomic per row and wave.  Weighted: scores are >= +0 (or +inf), so
+  // their bit patterns compare like the floats; a lane that never won carries (+inf, INT_MAX) and loses to every lane that
+  // did, and a row nobody won keeps its preset key.
+  using Key = typename std::conditional<WEIGHTED, unsigned, int>::type;
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        int b = best[m][g], j = bj[m][g];
+    for (int g = 0; g < 16; ++g) {
+      Key b;
+      if constexpr (WEIGHTED) b = __float_as_uint(best[m][g]);
+      else b = best[m][g];
+      int j = bj[m][g];
 #pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-          const int ob = __shfl_xor(b, o, 64), oj = __shfl_xor(j, o, 64);
-          if (ob < b || (ob == b && oj < j)) {
-            b = ob;
-            j = oj;
-          }
-        }
-        const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
-        if (lr == 0 && row < Nq && b != INT_MAX) {
-          const unsigned d2 = (unsigned)qn[row] + (unsigned)b;
-          atomicMin(&keys[row], ((unsigned long long)d2 << 32) | (unsigned)j);
+      for (int o = 16; o > 0; o >>= 1) {
+        const Key ob = (Key)__shfl_xor((int)b, o, 64);
+        const int oj = __shfl_xor(j, o, 64);
+        if (ob < b || (ob == b && oj < j)) {
+          b = ob;
+          j = oj;
         }
       }
-  } else {
-    // weighted: scores are >= +0 (or +inf), so their bit patterns compare like the floats; a lane that never won carries
-    // (+inf, INT_MAX) and loses to every lane that did.  A row nobody won keeps its preset key.
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        unsigned b = __float_as_uint(best[m][g]);
-        int j = bj[m][g];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-          const unsigned ob = (unsigned)__shfl_xor((int)b, o, 64);
-          const int oj = __shfl_xor(j, o, 64);
-          if (ob < b || (ob == b && oj < j)) {
-            b = ob;
-            j = oj;
-          }
-        }
-        const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+      const long row = arow0 + wr * 64 + pnn_acc_row(m, g, lh);
+      if constexpr (WEIGHTED) {
         if (lr == 0 && row < Nq && j != INT_MAX) atomicMin(&keys[row], ((unsigned long long)b << 32) | (unsigned)j);
+      } else if (lr == 0 && row < Nq && b != INT_MAX) {
+        const unsigned d2 = (unsigned)qn[row] + (unsigned)b;
+        atomicMin(&keys[row], ((unsigned long long)d2 << 32) | (unsigned)j);
       }
-  }
+    }
 }
 
 __global__ __launch_bounds__(256) void patchnn_unpack_kernel(const unsigned long long* __restrict__ keys, int* __restrict__ d2,
@@ -620,45 +637,13 @@ __global__ __launch_bounds__(256) void patchproj_hist_kernel(const signed char* 
                                                               int* __restrict__ hist, long N, int P, int Dp, long NB, int offset,
                                                               int ndir_tiles) {
   __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
+  const auto [wr, wc, lr, lh] = pnn_lane();
   const long xrow0 = (long)blockIdx.x * PNN_TILE;
-  const int nk = Dp / PNN_BK;
 
   for (int jt = 0; jt < ndir_tiles; ++jt) {
     const long prow0 = (long)jt * PNN_TILE;
     i32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
-
-    i32x4 ra[2], rb[2];
-    pnn_load_tile(S, X, prow0, xrow0, Dp, 0, tid, ra, rb);  // (the K loop's closing barrier covers buffer 0's last reads)
-    pnn_store_tile(lds[0][0], lds[0][1], tid, ra, rb);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) pnn_load_tile(S, X, prow0, xrow0, Dp, (kt + 1) * PNN_BK, tid, ra, rb);
-      const signed char* sa = lds[cur][0] + (wr * 64 + lr) * PNN_LDS_ROW + lh * 16;
-      const signed char* sb = lds[cur][1] + (wc * 64 + lr) * PNN_LDS_ROW + lh * 16;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        i32x4 fa[2], fb[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) fa[m] = *(const i32x4*)(sa + m * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-        for (int n = 0; n < 2; ++n) fb[n] = *(const i32x4*)(sb + n * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
-      }
-      if (kt + 1 < nk) pnn_store_tile(lds[cur ^ 1][0], lds[cur ^ 1][1], tid, ra, rb);
-      __syncthreads();
-    }
+    pnn_tile_products(S, X, prow0, xrow0, Dp, lds, acc);
 
     // epilogue: one increment per accumulator element of a real patch and a real direction.  The bin is in range for
     // directions in {-1, 0, +1}; the range test keeps any other input from writing outside the histogram.
@@ -669,7 +654,7 @@ __global__ __launch_bounds__(256) void patchproj_hist_kernel(const signed char* 
         const long i = xrow0 + wc * 64 + n * 32 + lr;  // this lane's patch
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const long p = prow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;  // this register's direction
+          const long p = prow0 + wr * 64 + pnn_acc_row(m, g, lh);  // this register's direction
           const long bin = (long)acc[m][n][g] + offset;
           if (i < N && p < P && bin >= 0 && bin < NB) atomicAdd(hist + (size_t)p * NB + bin, 1);
         }
@@ -737,7 +722,7 @@ int hpvg_patchnn_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const in
   if (!out3 || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
   out3[0] = (int)g.q.N;
   out3[1] = (int)g.r.N;
-  out3[2] = g.D;
+  out3[2] = g.p.D;
   return HPVG_OK;
 }
 
@@ -752,47 +737,73 @@ size_t hpvg_patchnn_ws_bytes(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, con
 
 namespace {
 
+// the pieces of a PnnGeom's workspace (the ball count's ends before keys)
+struct PnnWs { signed char *qmat, *rmat; int *qn, *rn; unsigned long long* keys; };
+
+inline PnnWs pnn_ws(const PnnGeom& g, void* ws) {
+  char* w = (char*)ws;
+  return {(signed char*)(w + g.off_qmat), (signed char*)(w + g.off_rmat), (int*)(w + g.off_qn), (int*)(w + g.off_rn),
+          (unsigned long long*)(w + g.off_keys)};
+}
+
+// pack one side: patchnn_pack_kernel over rows_pad rows, one wave per row, at most 16384 workgroups
+inline void pnn_pack_side(const unsigned char* vol, signed char* mat, int* norms, unsigned long long* keys, const PnnSide& side,
+                          const int* sel, long rows, long rows_pad, const PnnPatch& p, hipStream_t st) {
+  const long blocks = rows_pad / 4 < 16384 ? rows_pad / 4 : 16384;
+  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, st, vol, mat, norms, keys, side, sel, rows, rows_pad,
+                     p.ph, p.pw, p.D, p.Dp);
+}
+
+// the column splits of a search over nrt row tiles and nct column tiles: split until the grid has about PNN_TARGET_WGS
+// workgroups, then even the splits out (per column tiles each)
+inline void pnn_splits(long nrt, long nct, long& splits, long& per) {
+  splits = (PNN_TARGET_WGS + nrt - 1) / nrt;
+  if (splits > nct) splits = nct;
+  if (splits < 1) splits = 1;
+  per = (nct + splits - 1) / splits;
+  splits = (nct + per - 1) / per;
+}
+
+// The vote's gather reads v, nn (nq entries) and fallback while other threads write out: whether out overlaps any of them.
+inline bool pnn_vote_overlaps(const unsigned char* out, const unsigned char* fallback, const unsigned char* v, const int* nn,
+                              size_t qvoxels, size_t rvoxels, long nq) {
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + qvoxels * 3;
+  const uintptr_t in0[3] = {(uintptr_t)fallback, (uintptr_t)v, (uintptr_t)nn};
+  const size_t inb[3] = {qvoxels * 3, rvoxels * 3, (size_t)nq * 4};
+  for (int k = 0; k < 3; ++k)
+    if (o0 < in0[k] + inb[k] && in0[k] < o1) return true;
+  return false;
+}
+
 // pack both sides, the min kernel, unpack.  rweight == nullptr: d2 / nn into out0 (int); otherwise score / nn, out0 (float).
 // qsel / rsel (unweighted only): the subset search's lists, g laid out for their lengths; both null is the whole-grid search.
 int pnn_launch(const PnnGeom& g, const unsigned char* q, const unsigned char* r, const int* qsel, const int* rsel, const float* rweight,
                void* out0, int* nn, void* ws, void* stream) {
-  char* w = (char*)ws;
-  signed char* qmat = (signed char*)(w + g.off_qmat);
-  signed char* rmat = (signed char*)(w + g.off_rmat);
-  int* qn = (int*)(w + g.off_qn);
-  int* rn = (int*)(w + g.off_rn);
-  unsigned long long* keys = (unsigned long long*)(w + g.off_keys);
+  const PnnWs w = pnn_ws(g, ws);
   hipStream_t st = (hipStream_t)stream;
-  const long qblocks = g.mqpad / 4 < 16384 ? g.mqpad / 4 : 16384;
-  const long rblocks = g.mrpad / 4 < 16384 ? g.mrpad / 4 : 16384;
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)qblocks), dim3(256), 0, st, q, qmat, qn, keys, g.q, qsel, g.mq, g.mqpad, g.ph,
-                     g.pw, g.D, g.Dp);
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)rblocks), dim3(256), 0, st, r, rmat, rn, (unsigned long long*)nullptr, g.r,
-                     rsel, g.mr, g.mrpad, g.ph, g.pw, g.D, g.Dp);
+  pnn_pack_side(q, w.qmat, w.qn, w.keys, g.q, qsel, g.mq, g.mqpad, g.p, st);
+  pnn_pack_side(r, w.rmat, w.rn, nullptr, g.r, rsel, g.mr, g.mrpad, g.p, st);
   const long nrt = g.mqpad / PNN_TILE, nct = g.mrpad / PNN_TILE;
-  long splits = (PNN_TARGET_WGS + nrt - 1) / nrt;
-  if (splits > nct) splits = nct;
-  if (splits < 1) splits = 1;
-  const long per = (nct + splits - 1) / splits;
-  splits = (nct + per - 1) / per;
+  long splits, per;
+  pnn_splits(nrt, nct, splits, per);
   long ub = (g.q.N + 255) / 256;
   if (ub > 4096) ub = 4096;
   if (!rweight) {
-    hipLaunchKernelGGL(patchnn_min_kernel<false>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
-                       (const float*)nullptr, keys, g.mq, g.mr, g.Dp, (int)nct, (int)per);
+    hipLaunchKernelGGL(patchnn_min_kernel<false>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, w.qmat, w.rmat, w.qn, w.rn,
+                       (const float*)nullptr, w.keys, g.mq, g.mr, g.p.Dp, (int)nct, (int)per);
     if (!qsel && !rsel) {
-      hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (int*)out0, nn, g.q.N);
+      hipLaunchKernelGGL(patchnn_unpack_kernel, dim3((unsigned)ub), dim3(256), 0, st, w.keys, (int*)out0, nn, g.q.N);
     } else {
       if (qsel) hipLaunchKernelGGL(patchnn_fill_kernel, dim3((unsigned)ub), dim3(256), 0, st, (int*)out0, nn, g.q.N);
       long sb = (g.mq + 255) / 256;
       if (sb > 4096) sb = 4096;
-      hipLaunchKernelGGL(patchnn_unpack_subset_kernel, dim3((unsigned)sb), dim3(256), 0, st, keys, qsel, rsel, (int*)out0, nn, g.mq,
+      hipLaunchKernelGGL(patchnn_unpack_subset_kernel, dim3((unsigned)sb), dim3(256), 0, st, w.keys, qsel, rsel, (int*)out0, nn, g.mq,
                          g.q.N, g.mr, g.r.N);
     }
   } else {
-    hipLaunchKernelGGL(patchnn_min_kernel<true>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn,
-                       rweight, keys, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
-    hipLaunchKernelGGL(patchnn_unpack_weighted_kernel, dim3((unsigned)ub), dim3(256), 0, st, keys, (float*)out0, nn, g.q.N);
+    hipLaunchKernelGGL(patchnn_min_kernel<true>, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, w.qmat, w.rmat, w.qn, w.rn,
+                       rweight, w.keys, g.q.N, g.r.N, g.p.Dp, (int)nct, (int)per);
+    hipLaunchKernelGGL(patchnn_unpack_weighted_kernel, dim3((unsigned)ub), dim3(256), 0, st, w.keys, (float*)out0, nn, g.q.N);
   }
   return hpvg_launch_status();
 }
@@ -856,9 +867,9 @@ int hpvg_patch_vote_counts(int Tq, int Hq, int Wq, int Tr, int Hr, int Wr, const
   PnnGeom g;
   if (!out3 || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
   // along one axis a grid of n patches of p at stride s covers (n - 1) s + p coordinates when s <= p, and n p otherwise
-  const long ct = g.q.st <= g.pt ? (long)(g.q.nT - 1) * g.q.st + g.pt : (long)g.q.nT * g.pt;
-  const long cy = g.q.sy <= g.ph ? (long)(g.q.nY - 1) * g.q.sy + g.ph : (long)g.q.nY * g.ph;
-  const long cx = g.q.sx <= g.pw ? (long)(g.q.nX - 1) * g.q.sx + g.pw : (long)g.q.nX * g.pw;
+  const long ct = g.q.st <= g.p.pt ? (long)(g.q.nT - 1) * g.q.st + g.p.pt : (long)g.q.nT * g.p.pt;
+  const long cy = g.q.sy <= g.p.ph ? (long)(g.q.nY - 1) * g.q.sy + g.p.ph : (long)g.q.nY * g.p.ph;
+  const long cx = g.q.sx <= g.p.pw ? (long)(g.q.nX - 1) * g.q.sx + g.p.pw : (long)g.q.nX * g.p.pw;
   out3[0] = g.q.N;
   out3[1] = g.r.N;
   out3[2] = (long)Tq * Hq * Wq - ct * cy * cx;
@@ -869,16 +880,11 @@ int hpvg_patch_vote_u8(const unsigned char* v, int Tr, int Hr, int Wr, const int
                        const int* qstride, const int* rstride, const unsigned char* fallback, unsigned char* out, void* stream) {
   PnnGeom g;
   if (!v || !nn || !fallback || !out || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride)) return HPVG_ERR_ARG;
-  // the gather reads v, nn and fallback while other threads write out: out may overlap none of them
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)Tq * Hq * Wq * 3;
-  const uintptr_t in0[3] = {(uintptr_t)fallback, (uintptr_t)v, (uintptr_t)nn};
-  const size_t inb[3] = {(size_t)Tq * Hq * Wq * 3, (size_t)Tr * Hr * Wr * 3, (size_t)g.q.N * 4};
-  for (int k = 0; k < 3; ++k)
-    if (o0 < in0[k] + inb[k] && in0[k] < o1) return HPVG_ERR_ARG;
+  if (pnn_vote_overlaps(out, fallback, v, nn, (size_t)Tq * Hq * Wq, (size_t)Tr * Hr * Wr, g.q.N)) return HPVG_ERR_ARG;
   long blocks = ((long)Tq * Hq * Wq + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(patch_vote_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, nn, fallback, out, g.q, g.r,
-                     g.pt, g.ph, g.pw);
+                     g.p.pt, g.p.ph, g.p.pw);
   return hpvg_launch_status();
 }
 
@@ -898,15 +904,11 @@ int hpvg_patch_vote_wrap_u8(const unsigned char* v, int Tr, int Hr, int Wr, cons
   if (wm & 4) g.q.nX = Wq;
   if ((double)g.q.nT * (double)g.q.nY * (double)g.q.nX >= 2147483648.0) return HPVG_ERR_ARG;
   g.q.N = (long)g.q.nT * g.q.nY * g.q.nX;
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)Tq * Hq * Wq * 3;
-  const uintptr_t in0[3] = {(uintptr_t)fallback, (uintptr_t)v, (uintptr_t)nn};
-  const size_t inb[3] = {(size_t)Tq * Hq * Wq * 3, (size_t)Tr * Hr * Wr * 3, (size_t)g.q.N * 4};
-  for (int k = 0; k < 3; ++k)
-    if (o0 < in0[k] + inb[k] && in0[k] < o1) return HPVG_ERR_ARG;
+  if (pnn_vote_overlaps(out, fallback, v, nn, (size_t)Tq * Hq * Wq, (size_t)Tr * Hr * Wr, g.q.N)) return HPVG_ERR_ARG;
   long blocks = ((long)Tq * Hq * Wq + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(patch_vote_wrap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, v, nn, fallback, out, g.q, g.r,
-                     g.pt, g.ph, g.pw, wm);
+                     g.p.pt, g.p.ph, g.p.pw, wm);
   return hpvg_launch_status();
 }
 
@@ -929,18 +931,16 @@ int hpvg_patchproj_hist_u8(const unsigned char* vol, int T, int H, int W, const 
   signed char* mat = (signed char*)ws + g.off_mat;
   signed char* dmat = (signed char*)ws + g.off_dirs;
   hipStream_t st = (hipStream_t)stream;
-  const long pblocks = g.s.Npad / 4 < 16384 ? g.s.Npad / 4 : 16384;
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)pblocks), dim3(256), 0, st, vol, mat, (int*)nullptr,
-                     (unsigned long long*)nullptr, g.s, (const int*)nullptr, g.s.N, g.s.Npad, g.ph, g.pw, g.D, g.Dp);
-  long dblocks = (g.Ppad * (g.Dp / 4) + 255) / 256;
+  pnn_pack_side(vol, mat, nullptr, nullptr, g.s, nullptr, g.s.N, g.s.Npad, g.p, st);
+  long dblocks = (g.Ppad * (g.p.Dp / 4) + 255) / 256;
   if (dblocks > 4096) dblocks = 4096;
-  hipLaunchKernelGGL(patchproj_pack_dirs_kernel, dim3((unsigned)dblocks), dim3(256), 0, st, dirs, dmat, P, g.Ppad, g.D, g.Dp);
+  hipLaunchKernelGGL(patchproj_pack_dirs_kernel, dim3((unsigned)dblocks), dim3(256), 0, st, dirs, dmat, P, g.Ppad, g.p.D, g.p.Dp);
   const size_t nh = (size_t)P * g.NB;
   size_t zblocks = (nh / 4 + 255) / 256 + 1;
   if (zblocks > 8192) zblocks = 8192;
   hipLaunchKernelGGL(patchproj_zero_kernel, dim3((unsigned)zblocks), dim3(256), 0, st, hist, nh);
-  hipLaunchKernelGGL(patchproj_hist_kernel, dim3((unsigned)(g.s.Npad / PNN_TILE)), dim3(256), 0, st, mat, dmat, hist, g.s.N, P, g.Dp,
-                     g.NB, 128 * g.D, (int)(g.Ppad / PNN_TILE));
+  hipLaunchKernelGGL(patchproj_hist_kernel, dim3((unsigned)(g.s.Npad / PNN_TILE)), dim3(256), 0, st, mat, dmat, hist, g.s.N, P, g.p.Dp,
+                     g.NB, 128 * g.p.D, (int)(g.Ppad / PNN_TILE));
   return hpvg_launch_status();
 }
 

@@ -1,7 +1,8 @@
 // Included at the end of patchnn.hip: the two searches behind evaluate --prdc (improved precision / recall, Kynkaanniemi et al.
 // 2019; density / coverage, Naeem et al. 2020, on raw patches).  Both are further epilogues on patchnn_min_kernel's tile: the
-// pack kernel, the 128 x 128 tile of four waves, the LDS images, the K loop and its double buffering are those of patchnn.hip
-// (pnn_tile_products below is that loop, statement for statement); only what happens to the 64 x 64 accumulators of a wave differs.
+// pack kernel (pnn_pack_side), the 128 x 128 tile of four waves with its LDS images, K loop and double buffering
+// (pnn_tile_products), the lane coordinates (pnn_lane, pnn_acc_row, pnn_row_norms) and the column splits (pnn_splits) are
+// those of patchnn.hip; only what happens to the 64 x 64 accumulators of a wave differs.
 //
 // Self k-nearest (patchknn_self_kernel<KC>): one volume, A = B = its packed patch matrix.  For every row i the k smallest
 // d2(i, j) over j != i, j < N, ascending and with multiplicity (the exclusion is by index: another patch at distance 0
@@ -25,48 +26,6 @@
 // and commutative, so the result is independent of the launch geometry and of timing.
 
 namespace {
-
-// One 128 x 128 tile of products: acc[m][n] of this wave's 64 x 64 quarter, rows arow0.. of A against rows brow0.. of B.
-// The loop of patchnn_min_kernel: two LDS buffers, the next step's global loads in flight during the products, one barrier per
-// step; its closing barrier also covers buffer 0's last reads before the next call's first store.
-__device__ __forceinline__ void pnn_tile_products(const signed char* __restrict__ A, const signed char* __restrict__ B, long arow0,
-                                                  long brow0, int Dp, signed char (&lds)[2][2][PNN_TILE * PNN_LDS_ROW],
-                                                  i32x16 (&acc)[2][2]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
-  const int nk = Dp / PNN_BK;
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) acc[m][n][g] = 0;
-
-  i32x4 ra[2], rb[2];
-  pnn_load_tile(A, B, arow0, brow0, Dp, 0, tid, ra, rb);
-  pnn_store_tile(lds[0][0], lds[0][1], tid, ra, rb);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) pnn_load_tile(A, B, arow0, brow0, Dp, (kt + 1) * PNN_BK, tid, ra, rb);
-    const signed char* sa = lds[cur][0] + (wr * 64 + lr) * PNN_LDS_ROW + lh * 16;
-    const signed char* sb = lds[cur][1] + (wc * 64 + lr) * PNN_LDS_ROW + lh * 16;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      i32x4 fa[2], fb[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) fa[m] = *(const i32x4*)(sa + m * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-      for (int n = 0; n < 2; ++n) fb[n] = *(const i32x4*)(sb + n * 32 * PNN_LDS_ROW + ks * 32);
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[m], fb[n], acc[m][n], 0, 0, 0);
-    }
-    if (kt + 1 < nk) pnn_store_tile(lds[cur ^ 1][0], lds[cur ^ 1][1], tid, ra, rb);
-    __syncthreads();
-  }
-}
 
 // s into the ascending list: every slot keeps the smaller of itself and the travelling value, which leaves as the larger
 template <int KC>
@@ -109,8 +68,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC > 4 ? 1 
     const signed char* __restrict__ X, const int* __restrict__ xn, int* __restrict__ parts, long N, long Npad, int Dp, int ncol_tiles,
     int tiles_per_split) {
   __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
+  const auto [wr, wc, lr, lh] = pnn_lane();
   const long arow0 = (long)blockIdx.x * PNN_TILE;
   const int jt0 = blockIdx.y * tiles_per_split;
   const int jt1 = min(jt0 + tiles_per_split, ncol_tiles);
@@ -122,7 +80,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC > 4 ? 1 
     for (int g = 0; g < 16; ++g)
 #pragma unroll
       for (int t = 0; t < KC; ++t) list[m][g][t] = INT_MAX;
-  // register g of tile m is row rbase + m * 32 + (g & 3) + 8 * (g >> 2) of the matrix
+  // register g of tile m is row rbase + pnn_acc_row(m, g, 0) of the matrix (the lane half folded into the base)
   const int rbase = (int)arow0 + wr * 64 + 4 * lh;
 
   for (int jt = jt0; jt < jt1; ++jt) {
@@ -142,7 +100,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC > 4 ? 1 
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const int row = rbase + m * 32 + (g & 3) + 8 * (g >> 2);
+          const int row = rbase + pnn_acc_row(m, g, 0);
           const int s = ok && !(diag && j == row) ? rnj - 2 * acc[m][n][g] : INT_MAX;
           if (__any(s < list[m][g][KC - 1])) knn_insert<KC>(list[m][g], s);
         }
@@ -156,7 +114,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC > 4 ? 1 
     for (int g = 0; g < 16; ++g) {
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) knn_merge_lane<KC>(list[m][g], o);
-      const long row = (long)rbase + m * 32 + (g & 3) + 8 * (g >> 2);
+      const long row = (long)rbase + pnn_acc_row(m, g, 0);
       if (lr == 0 && row < N) {
         i32x4* dst = (i32x4*)(parts + (((size_t)(2 * blockIdx.y + wc)) * Npad + row) * KC);
 #pragma unroll
@@ -199,8 +157,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     const int* __restrict__ rad, int* __restrict__ count, long Nq, long Nr, int Dp, int ncol_tiles, int tiles_per_split) {
   __shared__ __attribute__((aligned(16))) signed char lds[2][2][PNN_TILE * PNN_LDS_ROW];
   __shared__ __attribute__((aligned(16))) int qn_tile[PNN_TILE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 31, lh = lane >> 5;
+  const int tid = threadIdx.x;
+  const auto [wr, wc, lr, lh] = pnn_lane();
   const long arow0 = (long)blockIdx.x * PNN_TILE;
   const int jt0 = blockIdx.y * tiles_per_split;
   const int jt1 = min(jt0 + tiles_per_split, ncol_tiles);
@@ -218,12 +176,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     i32x16 acc[2][2];
     pnn_tile_products(A, B, arow0, brow0, Dp, lds, acc);
 
-    // this lane's 32 row norms: register g of tile m is row m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh
     i32x4 qrow[2][4];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) qrow[m][b] = *(const i32x4*)(qn_tile + wr * 64 + m * 32 + 8 * b + 4 * lh);
+    pnn_row_norms(qn_tile, wr, lh, qrow);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const long j = brow0 + wc * 64 + n * 32 + lr;
@@ -243,40 +197,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
       int c = cnt[m][g];
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-      const long row = arow0 + wr * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+      const long row = arow0 + wr * 64 + pnn_acc_row(m, g, lh);
       if (lr == 0 && row < Nq && c != 0) atomicAdd(&count[row], c);
     }
-}
-
-// the column splits of a search over nrt row tiles and nct column tiles, as pnn_launch chooses them
-inline void pnn_splits(long nrt, long nct, long& splits, long& per) {
-  splits = (PNN_TARGET_WGS + nrt - 1) / nrt;
-  if (splits > nct) splits = nct;
-  if (splits < 1) splits = 1;
-  per = (nct + splits - 1) / splits;
-  splits = (nct + per - 1) / per;
 }
 
 // one volume against itself: the packed patches, their norms, then the partial lists [2 * splits][Npad][KC]
 struct KnnGeom {
   PnnSide s;
-  int pt, ph, pw;
-  int D, Dp;
+  PnnPatch p;
   int KC;
   long splits, per;
   size_t off_mat, off_norms, off_parts, bytes;
 };
 
 inline bool knn_geom(KnnGeom& g, int T, int H, int W, const int* patch, const int* stride, int k) {
-  if (k < 1 || k > 8 || !pnn_patch_ok(patch) || !pnn_side(g.s, T, H, W, patch, stride) || g.s.N <= k) return false;
-  g.pt = patch[0]; g.ph = patch[1]; g.pw = patch[2];
-  g.D = 3 * g.pt * g.ph * g.pw;
-  g.Dp = (g.D + PNN_BK - 1) / PNN_BK * PNN_BK;
+  if (k < 1 || k > 8 || !pnn_patch(g.p, patch) || !pnn_side(g.s, T, H, W, patch, stride) || g.s.N <= k) return false;
   g.KC = k <= 4 ? 4 : 8;
   const long nt = g.s.Npad / PNN_TILE;
   pnn_splits(nt, nt, g.splits, g.per);
   size_t o = 0;
-  g.off_mat = o; o = pnn_align(o + (size_t)g.s.Npad * g.Dp);
+  g.off_mat = o; o = pnn_align(o + (size_t)g.s.Npad * g.p.Dp);
   g.off_norms = o; o = pnn_align(o + (size_t)g.s.Npad * 4);
   g.off_parts = o; o = pnn_align(o + (size_t)(2 * g.splits) * g.s.Npad * g.KC * 4);
   g.bytes = o;
@@ -287,7 +228,7 @@ template <int KC>
 void knn_launch(const KnnGeom& g, const signed char* mat, const int* norms, int* parts, int* kth, int k, hipStream_t st) {
   const long nt = g.s.Npad / PNN_TILE;
   hipLaunchKernelGGL(patchknn_self_kernel<KC>, dim3((unsigned)nt, (unsigned)g.splits), dim3(256), 0, st, mat, norms, parts, g.s.N,
-                     g.s.Npad, g.Dp, (int)nt, (int)g.per);
+                     g.s.Npad, g.p.Dp, (int)nt, (int)g.per);
   long mb = (g.s.N + 255) / 256;
   if (mb > 4096) mb = 4096;
   hipLaunchKernelGGL(patchknn_merge_kernel<KC>, dim3((unsigned)mb), dim3(256), 0, st, (const int*)parts, norms, kth, g.s.N, g.s.Npad,
@@ -313,9 +254,7 @@ int hpvg_patchknn_self_u8(const unsigned char* vol, int T, int H, int W, const i
   int* norms = (int*)((char*)ws + g.off_norms);
   int* parts = (int*)((char*)ws + g.off_parts);
   hipStream_t st = (hipStream_t)stream;
-  const long pblocks = g.s.Npad / 4 < 16384 ? g.s.Npad / 4 : 16384;
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)pblocks), dim3(256), 0, st, vol, mat, norms, (unsigned long long*)nullptr, g.s,
-                     (const int*)nullptr, g.s.N, g.s.Npad, g.ph, g.pw, g.D, g.Dp);
+  pnn_pack_side(vol, mat, norms, nullptr, g.s, nullptr, g.s.N, g.s.Npad, g.p, st);
   if (g.KC == 4) knn_launch<4>(g, mat, norms, parts, kth, k, st);
   else knn_launch<8>(g, mat, norms, parts, kth, k, st);
   return hpvg_launch_status();
@@ -335,26 +274,18 @@ int hpvg_patch_ball_count_u8(const unsigned char* q, int Tq, int Hq, int Wq, con
   if (!q || !r || !ref_radius || !count || ((uintptr_t)count & 3) || !pnn_geom(g, Tq, Hq, Wq, Tr, Hr, Wr, patch, qstride, rstride))
     return HPVG_ERR_ARG;
   if (!ws || ws_bytes < g.off_keys || ((uintptr_t)ws & 15)) return HPVG_ERR_WORKSPACE;
-  char* w = (char*)ws;
-  signed char* qmat = (signed char*)(w + g.off_qmat);
-  signed char* rmat = (signed char*)(w + g.off_rmat);
-  int* qn = (int*)(w + g.off_qn);
-  int* rn = (int*)(w + g.off_rn);
+  const PnnWs w = pnn_ws(g, ws);  // w.keys is not part of this workspace
   hipStream_t st = (hipStream_t)stream;
-  const long qblocks = g.mqpad / 4 < 16384 ? g.mqpad / 4 : 16384;
-  const long rblocks = g.mrpad / 4 < 16384 ? g.mrpad / 4 : 16384;
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)qblocks), dim3(256), 0, st, q, qmat, qn, (unsigned long long*)nullptr, g.q,
-                     (const int*)nullptr, g.mq, g.mqpad, g.ph, g.pw, g.D, g.Dp);
-  hipLaunchKernelGGL(patchnn_pack_kernel, dim3((unsigned)rblocks), dim3(256), 0, st, r, rmat, rn, (unsigned long long*)nullptr, g.r,
-                     (const int*)nullptr, g.mr, g.mrpad, g.ph, g.pw, g.D, g.Dp);
+  pnn_pack_side(q, w.qmat, w.qn, nullptr, g.q, nullptr, g.mq, g.mqpad, g.p, st);
+  pnn_pack_side(r, w.rmat, w.rn, nullptr, g.r, nullptr, g.mr, g.mrpad, g.p, st);
   size_t zblocks = ((size_t)g.q.N / 4 + 255) / 256 + 1;
   if (zblocks > 8192) zblocks = 8192;
   hipLaunchKernelGGL(patchproj_zero_kernel, dim3((unsigned)zblocks), dim3(256), 0, st, count, (size_t)g.q.N);
   long splits, per;
   const long nrt = g.mqpad / PNN_TILE, nct = g.mrpad / PNN_TILE;
   pnn_splits(nrt, nct, splits, per);
-  hipLaunchKernelGGL(patchnn_ball_count_kernel, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, qmat, rmat, qn, rn, ref_radius,
-                     count, g.q.N, g.r.N, g.Dp, (int)nct, (int)per);
+  hipLaunchKernelGGL(patchnn_ball_count_kernel, dim3((unsigned)nrt, (unsigned)splits), dim3(256), 0, st, w.qmat, w.rmat, w.qn, w.rn,
+                     ref_radius, count, g.q.N, g.r.N, g.p.Dp, (int)nct, (int)per);
   return hpvg_launch_status();
 }
 

@@ -4,6 +4,7 @@ torch is used for device memory, streams and graph bookkeeping only; every arith
 hand-written gfx950 kernel in libhpvg.so.  The convolution family {Conv, ConvBwdData, ConvBwdWeight,
 LReLUMaskMul} is closed under differentiation (each backward is expressed with the other Functions), which is
 what the WGAN-GP double backward through the discriminator needs (reference: modules/utils.py:14-18)."""
+import collections
 import ctypes
 import os
 
@@ -1407,8 +1408,9 @@ def _patch_volumes(op, pairs):
     """The uint8 [T,H,W,3] views of volumes or images (all of one rank, on one device), and whether they are images."""
     vols = []
     for name, t in pairs:
-        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
-            raise RuntimeError("%s: %s must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (op, name, t.dtype, tuple(t.shape)))
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise RuntimeError("%s: %s must be uint8 [T,H,W,3] or [H,W,3], got %s %s"
+                               % (op, name, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
         if t.dim() != pairs[0][1].dim():
             raise RuntimeError("%s: %s and %s must both be volumes or both be images" % (op, pairs[0][0], name))
         if t.device != pairs[0][1].device:
@@ -1417,23 +1419,64 @@ def _patch_volumes(op, pairs):
     return vols, pairs[0][1].dim() == 3
 
 
+# what every patch op works out before its launch: the contiguous volumes (r is q for a single-volume op), whether they are
+# images, the C triples, both (T, H, W), the counts of hpvg_patchnn_counts and both patch grids
+_PatchArgs = collections.namedtuple("_PatchArgs", "q r image pa qs rs qg rg Nq Nr D grid rgrid")
+
+
+def _patch_geom(op, q, r, image, patch, qstride, rstride, qname="qstride", rname="rstride"):
+    """The _PatchArgs of volumes that are already [T,H,W,...]: triples refused by name, then hpvg_patchnn_counts, which refuses
+    every other bad argument by name."""
+    pa, qs, rs = _triple(patch, "patch", op), _triple(qstride, qname, op), _triple(rstride, rname, op)
+    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
+    counts = (ctypes.c_int * 3)()
+    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)
+    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    rgrid = tuple((rg[a] - pa[a]) // rs[a] + 1 for a in range(3))
+    return _PatchArgs(q, r, image, pa, qs, rs, qg, rg, counts[0], counts[1], counts[2], grid, rgrid)
+
+
+def _patch_args(op, pairs, patch, *strides):
+    """_patch_volumes, then _patch_geom: a (query, ref) op brings two pairs and two strides, a single-volume op one of each."""
+    vols, image = _patch_volumes(op, pairs)
+    if len(vols) == 1:
+        return _patch_geom(op, vols[0], vols[0], image, patch, strides[0], strides[0], "stride", "stride")
+    return _patch_geom(op, vols[0], vols[1], image, patch, *strides)
+
+
+def _per_ref_patch(op, name, t, dtype, Nr, rgrid, image, device):
+    """A tensor with one entry per patch of ref's grid (flat, or shaped as the grid), contiguous; its values are the caller's."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != device or \
+            tuple(t.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
+        raise RuntimeError("%s: %s must be %s [%d] or %s on %s, got %s %s on %s"
+                           % (op, name, str(dtype)[6:], Nr, rgrid[1:] if image else rgrid, device, getattr(t, "dtype", type(t)),
+                              tuple(getattr(t, "shape", ())), getattr(t, "device", None)))
+    return _c(t)
+
+
+def _ref_weight(op, w, a):
+    w = _per_ref_patch(op, "ref_weight", w, torch.float32, a.Nr, a.rgrid, a.image, a.r.device)
+    if not bool((torch.isfinite(w) & (w > 0)).all()):   # one device reduction
+        raise RuntimeError("%s: every ref_weight must be finite and > 0" % op)
+    return w
+
+
+def _ungrid(image, *outs):
+    """Outputs shaped as [gT,gH,gW,...] patch grids, without the leading 1 for images; one output comes back bare."""
+    outs = tuple(o[0] for o in outs) if image else outs
+    return outs[0] if len(outs) == 1 else outs
+
+
 def patch_nn(query_u8, ref_u8, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
     """Exact patch nearest neighbours (hpvg_patchnn_u8, i8 matrix cores): query / ref are uint8 device tensors [T,H,W,3] or
     [H,W,3]; for every patch of the query's strided grid, d2 = the smallest squared distance to a patch of ref's grid and nn =
     the smallest index (raster order of ref's grid) that attains it.  Both int32, shaped as the query's patch grid."""
-    (q, r), image = _patch_volumes("patch_nn", (("query", query_u8), ("ref", ref_u8)))
-    pa, qs, rs = _triple(patch, "patch"), _triple(qstride, "qstride"), _triple(rstride, "rstride")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, (ctypes.c_int * 3)())   # refuses bad arguments by name
-    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
-    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
-    ws = _scratch(nbytes, q.device)
-    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
-    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patchnn_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(d2), ptr(nn), *ws, stream())
-    if image:
-        d2, nn = d2[0], nn[0]
-    return d2, nn
+    a = _patch_args("patch_nn", (("query", query_u8), ("ref", ref_u8)), patch, qstride, rstride)
+    ws = _scratch(call("hpvg_patchnn_ws_bytes", *a.qg, *a.rg, a.pa, a.qs, a.rs), a.q.device)
+    d2 = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    nn = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    call("hpvg_patchnn_u8", ptr(a.q), *a.qg, ptr(a.r), *a.rg, a.pa, a.qs, a.rs, ptr(d2), ptr(nn), *ws, stream())
+    return _ungrid(a.image, d2, nn)
 
 
 def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
@@ -1441,32 +1484,13 @@ def patch_nn_weighted(query_u8, ref_u8, ref_weight, patch, qstride=(1, 1, 1), rs
     normalisation): score = min_j float32(d2_ij) * ref_weight[j], the exact int32 distance converted and multiplied once in
     fp32, and nn = the smallest j that attains it.  ref_weight: float32 device tensor of Nr entries (flat, or shaped as ref's
     patch grid), every one finite and > 0.  Returns (score float32, nn int32), shaped as the query's patch grid."""
-    (q, r), image = _patch_volumes("patch_nn_weighted", (("query", query_u8), ("ref", ref_u8)))
-    pa, qs, rs = _triple(patch, "patch", "patch_nn_weighted"), _triple(qstride, "qstride", "patch_nn_weighted"), \
-        _triple(rstride, "rstride", "patch_nn_weighted")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    counts = (ctypes.c_int * 3)()
-    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
-    Nr = counts[1]
-    rgrid = tuple((rg[a] - pa[a]) // rs[a] + 1 for a in range(3))
-    w = ref_weight
-    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != r.device or \
-            tuple(w.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
-        raise RuntimeError("patch_nn_weighted: ref_weight must be float32 [%d] or %s on %s, got %s %s on %s"
-                           % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(w, "dtype", type(w)),
-                              tuple(getattr(w, "shape", ())), getattr(w, "device", None)))
-    w = _c(w)
-    if not bool((torch.isfinite(w) & (w > 0)).all()):   # one device reduction
-        raise RuntimeError("patch_nn_weighted: every ref_weight must be finite and > 0")
-    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
-    nbytes = call("hpvg_patchnn_ws_bytes", *qg, *rg, pa, qs, rs)
-    ws = _scratch(nbytes, q.device)
-    score = torch.empty(grid, dtype=torch.float32, device=q.device)
-    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patchnn_weighted_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(w), ptr(score), ptr(nn), *ws, stream())
-    if image:
-        score, nn = score[0], nn[0]
-    return score, nn
+    a = _patch_args("patch_nn_weighted", (("query", query_u8), ("ref", ref_u8)), patch, qstride, rstride)
+    w = _ref_weight("patch_nn_weighted", ref_weight, a)
+    ws = _scratch(call("hpvg_patchnn_ws_bytes", *a.qg, *a.rg, a.pa, a.qs, a.rs), a.q.device)
+    score = torch.empty(a.grid, dtype=torch.float32, device=a.q.device)
+    nn = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    call("hpvg_patchnn_weighted_u8", ptr(a.q), *a.qg, ptr(a.r), *a.rg, a.pa, a.qs, a.rs, ptr(w), ptr(score), ptr(nn), *ws, stream())
+    return _ungrid(a.image, score, nn)
 
 
 def _wrap_flags(wrap, name, op):
@@ -1491,46 +1515,28 @@ def patch_match(query_u8, ref_u8, patch, iters, seed=0, ref_weight=None, nn_init
     entry point, exactly as before."""
     (q, r), image = _patch_volumes("patch_match", (("query", query_u8), ("ref", ref_u8)))
     qw, rw = _wrap_flags(qwrap, "qwrap", "patch_match"), _wrap_flags(rwrap, "rwrap", "patch_match")
-    pa, one = _triple(patch, "patch", "patch_match"), _triple((1, 1, 1), "stride", "patch_match")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    counts = (ctypes.c_int * 3)()
-    call("hpvg_patchnn_counts", *qg, *rg, pa, one, one, counts)   # refuses bad arguments by name
-    Nq, Nr = counts[0], counts[1]
-    grid = tuple(qg[a] - pa[a] + 1 for a in range(3))
-    rgrid = tuple(rg[a] - pa[a] + 1 for a in range(3))
-    w = ref_weight
-    if w is not None:
-        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != r.device or \
-                tuple(w.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
-            raise RuntimeError("patch_match: ref_weight must be float32 [%d] or %s on %s, got %s %s on %s"
-                               % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(w, "dtype", type(w)),
-                                  tuple(getattr(w, "shape", ())), getattr(w, "device", None)))
-        w = _c(w)
-        if not bool((torch.isfinite(w) & (w > 0)).all()):   # one device reduction
-            raise RuntimeError("patch_match: every ref_weight must be finite and > 0")
+    a = _patch_geom("patch_match", q, r, image, patch, (1, 1, 1), (1, 1, 1))
+    w = _ref_weight("patch_match", ref_weight, a) if ref_weight is not None else None
     if nn_init is not None:
-        if not isinstance(nn_init, torch.Tensor) or nn_init.dtype != torch.int32 or nn_init.numel() != Nq or nn_init.device != q.device:
+        if not isinstance(nn_init, torch.Tensor) or nn_init.dtype != torch.int32 or nn_init.numel() != a.Nq or nn_init.device != q.device:
             raise RuntimeError("patch_match: nn_init must be int32 with %d entries on %s, got %s %s on %s"
-                               % (Nq, q.device, getattr(nn_init, "dtype", type(nn_init)), tuple(getattr(nn_init, "shape", ())),
+                               % (a.Nq, q.device, getattr(nn_init, "dtype", type(nn_init)), tuple(getattr(nn_init, "shape", ())),
                                   getattr(nn_init, "device", None)))
         nn_init = _c(nn_init)
-    nbytes = call("hpvg_patchmatch_ws_bytes", *qg, *rg, pa)
+    nbytes = call("hpvg_patchmatch_ws_bytes", *a.qg, *a.rg, a.pa)
     if nbytes == 0 or not 0 <= int(iters) <= 1024:
         raise RuntimeError("patch_match: refused (a patch grid side >= 65536, or iters %r outside [0, 1024])" % (iters,))
     ws = _scratch(nbytes, q.device)
-    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
-    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    score = torch.empty(grid, dtype=torch.float32, device=q.device) if w is not None else None
+    d2 = torch.empty(a.grid, dtype=torch.int32, device=q.device)
+    nn = torch.empty(a.grid, dtype=torch.int32, device=q.device)
+    score = torch.empty(a.grid, dtype=torch.float32, device=q.device) if w is not None else None
     if qw is None and rw is None:
-        call("hpvg_patchmatch_u8", ptr(q), *qg, ptr(r), *rg, pa, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2), ptr(nn),
+        call("hpvg_patchmatch_u8", ptr(q), *a.qg, ptr(r), *a.rg, a.pa, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2), ptr(nn),
              ptr(score), *ws, stream())
     else:
-        call("hpvg_patchmatch_wrap_u8", ptr(q), *qg, ptr(r), *rg, pa, qw, rw, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2),
+        call("hpvg_patchmatch_wrap_u8", ptr(q), *a.qg, ptr(r), *a.rg, a.pa, qw, rw, ptr(w), ptr(nn_init), int(iters), int(seed), ptr(d2),
              ptr(nn), ptr(score), *ws, stream())
-    out = score if w is not None else d2
-    if image:
-        out, nn = out[0], nn[0]
-    return out, nn
+    return _ungrid(image, score if w is not None else d2, nn)
 
 
 def _patch_sel(sel, name, N, device):
@@ -1554,25 +1560,18 @@ def patch_nn_subset(query_u8, ref_u8, patch, qsel=None, rsel=None, qstride=(1, 1
     Only the selected patches are packed and compared.  Returns (d2, nn), int32, shaped as the query's patch grid: for a
     selected query patch the smallest squared distance to a selected patch of ref and the smallest index IN REF'S GRID that
     attains it; -1, -1 for every other patch (patch_vote skips those)."""
-    (q, r), image = _patch_volumes("patch_nn_subset", (("query", query_u8), ("ref", ref_u8)))
-    pa, qs, rs = _triple(patch, "patch", "patch_nn_subset"), _triple(qstride, "qstride", "patch_nn_subset"), \
-        _triple(rstride, "rstride", "patch_nn_subset")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    counts = (ctypes.c_int * 3)()
-    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
-    qp, nq, qkeep = _patch_sel(qsel, "qsel", counts[0], q.device)
-    rp, nr, rkeep = _patch_sel(rsel, "rsel", counts[1], q.device)
-    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
+    a = _patch_args("patch_nn_subset", (("query", query_u8), ("ref", ref_u8)), patch, qstride, rstride)
+    qp, nq, qkeep = _patch_sel(qsel, "qsel", a.Nq, a.q.device)
+    rp, nr, rkeep = _patch_sel(rsel, "rsel", a.Nr, a.q.device)
     # the workspace query has no list pointers to tell a null list by: there a negative count stands for one (the search itself
     # takes the null pointer and ignores the count)
-    nbytes = call("hpvg_patchnn_subset_ws_bytes", *qg, *rg, pa, qs, rs, nq if qsel is not None else -1, nr if rsel is not None else -1)
-    ws = _scratch(nbytes, q.device)
-    d2 = torch.empty(grid, dtype=torch.int32, device=q.device)
-    nn = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patchnn_subset_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, qp, nq, rp, nr, ptr(d2), ptr(nn), *ws, stream())
-    if image:
-        d2, nn = d2[0], nn[0]
-    return d2, nn
+    nbytes = call("hpvg_patchnn_subset_ws_bytes", *a.qg, *a.rg, a.pa, a.qs, a.rs, nq if qsel is not None else -1,
+                  nr if rsel is not None else -1)
+    ws = _scratch(nbytes, a.q.device)
+    d2 = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    nn = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    call("hpvg_patchnn_subset_u8", ptr(a.q), *a.qg, ptr(a.r), *a.rg, a.pa, a.qs, a.rs, qp, nq, rp, nr, ptr(d2), ptr(nn), *ws, stream())
+    return _ungrid(a.image, d2, nn)
 
 
 def patch_mask_count(mask_u8, patch, stride=(1, 1, 1)):
@@ -1584,13 +1583,10 @@ def patch_mask_count(mask_u8, patch, stride=(1, 1, 1)):
                            % (getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ()))))
     image = m.dim() == 2
     m = _c(m[None] if image else m)
-    pa, st = _triple(patch, "patch", "patch_mask_count"), _triple(stride, "stride", "patch_mask_count")
-    g = tuple(m.shape)
-    call("hpvg_patchnn_counts", *g, *g, pa, st, st, (ctypes.c_int * 3)())   # refuses bad arguments by name
-    grid = tuple((g[a] - pa[a]) // st[a] + 1 for a in range(3))
-    count = torch.empty(grid, dtype=torch.int32, device=m.device)
-    call("hpvg_patch_mask_count_u8", ptr(m), *g, pa, st, ptr(count), stream())
-    return count[0] if image else count
+    a = _patch_geom("patch_mask_count", m, m, image, patch, stride, stride, "stride", "stride")
+    count = torch.empty(a.grid, dtype=torch.int32, device=m.device)
+    call("hpvg_patch_mask_count_u8", ptr(m), *a.qg, a.pa, a.qs, ptr(count), stream())
+    return _ungrid(image, count)
 
 
 PATCH_KNN_MAX_K = 8   # hpvg_patchknn_self_u8 keeps at most this many distances per patch
@@ -1602,22 +1598,15 @@ def patch_knn_self(vol_u8, patch, k, stride=(1, 1, 1)):
     patch count.  Returns int32 [gT,gH,gW,k] ([gH,gW,k] for an image), ascending along the last axis and with multiplicity: a
     patch is excluded from its own list by index, so an exact duplicate elsewhere contributes a 0.  [..., k-1] is the radius
     of improved precision / recall."""
-    (v,), image = _patch_volumes("patch_knn_self", (("vol", vol_u8),))
-    pa, st = _triple(patch, "patch", "patch_knn_self"), _triple(stride, "stride", "patch_knn_self")
-    g = tuple(v.shape[:3])
-    counts = (ctypes.c_int * 3)()
-    call("hpvg_patchnn_counts", *g, *g, pa, st, st, counts)   # refuses bad arguments by name
-    N = counts[0]
+    a = _patch_args("patch_knn_self", (("vol", vol_u8),), patch, stride)
     if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > PATCH_KNN_MAX_K:
         raise RuntimeError("patch_knn_self: k must be an int in [1, %d], got %r" % (PATCH_KNN_MAX_K, k))
-    if N <= k:
-        raise RuntimeError("patch_knn_self: %d patches cannot have %d neighbours each (the patch count must exceed k)" % (N, k))
-    grid = tuple((g[a] - pa[a]) // st[a] + 1 for a in range(3))
-    nbytes = call("hpvg_patchknn_self_ws_bytes", *g, pa, st, k)
-    ws = _scratch(nbytes, v.device)
-    kth = torch.empty(grid + (k,), dtype=torch.int32, device=v.device)
-    call("hpvg_patchknn_self_u8", ptr(v), *g, pa, st, k, ptr(kth), *ws, stream())
-    return kth[0] if image else kth
+    if a.Nq <= k:
+        raise RuntimeError("patch_knn_self: %d patches cannot have %d neighbours each (the patch count must exceed k)" % (a.Nq, k))
+    ws = _scratch(call("hpvg_patchknn_self_ws_bytes", *a.qg, a.pa, a.qs, k), a.q.device)
+    kth = torch.empty(a.grid + (k,), dtype=torch.int32, device=a.q.device)
+    call("hpvg_patchknn_self_u8", ptr(a.q), *a.qg, a.pa, a.qs, k, ptr(kth), *ws, stream())
+    return _ungrid(a.image, kth)
 
 
 def patch_ball_count(query_u8, ref_u8, ref_radius, patch, qstride=(1, 1, 1), rstride=(1, 1, 1)):
@@ -1625,29 +1614,14 @@ def patch_ball_count(query_u8, ref_u8, ref_radius, patch, qstride=(1, 1, 1), rst
     (hpvg_patch_ball_count_u8, i8 matrix cores; d2 the exact squared distance of patch_nn).  ref_radius: int32 device tensor of
     Nr entries (flat, or shaped as ref's patch grid), every one >= 0.  Returns int32 shaped as the query's patch grid; > 0 is
     "inside some ball" (precision / recall), the sum is the numerator of density."""
-    (q, r), image = _patch_volumes("patch_ball_count", (("query", query_u8), ("ref", ref_u8)))
-    pa, qs, rs = _triple(patch, "patch", "patch_ball_count"), _triple(qstride, "qstride", "patch_ball_count"), \
-        _triple(rstride, "rstride", "patch_ball_count")
-    qg, rg = tuple(q.shape[:3]), tuple(r.shape[:3])
-    counts = (ctypes.c_int * 3)()
-    call("hpvg_patchnn_counts", *qg, *rg, pa, qs, rs, counts)   # refuses bad arguments by name
-    Nr = counts[1]
-    rgrid = tuple((rg[a] - pa[a]) // rs[a] + 1 for a in range(3))
-    rad = ref_radius
-    if not isinstance(rad, torch.Tensor) or rad.dtype != torch.int32 or rad.device != r.device or \
-            tuple(rad.shape) not in ((Nr,), rgrid, rgrid[1:] if image else rgrid):
-        raise RuntimeError("patch_ball_count: ref_radius must be int32 [%d] or %s on %s, got %s %s on %s"
-                           % (Nr, rgrid[1:] if image else rgrid, r.device, getattr(rad, "dtype", type(rad)),
-                              tuple(getattr(rad, "shape", ())), getattr(rad, "device", None)))
-    rad = _c(rad)
+    a = _patch_args("patch_ball_count", (("query", query_u8), ("ref", ref_u8)), patch, qstride, rstride)
+    rad = _per_ref_patch("patch_ball_count", "ref_radius", ref_radius, torch.int32, a.Nr, a.rgrid, a.image, a.r.device)
     if not bool((rad >= 0).all()):   # one device reduction
         raise RuntimeError("patch_ball_count: every ref_radius must be >= 0")
-    grid = tuple((qg[a] - pa[a]) // qs[a] + 1 for a in range(3))
-    nbytes = call("hpvg_patch_ball_count_ws_bytes", *qg, *rg, pa, qs, rs)
-    ws = _scratch(nbytes, q.device)
-    count = torch.empty(grid, dtype=torch.int32, device=q.device)
-    call("hpvg_patch_ball_count_u8", ptr(q), *qg, ptr(r), *rg, pa, qs, rs, ptr(rad), ptr(count), *ws, stream())
-    return count[0] if image else count
+    ws = _scratch(call("hpvg_patch_ball_count_ws_bytes", *a.qg, *a.rg, a.pa, a.qs, a.rs), a.q.device)
+    count = torch.empty(a.grid, dtype=torch.int32, device=a.q.device)
+    call("hpvg_patch_ball_count_u8", ptr(a.q), *a.qg, ptr(a.r), *a.rg, a.pa, a.qs, a.rs, ptr(rad), ptr(count), *ws, stream())
+    return _ungrid(a.image, count)
 
 
 def nnf_chunks(nn, ref_grid, qstride=(1, 1, 1), rstride=(1, 1, 1), d2=None, max_d2=None):
@@ -1751,18 +1725,13 @@ def volume_resize_u8(vol_u8, size):
     upsizing, the triangle filter over everything an output voxel stands for when downsizing - and one rounding (halves up) of
     the separable weighted mean.  An image [H,W,3] is the volume with T = 1 and takes a size of 2 entries (or 3 with T = 1).
     An equal size returns a contiguous copy.  Returns a new uint8 tensor."""
-    v = vol_u8
-    if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or v.dim() not in (3, 4) or v.shape[-1] != 3:
-        raise RuntimeError("volume_resize_u8: the volume must be uint8 [T,H,W,3] or [H,W,3], got %s %s"
-                           % (getattr(v, "dtype", type(v)), tuple(getattr(v, "shape", ()))))
-    image = v.dim() == 3
+    (src,), image = _patch_volumes("volume_resize_u8", (("the volume", vol_u8),))
     size = tuple(int(e) for e in size)
     if len(size) not in ((2, 3) if image else (3,)) or (image and len(size) == 3 and size[0] != 1):
         raise RuntimeError("volume_resize_u8: size must be (T, H, W)%s, got %s" % (" or (H, W) with T = 1" if image else "", size))
     if image and len(size) == 2:
         size = (1,) + size
-    src = _c(v[None] if image else v)
-    ptr(src)   # refuses a host tensor by name
+    ptr(src)  # refuses a host tensor by name
     sg = tuple(src.shape[:3])
     volume_resize_check(sg, size)   # refuses bad sizes by name
     if sg == size:
@@ -1793,9 +1762,7 @@ def patch_proj_hist(vol_u8, patch, dirs_i8, stride=(1, 1, 1)):
     cores): vol is a uint8 device tensor [T,H,W,3] or [H,W,3], dirs an int8 device tensor [P, D] with entries in {-1, 0, +1},
     D = 3 * t * h * w of the patch.  Returns int32 [P, NB], NB = 256 D + 1: hist[p][b] = the number of patches of the strided
     grid with sum_k dirs[p][k] * (byte[k] - 128) == b - 128 D.  Exact; every row sums to the patch count."""
-    if vol_u8.dtype != torch.uint8 or vol_u8.dim() not in (3, 4) or vol_u8.shape[-1] != 3:
-        raise RuntimeError("patch_proj_hist: vol must be uint8 [T,H,W,3] or [H,W,3], got %s %s" % (vol_u8.dtype, tuple(vol_u8.shape)))
-    v = _c(vol_u8 if vol_u8.dim() == 4 else vol_u8[None])
+    (v,), _ = _patch_volumes("patch_proj_hist", (("vol", vol_u8),))
     pa, st = _triple(patch, "patch", "patch_proj_hist"), _triple(stride, "stride", "patch_proj_hist")
     NB = patch_proj_bins(patch)
     D = (NB - 1) // 256

@@ -663,7 +663,9 @@ __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsig
   }
   return Philox4{c0, c1, c2, c3};
 }
-// four N(0,1) values from one Philox block (two Box-Muller pairs; uniforms in (0, 1) from the top 24 bits)
+// four N(0,1) values from one Philox block (two Box-Muller pairs; uniforms from the top 24 bits k: (k + 0.5) * 2^-24 rounded in
+// fp32, which lies in [2^-25, 1] - k + 0.5 rounds to even from k = 2^23 on, so k = 2^24 - 1 gives u = 1.0 exactly: as u0 a
+// radius sqrt(-0) and a pair of signed zeros, never NaN; as u1 the angle fp32 2pi.  |n| <= sqrt(-2 ln 2^-25) = 5.887)
 __device__ __forceinline__ void philox_normal4(long q, unsigned call_id, unsigned iter, unsigned long long seed, float (&n)[4]) {
   const Philox4 r = philox4x32_10((unsigned)q, (unsigned)((unsigned long long)q >> 32), call_id, iter, (unsigned)seed,
                                   (unsigned)(seed >> 32));
@@ -688,7 +690,7 @@ __global__ __launch_bounds__(256) void normal_kernel(float* __restrict__ out, lo
   }
 }
 
-// U(0,1) from the same Philox stream (reparameterize_bern's eps, networks_3d.py:40)
+// U[0, 1) from the same Philox stream: (word >> 8) * 2^-24, exact in fp32 (reparameterize_bern's eps, networks_3d.py:40)
 __global__ __launch_bounds__(256) void uniform_kernel(float* __restrict__ out, long n, unsigned long long seed, unsigned call_id,
                                                        const int* __restrict__ iter) {
   const unsigned it = iter ? (unsigned)iter[0] : 0u;

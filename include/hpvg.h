@@ -278,7 +278,10 @@ int hpvg_upsample_linear_ac_f32(const float* x, float* y, const float* noise, fl
                                 int Wi, int To, int Ho, int Wo, void* stream);
 /* ---- N(0,1) noise (utils/images.py:49 zeros(..).normal_(0,1); networks_3d.py:32 reparameterisation eps): counter-based
  * Philox4x32-10 + Box-Muller, stream = (seed, call_id, iter[0]); iter: device int bumped once per train iteration
- * (hpvg_counter_inc_i32), so a replayed hipGraph draws fresh noise with unchanged launch arguments; NULL = 0. */
+ * (hpvg_counter_inc_i32), so a replayed hipGraph draws fresh noise with unchanged launch arguments; NULL = 0.
+ * out[i] = value i % 4 of block i / 4: philox(counter = (q_lo, q_hi, call_id, iter), key = (seed_lo, seed_hi)).  The Box-Muller
+ * uniforms are (k + 0.5) * 2^-24 of the words' top 24 bits k, rounded in fp32: in [2^-25, 1], NOT the open interval (0, 1) -
+ * k = 2^24 - 1 rounds to 1.0, which as a radius gives a pair of signed zeros (never NaN); |out| <= 5.887. */
 int hpvg_normal_f32(float* out, long n, unsigned long long seed, unsigned call_id, const int* iter, void* stream);
 int hpvg_uniform_f32(float* out, long n, unsigned long long seed, unsigned call_id, const int* iter, void* stream); /* U[0,1) */
 /* resize + level noise generated in the kernel (networks_3d.py:395-400): y = resize(x), yn = y + amp * N(0,1) where the noise

@@ -1782,3 +1782,6 @@ int hpvg_state_digest_u32(const void* words, long n, unsigned long long salt, un
 }
 
 }  // extern "C"
+
+// generate --wrap: the circular pad in front of the generator's convs and the resize that interpolates across the seam
+#include "ring.inl"

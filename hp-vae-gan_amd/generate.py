@@ -1,6 +1,14 @@
 """`python -m hp_vae_gan_amd.generate --exp-dir run/<clip>/<checkname>/experiment_<n> --num-samples N`: sample videos
-(or images) from a trained experiment; writes samples.npy and one GIF / PNG per sample."""
+(or images) from a trained experiment; writes samples.npy and one GIF / PNG per sample.
+
+--size T H W (images: H W) samples at another size than the trained one: the generator is fully convolutional and its input is
+a noise volume, so every level of the pyramid is drawn at the trained ratio of the requested size (level_sizes).  --wrap AXES
+(letters of t, h, w) closes those axes into rings: every convolution of the decoder and the levels sees its input circularly
+along them and the resize between levels interpolates across the seam, so a `t` ring is a clip that loops and `hw` a tile.
+With either flag the samples go to <exp-dir>/eval/samples_<T>x<H>x<W>[_wrap<axes>] and generate.json is written beside
+samples.npy; without them every byte is what it was."""
 import argparse
+import json
 import math
 import os
 import sys
@@ -10,7 +18,8 @@ import torch
 
 from . import checkpoint, ops
 from . import utils as hp_utils
-from .programs import gpu_device, load_opt, networks_of, write_samples
+from .modules._nets import Conv
+from .programs import gpu_device, load_opt, networks_of, parse_wrap_axes, write_samples
 
 
 def generate_parser():
@@ -21,8 +30,52 @@ def generate_parser():
     p.add_argument('--num-samples', type=int, default=8, help='number of samples')
     p.add_argument('--batch-size', type=int, default=None, help='samples per generator pass (default: the run\'s)')
     p.add_argument('--seed', type=int, default=0, help='seed of the noise')
-    p.add_argument('--out', default=None, help='output directory (default: <exp-dir>/eval/samples)')
+    p.add_argument('--out', default=None, help='output directory (default: <exp-dir>/eval/samples; with --size / --wrap: '
+                   '<exp-dir>/eval/samples_<T>x<H>x<W>[_wrap<axes>])')
+    p.add_argument('--size', type=int, nargs='+', default=None, metavar='N',
+                   help='finest size T H W (images: H W) to sample at (default: the trained size)')
+    p.add_argument('--wrap', default=None, metavar='AXES',
+                   help='distinct letters of t, h, w: the axes that are rings (t: a clip that loops; hw: a tile)')
     return p
+
+
+def level_sizes(trained, size):
+    """The shape of every pyramid level for the finest shape `size`, from the trained shapes `trained` (coarsest first, the
+    last one the trained finest shape s_L).  Per level and axis, in integers: the trained side where the request equals the
+    trained finest side, otherwise max(1, round_half_up(s_l * size / s_L)).  The last level is `size`; size == s_L returns
+    `trained` itself."""
+    fine = [int(s) for s in trained[-1]]
+    size = [int(s) for s in size]
+    if len(size) != len(fine):
+        raise ValueError("level_sizes: size {} does not fit the trained shape {}".format(size, fine))
+    if min(size) < 1:
+        raise ValueError("level_sizes: every side must be >= 1, got {}".format(size))
+    if size == fine:
+        return trained
+    return [[int(s[a]) if size[a] == fine[a] else max(1, (2 * int(s[a]) * size[a] + fine[a]) // (2 * fine[a]))
+             for a in range(len(fine))] for s in trained]
+
+
+def check_request(opt, size, wrap):
+    """The refusals of --size / --wrap that need no device: host checks on the flags and opt.json.  Returns the ring flags per
+    spatial axis of the run (None without --wrap)."""
+    image = opt.dims == 2
+    if (size is not None or wrap is not None) and getattr(opt, 'program', None) == 'train_video_baselines':
+        raise SystemExit("generate: --size / --wrap are not built for a train_video_baselines experiment (its generators pad once "
+                         "per stage, not per convolution)")
+    if size is not None:
+        want = 2 if image else 3
+        if len(size) != want:
+            raise SystemExit("generate: --size takes {} for this {} run, got {} values".format(
+                "H W" if image else "T H W", "image" if image else "video", len(size)))
+        if min(size) < 1:
+            raise SystemExit("generate: --size: every side must be >= 1, got {}".format(list(size)))
+    if wrap is None:
+        return None
+    flags = parse_wrap_axes(wrap)
+    if image and flags[0]:
+        raise SystemExit("generate: --wrap t: an image run has no time axis (use letters of h, w)")
+    return flags[1:] if image else flags
 
 
 def load_generator(exp_dir, device):
@@ -36,9 +89,22 @@ def load_generator(exp_dir, device):
     return opt, netG.to(device)
 
 
-def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None):
+def set_ring(netG, ring):
+    """Close the axes flagged in `ring` (one 0 / 1 per spatial axis) on the sampling path of a GeneratorHPVAEGAN: every Conv of
+    the decoder and the body, and the generator's resize between levels."""
+    for part in (netG.decoder, netG.body):
+        for m in part.modules():
+            if isinstance(m, Conv):
+                m.ring = tuple(ring)
+    netG.ring = tuple(ring)
+
+
+def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None, size=None, wrap=None):
     """Draw `num_samples` samples in groups of batch_size (train mode, no_grad: BatchNorm statistics per group, as the
-    reference's previews); write samples.npy (uint8 [N, T, H, W, 3], images [N, H, W, 3]) and one GIF / PNG per sample."""
+    reference's previews); write samples.npy (uint8 [N, T, H, W, 3], images [N, H, W, 3]) and one GIF / PNG per sample.
+    size / wrap: see the module docstring."""
+    ring = check_request(load_opt(exp_dir), size, wrap)   # before the device is asked for
+    flagged = size is not None or wrap is not None
     device = gpu_device()
     opt, netG = load_generator(exp_dir, device)
     bs = int(batch_size or opt.batch_size)
@@ -51,26 +117,53 @@ def generate(exp_dir, num_samples, batch_size=None, seed=0, out=None):
         level0 = hp_utils.images.level_shape_2d(0, opt)
         fps = 1
     baseline = getattr(opt, 'program', None) == 'train_video_baselines'
-    size = [bs, 3 if baseline else opt.latent_dim, *level0]
+    sizes = None
+    if flagged:
+        trained = [netG._level_size(l) for l in range(len(netG.body) + 1)]
+        sizes = level_sizes(trained, size if size is not None else trained[-1])
+        if sizes is not trained:
+            netG.level_sizes = sizes
+        level0 = sizes[0]
+        if ring is not None:
+            set_ring(netG, ring)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    size0 = [bs, 3 if baseline else opt.latent_dim, *level0]
     samples = []
     with torch.no_grad(), ops.noise_stream(device):
+        if flagged:
+            t0.record()
         for _ in range(math.ceil(num_samples / bs)):
-            noise_init = hp_utils.generate_noise(size=size, device=device)
+            noise_init = hp_utils.generate_noise(size=size0, device=device)
             if baseline:
                 fake = netG(noise_init, opt.Noise_Amps, mode='rand')
             else:
                 fake, _ = netG(noise_init, opt.Noise_Amps, noise_init=noise_init, mode="rand")
             samples.append(ops.video_to_u8(fake).cpu().numpy())
+        if flagged:
+            t1.record()
+            t1.synchronize()
     arr = np.concatenate(samples, 0)[:num_samples]
-    out = out or os.path.join(exp_dir, 'eval', 'samples')
+    if out is None:
+        name = 'samples'
+        if flagged:
+            name += '_' + 'x'.join(str(int(s)) for s in sizes[-1])
+            if wrap is not None:
+                name += '_wrap' + wrap
+        out = os.path.join(exp_dir, 'eval', name)
     write_samples(out, arr, fps)
+    if flagged:
+        made = math.ceil(num_samples / bs) * bs
+        with open(os.path.join(out, 'generate.json'), 'w') as f:
+            json.dump({"size": [int(s) for s in sizes[-1]], "level_sizes": [[int(s) for s in q] for q in sizes],
+                       "wrap": wrap, "seed": int(seed), "num_samples": int(num_samples), "batch_size": bs,
+                       "seconds_per_sample": t0.elapsed_time(t1) / 1000.0 / made}, f, indent=1, sort_keys=True)
     print("wrote {} samples {} to {}".format(len(arr), tuple(arr.shape[1:]), out))
     return arr
 
 
 def main(argv=None):
     a = generate_parser().parse_args(argv)
-    generate(a.exp_dir, a.num_samples, a.batch_size, a.seed, a.out)
+    generate(a.exp_dir, a.num_samples, a.batch_size, a.seed, a.out, a.size, a.wrap)
     return 0
 
 

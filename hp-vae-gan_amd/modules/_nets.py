@@ -64,10 +64,31 @@ class Conv(nn.Module):
 
     # multi-GPU: slab.Halo when this layer's level is cut into row slabs over neighbouring ranks (multigpu.py sets it)
     halo = None
+    # sampling on rings (generate --wrap sets it): one 0 / 1 flag per spatial axis; a flagged axis is convolved circularly
+    ring = None
+
+    def _forward_ring(self, x, act):
+        """The circular convolution on the axes flagged in self.ring: the ring axes padded circularly by ker_size // 2
+        (ops.ring_pad), the unchanged 'same' conv - whose zero padding now falls outside real data on those axes - and the ring
+        axes cropped back (ops.ring_crop), so every kept output read only real values.  No backward (ops.ring_pad refuses)."""
+        if len(self.ring) != self.dims or any(f not in (0, 1) for f in self.ring):
+            raise ValueError("Conv.ring must hold one 0 / 1 flag per spatial axis (%d), got %r" % (self.dims, self.ring))
+        if self.halo is not None:
+            raise NotImplementedError("rings are not implemented on row slabs")
+        if self.padding != max(self.ker_size // 2, 1):
+            raise NotImplementedError("a ring conv keeps the size: padding must be ker_size // 2 (got ker_size=%d, padding=%d)"
+                                      % (self.ker_size, self.padding))
+        pad = tuple(int(f) * (self.ker_size // 2) for f in self.ring)
+        w = self.weight if self.ker_size != 1 else embed_center(self.weight, self.dims)
+        if not any(pad):
+            return ops.Conv.apply(x, w, self.bias, act)
+        return ops.ring_crop(ops.Conv.apply(ops.ring_pad(x, pad), w, self.bias, act), pad)
 
     def forward(self, x, act=False, in_act=False, in_bits=None):
         """in_act: x is the activated output of a spectral-norm block that left its LeakyReLU backward to this conv
         (ops.Conv: the mask rides in this layer's backward-data epilogue); in_bits: its 1-bit form from the producer."""
+        if self.ring is not None and any(self.ring):
+            return self._forward_ring(x, act)
         if self.ker_size in WIDE_KER_SIZES:
             if self.halo is not None:
                 raise NotImplementedError("row slabs exchange one boundary row per conv: ker_size=%d is not implemented on them" % self.ker_size)
@@ -433,7 +454,15 @@ class GeneratorHPVAEGAN(nn.Module):
         generated, fake = ops.SplitBatch.apply(x, B)
         return generated, fake, vae_out.detach()[:B], (mu, logvar)
 
+    # sampling at another size (generate --size sets it): the shape of every level, 0 .. len(body); None = the trained pyramid
+    level_sizes = None
+    # sampling on rings (generate --wrap sets it, with Conv.ring on the decoder's and the body's convs): one 0 / 1 flag per spatial
+    # axis; the resize between levels then interpolates across the seam of a flagged axis (ops.upsample_ring)
+    ring = None
+
     def _level_size(self, index):
+        if self.level_sizes is not None:
+            return list(self.level_sizes[index])
         if self.dims == 3:
             return hp_utils.images.level_shape_3d(index, self.opt)
         return hp_utils.images.level_shape_2d(index, self.opt)
@@ -452,7 +481,13 @@ class GeneratorHPVAEGAN(nn.Module):
                 x_prev_out.detach_()
             size = self._level_size(idx + 1)
             inject = self._inject_noise(idx, mode)
-            if inject and self.noise_source is None:
+            if self.ring is not None and any(self.ring):
+                # the resize across the seam, then the level noise by the existing kernel (a resize to the same size is the
+                # identity, so up_noisy = up + amp * noise); i.i.d. noise is periodic as it is
+                up = up_noisy = ops.upsample_ring(x_prev_out, tuple(size), self.ring)
+                if inject:
+                    _, up_noisy = ops.UpsampleAC.apply(up, tuple(size), self._noise_like(up), float(noise_amp[idx + 1]))
+            elif inject and self.noise_source is None:
                 up, up_noisy = ops.UpsampleACNoise.apply(x_prev_out, tuple(size), float(noise_amp[idx + 1]), 0)   # noise made in the kernel
             elif inject:
                 ref = x_prev_out.new_empty((x_prev_out.shape[0], x_prev_out.shape[1], *size))

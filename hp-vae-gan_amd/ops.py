@@ -977,6 +977,65 @@ class UpsampleAC(Function):
         return dx, None, None, None
 
 
+# ------------------------------------------------------------------------------------------ rings (generate --wrap)
+def _ring_input(x, what):
+    """Rings are a sampling feature: no backward is built, so an input that would need one is refused."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("%s has no backward (rings are a sampling feature): run it under torch.no_grad()" % what)
+    if x.dtype != torch.float32:
+        raise RuntimeError("%s takes fp32, got %s" % (what, x.dtype))
+    return _c(x)
+
+
+def _per_axis(v, x, name, what):
+    """One non-negative int per spatial axis of x as a triple (t, h, w); an image gets t = 0."""
+    v = tuple(int(e) for e in v)
+    if len(v) != x.dim() - 2 or min(v) < 0:
+        raise ValueError("%s: %s must hold one value >= 0 per spatial axis of %s, got %r" % (what, name, tuple(x.shape), v))
+    return v if x.dim() == 5 else (0,) + v
+
+
+def ring_pad(x, pad):
+    """[B, C, (T,) H, W] -> every spatial axis a grown by 2 * pad[a], filled circularly: out[.., i, ..] = x[.., (i - pad[a]) mod
+    side, ..] (hpvg_ring_pad_f32).  pad[a] = 0 leaves the axis alone; a pad may exceed the side."""
+    x = _ring_input(x, "ring_pad")
+    B, C, T, H, W = geom(x)
+    p = _per_axis(pad, x, "pad", "ring_pad")
+    big = (T + 2 * p[0], H + 2 * p[1], W + 2 * p[2])
+    out = x.new_empty((B, C) + (big if x.dim() == 5 else big[1:]))
+    call("hpvg_ring_pad_f32", ptr(x), B * C, T, H, W, (ctypes.c_int * 3)(*p), ptr(out), stream())
+    return out
+
+
+def ring_crop(y, pad):
+    """The inverse geometry of ring_pad: pad[a] voxels dropped from both ends of every spatial axis (hpvg_box_copy_f32)."""
+    y = _ring_input(y, "ring_crop")
+    B, C, T, H, W = geom(y)
+    p = _per_axis(pad, y, "pad", "ring_crop")
+    small = (T - 2 * p[0], H - 2 * p[1], W - 2 * p[2])
+    if min(small) < 1:
+        raise RuntimeError("ring_crop of %r leaves nothing of %s" % (p, tuple(y.shape)))
+    out = y.new_empty((B, C) + (small if y.dim() == 5 else small[1:]))
+    call("hpvg_box_copy_f32", ptr(y), ptr(out), B * C, T, H, W, *small, -p[0], -p[1], -p[2], stream())
+    return out
+
+
+def upsample_ring(x, size, wrap):
+    """Linear resize of [B, C, (T,) H, W] to `size` whose axes flagged in `wrap` (one 0 / 1 per spatial axis) are rings: source
+    coordinate o S / O, the last sample interpolating towards the first; the other axes as UpsampleAC
+    (hpvg_upsample_linear_ring_f32)."""
+    x = _ring_input(x, "upsample_ring")
+    B, C, Ti, Hi, Wi = geom(x)
+    size = tuple(int(s) for s in size)
+    if len(size) != x.dim() - 2:
+        raise ValueError("upsample_ring: size %r does not fit %s" % (size, tuple(x.shape)))
+    w = _per_axis(wrap, x, "wrap", "upsample_ring")
+    To, Ho, Wo = size if x.dim() == 5 else (1,) + size
+    y = torch.empty((B, C) + size, dtype=torch.float32, device=x.device)
+    call("hpvg_upsample_linear_ring_f32", ptr(x), B * C, Ti, Hi, Wi, ptr(y), To, Ho, Wo, (ctypes.c_int * 3)(*w), stream())
+    return y
+
+
 # ------------------------------------------------------------------------------------------ N(0,1) noise (Philox kernel)
 class _RngState:
     """Counter-based noise stream of one device: (seed, iteration counter ON THE DEVICE, call index inside the iteration).

@@ -294,6 +294,25 @@ int hpvg_upsample_linear_ac_noise_f32(const float* x, float* y, float* yn, float
 int hpvg_upsample_linear_ac_bwd_f32(const float* dy, const float* dy2, float* dx, long BC, int Ti, int Hi, int Wi, int To, int Ho,
                                     int Wo, void* stream);
 
+/* ---- rings on the sampling path (generate --wrap): the generator's volumes with some axes closed into rings.  No backward is
+ * built: rings are a sampling feature.
+ * Circular pad.  x: [NC][T][H][W], out: [NC][T + 2 pt][H + 2 ph][W + 2 pw] with pad = (pt, ph, pw) (a host array; 2-D: T = 1,
+ * pt = 0):  out[c, t, y, x] = x[c, mod(t - pt, T), mod(y - ph, H), mod(x - pw, W)]  with the non-negative modulus.  pad[a] = 0
+ * leaves that axis alone; a pad may exceed its side (a side of 1 with a pad of 3 repeats the one slice 7 times).  An exact copy:
+ * one launch, no workspace, no atomics, no host synchronisation.  Both pointers may sit at any 4-byte offset (the 16-byte stores
+ * of the body start at out's first aligned element; the elements before and behind it are stored one by one).
+ * HPVG_ERR_ARG: a NULL pointer, a side < 1, a pad < 0, out overlapping x; HPVG_ERR_UNSUPPORTED: out holds 2^31 elements or more. */
+int hpvg_ring_pad_f32(const float* x, long NC, int T, int H, int W, const int* pad, float* out, void* stream);
+/* Separable linear resize x [NC][Ts][Hs][Ws] -> out [NC][To][Ho][Wo] with wrap = (wt, wh, ww) flags (a host array, each 0 or 1,
+ * anything else HPVG_ERR_ARG; NULL = all zero).  An axis without its flag follows the rule of hpvg_upsample_linear_ac_f32 exactly.
+ * A ring axis of S source and O output positions has the source coordinate o S / O:  i0 = (o S) / O,  f = ((o S) % O) / O (one
+ * fp32 division of the two integers),  i1 = (i0 + 1) % S,  weights 1 - f and f - the last sample interpolates towards the first.
+ * S == O is the identity along that axis.  All flags zero is hpvg_upsample_linear_ac_f32 without noise, bit for bit (the same
+ * kernel).  With O = k S on a ring axis the weights depend on o mod k only, so rolling x by r along it rolls out by k r, bit for
+ * bit.  Level noise is added afterwards (hpvg_upsample_linear_ac_f32 at equal sizes is y = x, yn = x + amp * noise). */
+int hpvg_upsample_linear_ring_f32(const float* x, long NC, int Ts, int Hs, int Ws, float* out, int To, int Ho, int Wo, const int* wrap,
+                                  void* stream);
+
 /* ---- data front-end (the step before the path): frames [N][H][W][3] uint8 RGB -> the stage's clip tensor
  * [3][count][h][w] fp32: cv2.resize(INTER_LINEAR) geometry per frame (datasets/generate_frames.py:44-46), temporal window
  * frame[first + k*step] (datasets/video.py:56-57), /255, K.hflip, K.normalize(0.5, 0.5), permute C,T,H,W (video.py:58-82).

@@ -73,6 +73,9 @@
 //
 // The pyramid's resize (generate_patchnn --antialias / --t-ratio, evaluate --scales): volresize.inl, included at the end, an exact
 // antialiased resize of a uint8 volume in integer arithmetic, one gather kernel of its own.
+//
+// The feathered composite (generate / generate_patchnn --guide-mask): maskblend.inl, included at the end, a box dilation and a
+// box count of a hole mask as 1-D passes, and the exact integer blend of two volumes under the resulting weights.
 #include <limits.h>
 
 #include <type_traits>
@@ -1207,3 +1210,6 @@ int hpvg_nnf_chunks_i32(const int* nn, const int* d2, int max_d2, const int* qgr
 
 // generate_patchnn --antialias / --t-ratio, evaluate --scales: the exact antialiased volume resize (its own gather kernel)
 #include "volresize.inl"
+
+// generate --guide-mask, generate_patchnn --guide-mask: the dilate-and-feather composite of two byte volumes (1-D passes)
+#include "maskblend.inl"

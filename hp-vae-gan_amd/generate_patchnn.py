@@ -6,7 +6,9 @@ above the coarsest search by a deterministic PatchMatch (linear in the patch cou
 (letters of t, h, w) the samples are rings along those axes: `--wrap t` makes clips whose last frame continues into the first
 (seamless loops), `--wrap hw` tileable textures.  With `--antialias` every resize of the run is the exact antialiased integer
 resize (ops.volume_resize_u8: the coarse levels are low-passed, not subsampled), and with `--t-ratio R` the pyramid also
-scales T (a spatio-temporal pyramid)."""
+scales T (a spatio-temporal pyramid).  With `--guide PATH --guide-level N` every sample starts from the given volume at pyramid
+level N instead of from noise (structural analogies, sketch-to-video, editing), and with `--guide-mask hole.npy` it is kept only
+inside the feathered hole (ops.mask_blend)."""
 import argparse
 import json
 import math
@@ -19,8 +21,9 @@ import torch
 from . import ops
 from . import utils as hp_utils
 from . import datasets
-from .programs import (default_patch, gpu_device, load_opt, load_u8_frames, parse_wrap_axes, patchnn_wrap_pad, real_volume,
-                       wrap_triple as _wrap3, write_samples)
+from .programs import (add_guide_flags, check_guide_flags, default_patch, gpu_device, load_guide_frames, load_opt, load_u8_frames,
+                       mask_forms, parse_wrap_axes, patchnn_wrap_pad, pick_mask, real_volume,
+                       refuse_trivial_mask as _refuse_trivial_mask, wrap_triple as _wrap3, write_samples)
 
 
 # The training-free counterpart of the trained generator: GPNN (Granot et al., "Drop the GAN", CVPR 2022) and its video form
@@ -82,6 +85,9 @@ def generate_patchnn_parser():
                    'Not for an image, and not with --mask (the mask resize keeps T)')
     p.add_argument('--min-frames', type=int, default=None, metavar='F', help='no level of a --t-ratio pyramid has fewer frames '
                    '(default: patch T + 1; at least patch T); only with --t-ratio below 1')
+    add_guide_flags(p)
+    p.add_argument('--guide-noise', type=float, default=None, metavar='S', help='standard deviation, in units of 255, of the noise '
+                   'added to the guide at --guide-level (default 0; --noise is not used in a guided run); only with --guide')
     return p
 
 
@@ -248,9 +254,25 @@ def patchnn_refine(query, keys, values, patch, alpha_abs, return_score=False, se
     return out
 
 
+def patchnn_sample_sizes(sizes, real_shape, size, patch, ratio=0.75, t_ratio=1.0, min_frames=None, start=0):
+    """The (T, H, W) of every level of a sample of (T, H, W) = size beside the real pyramid `sizes` of a volume of real_shape:
+    `sizes` itself for size None or the real shape, else per level the sample's sides scaled as patchnn_pyramid_sizes scales the
+    real ones.  Refuses (ValueError) a sample whose coarsest used level `start` is smaller than the patch.  Host only."""
+    L = len(sizes)
+    if size is None or tuple(size) == tuple(real_shape):
+        return sizes
+    St, Sh, Sw = (int(e) for e in size)
+    qsizes = [(patchnn_level_frames(St, L - 1 - l, t_ratio, min_frames, patch[0]),
+               int(math.floor(Sh * ratio ** (L - 1 - l) + 0.5)), int(math.floor(Sw * ratio ** (L - 1 - l) + 0.5)))
+              for l in range(L)]
+    if any(s < p for s, p in zip(qsizes[start], patch)):
+        raise ValueError("patchnn_synthesize: the sample's coarsest level %s is smaller than the patch %s" % (qsizes[start], tuple(patch)))
+    return qsizes
+
+
 def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, iters=10, noise=0.75, alpha=0.005, seed=0, index=0,
                        pyramid=None, search='exact', pm_iters=PM_ITERS, pm_from_level=PM_FROM_LEVEL, wrap=None, antialias=False,
-                       t_ratio=1.0, min_frames=None):
+                       t_ratio=1.0, min_frames=None, guide=None, guide_level=None, guide_noise=0.0):
     """One sample of the uint8 device volume `real` ([T,H,W,3]; images [H,W,3]) -> (sample, mean final score).  size: the
     sample's (T, H, W) (default real's).  The coarsest guess is real level 0 (resized to the sample's coarsest size) plus
     noise * 255 * N(0, 1) drawn under torch.manual_seed(seed + index); level 0 runs `iters` steps with keys = values = real
@@ -266,7 +288,13 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
     (not periodic): the steps that follow re-vote every voxel.
     antialias: every resize (real levels, blurred keys, coarsest guess, the guess between levels) is ops.volume_resize_u8.
     t_ratio / min_frames: the pyramid scales T as well (patchnn_pyramid_sizes); a sample of another size scales its own T by the
-    same rule.  A given `pyramid` must have been made with the same three settings."""
+    same rule.  A given `pyramid` must have been made with the same three settings.
+    guide (a uint8 device volume [T,H,W,3]; images [H,W,3]) with guide_level = N in 0 .. L - 1: the sample starts from the guide
+    instead of from noise.  The guide's (T, H, W) is the sample's size (a `size` that differs is refused); the levels below N are
+    skipped; the guess at level N is the guide resized to the sample's level-N size plus guide_noise * 255 * N(0, 1), drawn under
+    seed + index as the coarsest noise is (`noise` is not used); level N is this run's coarsest level - `iters` steps with
+    keys = values = real level N, always exact - and PatchMatch starts at max(pm_from_level, N + 1); the finer levels run as
+    they always do.  guide None: the function it always was."""
     wrap = _wrap3(wrap)
     image = real.dim() == 3
     vol = real[None] if image else real
@@ -276,18 +304,28 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
         pyramid = (sizes,) + patchnn_real_levels(vol, sizes, antialias)
     sizes, levels, keys = pyramid
     L = len(sizes)
-    if size is None or tuple(size) == tuple(vol.shape[:3]):
-        qsizes = sizes
-    else:
-        St, Sh, Sw = (int(e) for e in size)
-        qsizes = [(patchnn_level_frames(St, L - 1 - l, t_ratio, min_frames, patch[0]),
-                   int(math.floor(Sh * ratio ** (L - 1 - l) + 0.5)), int(math.floor(Sw * ratio ** (L - 1 - l) + 0.5)))
-                  for l in range(L)]
-        if any(s < p for s, p in zip(qsizes[0], patch)):
-            raise ValueError("patchnn_synthesize: the sample's coarsest level %s is smaller than the patch %s" % (qsizes[0], patch))
+    start = 0
+    if guide is not None:
+        gvol = guide[None] if guide.dim() == 3 else guide
+        if guide.dim() != real.dim() or gvol.dtype != torch.uint8 or gvol.dim() != 4 or gvol.shape[-1] != 3 or gvol.device != vol.device:
+            raise ValueError("patchnn_synthesize: the guide must be uint8 %s on %s like the real volume, got %s %s on %s"
+                             % ("[H,W,3]" if image else "[T,H,W,3]", vol.device, guide.dtype, tuple(guide.shape), guide.device))
+        if size is not None and tuple(int(e) for e in size) != tuple(gvol.shape[:3]):
+            raise ValueError("patchnn_synthesize: the guide's size %s is the sample's: size %s differs"
+                             % (tuple(gvol.shape[:3]), tuple(size)))
+        if guide_level is None or isinstance(guide_level, bool) or not 0 <= int(guide_level) < L:
+            raise ValueError("patchnn_synthesize: guide_level must lie in 0 .. %d (the pyramid has %d levels), got %r"
+                             % (L - 1, L, guide_level))
+        size, start = tuple(int(e) for e in gvol.shape[:3]), int(guide_level)
+    elif guide_level is not None or guide_noise:
+        raise ValueError("patchnn_synthesize: guide_level and guide_noise need a guide")
+    qsizes = patchnn_sample_sizes(sizes, vol.shape[:3], size, patch, ratio, t_ratio, min_frames, start)
     alpha_abs = float(alpha) * 3 * patch[0] * patch[1] * patch[2] * 255 * 255
     iters = max(int(iters), 1)
-    q = _resize_u8(levels[0], qsizes[0], antialias)
+    if guide is None:
+        q = _resize_u8(levels[0], qsizes[0], antialias)
+    else:
+        q, noise, pm_from_level = _resize_u8(gvol, qsizes[start], antialias), guide_noise, max(int(pm_from_level), start + 1)
     if noise:
         torch.manual_seed(int(seed) + int(index))
         with ops.noise_stream(q.device):
@@ -295,8 +333,8 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
         q = torch.round(q.to(torch.float32) + (float(noise) * 255.0) * z).clamp_(0, 255).to(torch.uint8)
     state = patchnn_search_state(seed, index) if search == "patchmatch" else None
     score = None
-    for l in range(L):
-        if l > 0:
+    for l in range(start, L):
+        if l > start:
             q = _resize_u8(q, qsizes[l], antialias)
             if state is not None:
                 qf, qt = (patchnn_wrap_grid(qsizes[k], patch, wrap) for k in (l - 1, l))
@@ -306,7 +344,7 @@ def patchnn_synthesize(real, size=None, patch=None, ratio=0.75, min_size=16, ite
                 if state["rev"] is not None:
                     state["rev"] = patchnn_field_resize(state["rev"], rf, qf, rt, qt)
         for it in range(iters):
-            k = keys[l] if (l > 0 and it == 0) else levels[l]
+            k = keys[l] if (l > start and it == 0) else levels[l]
             q, score = patchnn_refine(q, k, levels[l], patch, alpha_abs, return_score=True, search=search, pm_iters=pm_iters,
                                       pm_from_level=pm_from_level, level=l, state=state, wrap=wrap)
     return (q[0] if image else q), score
@@ -439,42 +477,37 @@ def patchnn_inpaint(real, mask, patch=None, ratio=0.75, min_size=16, iters=10, n
     return results[-1], score
 
 
-def mask_forms(path):
-    """Every [T,H,W] bool reading of a mask input, as host arrays: a .npy [T,H,W] or [H,W] (bool or uint8) as it is, and an
-    input with a last axis of 3 ([...,3] .npy, an image file, a frame directory) with any nonzero channel as hole.  An array
-    [H,W,3] has both readings; the real volume's shape decides between them (pick_mask).  Another dtype or rank ends the
-    program."""
-    ra = datasets.load_frames(path)
-    if ra.dtype not in (np.bool_, np.uint8):
-        raise SystemExit("generate_patchnn: --mask must be bool or uint8, got {} {}".format(ra.dtype, ra.shape))
-    forms = ([ra] if ra.ndim in (2, 3) else []) + ([ra.any(-1)] if ra.ndim in (3, 4) and ra.shape[-1] == 3 else [])
-    if not forms:
-        raise SystemExit("generate_patchnn: --mask must be [T,H,W], [H,W] or either with a last axis of 3, got {}".format(ra.shape))
-    return [np.ascontiguousarray((m[None] if m.ndim == 2 else m) != 0) for m in forms]
-
-
-def pick_mask(forms, shape):
-    """The reading of mask_forms with the real volume's (T, H, W) = shape; none ends the program."""
-    for m in forms:
-        if tuple(m.shape) == tuple(shape):
-            return m
-    raise SystemExit("generate_patchnn: --mask must have the real volume's shape {}, got {}".format(
-        tuple(shape), " or ".join(str(tuple(m.shape)) for m in forms)))
-
-
 def load_mask(path, shape):
-    """The hole mask at `path` of a volume of (T, H, W) = shape as a host bool array [T,H,W] (mask_forms, pick_mask)."""
+    """The hole mask at `path` of a volume of (T, H, W) = shape as a host bool array [T,H,W] (programs.mask_forms, pick_mask)."""
     return pick_mask(mask_forms(path), shape)
 
 
-def _refuse_trivial_mask(forms):
-    if all(not m.any() for m in forms) or all(m.all() for m in forms):
-        raise SystemExit("generate_patchnn: --mask is {}".format("empty" if not forms[0].any() else "all hole"))
+def _host_real_shape(exp_dir, video_path, image_path):
+    """((T, H, W), image) of the real volume a run will load, from the host alone: the input's frames as they are, or for an
+    experiment directory what programs.real_volume makes of the run's input."""
+    if exp_dir is None:
+        ra = datasets.load_frames(video_path or image_path)
+        image = image_path is not None
+        if ra.ndim not in (3, 4) or ra.shape[-1] != 3:
+            raise SystemExit("generate_patchnn: the input must be uint8 [N,H,W,3] or [H,W,3], got {} {}".format(ra.dtype, ra.shape))
+        if image or ra.ndim == 3:
+            return (1,) + tuple(ra.shape[-3:-1]), image
+        return tuple(ra.shape[:3]), False
+    opt = load_opt(exp_dir)
+    h, w = datasets._stage_size(opt, opt.stop_scale)
+    if opt.dims != 3:
+        return (1, h, w), True
+    frames = datasets.load_frames(opt.video_path)
+    start = getattr(opt, "start_frame", 0)
+    n = len(frames[start:start + opt.max_frames] if getattr(opt, "max_frames", None) else frames[start:])
+    every = opt.sampling_rates[hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[2]]
+    return (len(range(0, n, every)), h, w), False
 
 
 def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, num_samples=8, seed=0, patch=None, ratio=0.75,
                      min_size=16, iters=10, alpha=0.005, noise=0.75, size=None, save_levels=False, mask=None, search='exact',
-                     pm_iters=None, pm_from_level=None, wrap=None, antialias=False, t_ratio=1.0, min_frames=None):
+                     pm_iters=None, pm_from_level=None, wrap=None, antialias=False, t_ratio=1.0, min_frames=None, guide=None,
+                     guide_level=None, guide_mask=None, guide_feather=None, guide_noise=None):
     """Write samples.npy (uint8 [N,T,H,W,3], images [N,H,W,3]: what `evaluate --samples` reads), one GIF / PNG per sample and
     patchnn.json (the settings, the level sizes, seconds per sample from HIP events, the mean final score per sample).  mask: the
     path of a hole mask of the real volume; the samples are then completions of the hole (patchnn_inpaint), land in
@@ -485,7 +518,13 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
     (letters of t, h, w): the samples are rings along those axes (patchnn_synthesize's wrap); patchnn.json then records it.  Not
     with a mask, and no t for an image.  antialias: every resize is ops.volume_resize_u8.  t_ratio < 1 (with min_frames): the
     pyramid scales T too; not for an image and not with a mask.  patchnn.json records antialias when it is set, and t_ratio and
-    min_frames (the value in force) when t_ratio is below 1."""
+    min_frames (the value in force) when t_ratio is below 1.
+    guide (a path: .npy, a frame directory or an image file) with guide_level = N: every sample starts from the guide at level N
+    (patchnn_synthesize's guide) plus guide_noise (default 0) instead of from the coarsest level plus `noise`; the guide's
+    (T, H, W) is the sample's size.  guide_mask (the forms of `mask`, the sample's shape) with guide_feather (default 1 5 5, images
+    0 5 5): every finished sample becomes ops.mask_blend(sample, guide, mask, feather) - the sample inside the hole, the guide
+    away from it.  Not with `mask`.  The samples land in <exp-dir>/eval/samples_patchnn_guide<N> by default and patchnn.json also
+    records guide, guide_level, guide_noise, guide_mask and guide_feather."""
     t_ratio = 1.0 if t_ratio is None else float(t_ratio)
     if not 0.0 < t_ratio <= 1.0:
         raise SystemExit("generate_patchnn: --t-ratio must lie in (0, 1], got {}".format(t_ratio))
@@ -531,6 +570,38 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         raise SystemExit("generate_patchnn: give exactly one of --exp-dir, --video-path and --image-path")
     if exp_dir is None and out is None:
         raise SystemExit("generate_patchnn: --video-path / --image-path need --out")
+    gframes = gmask = gfeather = None
+    if guide is None and guide_noise is not None:
+        raise SystemExit("generate_patchnn: --guide-noise needs --guide")
+    if guide is not None or guide_level is not None or guide_mask is not None or guide_feather is not None:
+        # everything the guide's flags and files decide, before the device is touched
+        host = _host_real_shape(exp_dir, video_path, image_path)
+        gfeather, gforms = check_guide_flags("generate_patchnn", guide, guide_level, guide_mask, guide_feather, host[1])
+        if mask is not None:
+            raise SystemExit("generate_patchnn: --guide starts every voxel from the guide, --mask fills a hole of the real volume: "
+                             "they do not combine (use --guide-mask to keep the guide outside a hole)")
+        guide_noise = 0.0 if guide_noise is None else float(guide_noise)
+        if not guide_noise >= 0 or math.isinf(guide_noise):
+            raise SystemExit("generate_patchnn: --guide-noise must be finite and >= 0, got {}".format(guide_noise))
+        gframes = load_guide_frames("generate_patchnn", guide)
+        if host[1] and gframes.shape[0] != 1:
+            raise SystemExit("generate_patchnn: the guide of an image run is one image, got {} frames".format(gframes.shape[0]))
+        if size is not None and tuple(size) != tuple(gframes.shape[:3]):
+            raise SystemExit("generate_patchnn: the guide's size {} is the samples': --size {} differs".format(
+                tuple(gframes.shape[:3]), tuple(size)))
+        size = tuple(int(e) for e in gframes.shape[:3])
+        gpatch = tuple(patch) if patch else default_patch(not host[1])
+        try:
+            gsizes = patchnn_pyramid_sizes(host[0], ratio, min_size, gpatch, t_ratio, min_frames)
+            if not 0 <= int(guide_level) < len(gsizes):
+                raise ValueError("--guide-level must lie in 0 .. {} (the pyramid of the real volume {} has {} levels), got {}".format(
+                    len(gsizes) - 1, tuple(host[0]), len(gsizes), guide_level))
+            patchnn_sample_sizes(gsizes, host[0], size, gpatch, ratio, t_ratio, min_frames, int(guide_level))
+        except ValueError as e:
+            raise SystemExit("generate_patchnn: {}".format(e))
+        if gforms is not None:
+            gmask = pick_mask(gforms, size, "generate_patchnn: --guide-mask", "the guide's")
+            _refuse_trivial_mask([gmask], "generate_patchnn: --guide-mask")
     hole = forms = None
     if mask is not None:
         # what the mask alone decides, before the device is touched.  The mask has the real volume's shape (checked below, once
@@ -550,7 +621,8 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         real = real_volume(opt, None, device)
         if opt.dims == 3:
             fps = hp_utils.get_fps_td_by_index(opt.stop_scale, opt)[0]
-        out = out or os.path.join(exp_dir, 'eval', 'samples_patchinpaint' if mask is not None else 'samples_patchnn')
+        out = out or os.path.join(exp_dir, 'eval', 'samples_patchinpaint' if mask is not None else
+                                  'samples_patchnn_guide{}'.format(int(guide_level)) if guide is not None else 'samples_patchnn')
     else:
         real = load_u8_frames(video_path or image_path, device, image_path is not None,
                               "generate_patchnn: the input must be uint8 [N,H,W,3] or [H,W,3]", ranks=(3, 4))
@@ -579,6 +651,12 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
             pyramid = pyramid + (patchnn_inpaint_plan(hole, sizes, patch),)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
+    gkw = {}
+    if guide is not None:
+        gdev = torch.from_numpy(gframes).to(device)
+        gkw = {"guide": gdev, "guide_level": int(guide_level), "guide_noise": guide_noise}
+        if gmask is not None:
+            gmask = torch.from_numpy(gmask).to(device)
     os.makedirs(out, exist_ok=True)
     if save_levels:
         np.savez(os.path.join(out, 'levels.npz'), **{"level_%d" % l: v.cpu().numpy() for l, v in enumerate(pyramid[1])},
@@ -598,7 +676,9 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
                     pm["antialias"] = True
                 if t_ratio != 1.0:
                     pm.update({"t_ratio": t_ratio, "min_frames": min_frames})
-                smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid, **pm)
+                smp, score = patchnn_synthesize(vol, size, patch, ratio, min_size, iters, noise, alpha, seed, i, pyramid, **pm, **gkw)
+                if gmask is not None:
+                    smp = ops.mask_blend(smp, gdev, gmask, gfeather)
         except ValueError as e:
             raise SystemExit("generate_patchnn: {}".format(e))
         e1.record()
@@ -626,6 +706,10 @@ def generate_patchnn(exp_dir=None, video_path=None, image_path=None, out=None, n
         info["antialias"] = True
     if t_ratio != 1.0:
         info.update({"t_ratio": t_ratio, "min_frames": patch[0] + 1 if min_frames is None else int(min_frames)})
+    if guide is not None:
+        info.update({"guide": os.path.abspath(guide), "guide_level": int(guide_level), "guide_noise": guide_noise,
+                     "guide_mask": os.path.abspath(guide_mask) if guide_mask is not None else None,
+                     "guide_feather": list(gfeather) if gfeather is not None else None})
     with open(os.path.join(out, 'patchnn.json'), 'w') as f:
         json.dump(info, f, indent=1, sort_keys=True)
     print("wrote {} patch nearest-neighbour samples {} ({} levels, {:.3f} s per sample) to {}".format(
@@ -637,7 +721,7 @@ def main(argv=None):
     a = generate_patchnn_parser().parse_args(argv)
     generate_patchnn(a.exp_dir, a.video_path, a.image_path, a.out, a.num_samples, a.seed, a.patch, a.ratio, a.min_size, a.iters,
                      a.alpha, a.noise, a.size, a.save_levels, a.mask, a.search, a.pm_iters, a.pm_from_level, a.wrap, a.antialias, a.t_ratio,
-                     a.min_frames)
+                     a.min_frames, a.guide, a.guide_level, a.guide_mask, a.guide_feather, a.guide_noise)
     return 0
 
 

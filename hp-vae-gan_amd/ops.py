@@ -1801,6 +1801,41 @@ def volume_resize_u8(vol_u8, size):
     return out[0] if image else out
 
 
+MASK_BLEND_MAX_RADIUS = 64   # hpvg_mask_blend_u8 takes radii in [0, 64]
+
+
+def mask_blend(a_u8, b_u8, mask, radius):
+    """The dilate-and-feather composite of two uint8 device volumes [T,H,W,3] (hpvg_mask_blend_u8): `a` inside the hole `mask`
+    ([T,H,W], uint8 or bool, nonzero = hole), `b` farther than twice the radius from it, the exact integer blend
+    (2 (c a + (n - c) b) + n) / (2 n) in between, c the dilated hole's voxels in the clipped box of radius = (rt, rh, rw) around
+    the voxel and n the box's (include/hpvg.h).  Radius (0, 0, 0) is the hard composite.  Images [H,W,3] with a mask [H,W] are
+    the volume with T = 1 and take a radius of 2 entries (or 3 with rt = 0).  Returns a new uint8 tensor shaped as `a`."""
+    (a, b), image = _patch_volumes("mask_blend", (("a", a_u8), ("b", b_u8)))
+    if a.shape != b.shape:
+        raise RuntimeError("mask_blend: a %s and b %s must have one shape" % (tuple(a_u8.shape), tuple(b_u8.shape)))
+    m = mask
+    if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or tuple(m.shape) != tuple(a_u8.shape[:-1]) or \
+            m.device != a.device:
+        raise RuntimeError("mask_blend: mask must be uint8 or bool %s on %s, got %s %s on %s"
+                           % (tuple(a_u8.shape[:-1]), a.device, getattr(m, "dtype", type(m)), tuple(getattr(m, "shape", ())),
+                              getattr(m, "device", None)))
+    m = _c(m.to(torch.uint8))
+    rad = tuple(int(e) for e in radius)
+    if len(rad) not in ((2, 3) if image else (3,)) or (image and len(rad) == 3 and rad[0] != 0):
+        raise RuntimeError("mask_blend: radius must be (rt, rh, rw)%s, got %s" % (" or (rh, rw): an image has rt = 0" if image else "", rad))
+    if image and len(rad) == 2:
+        rad = (0,) + rad
+    if min(rad) < 0 or max(rad) > MASK_BLEND_MAX_RADIUS:
+        raise RuntimeError("mask_blend: every radius must lie in [0, %d], got %s" % (MASK_BLEND_MAX_RADIUS, rad))
+    ptr(a)  # refuses a host tensor by name
+    T, H, W = (int(e) for e in a.shape[:3])
+    rp = _triple(rad, "radius", "mask_blend")
+    ws = _scratch(call("hpvg_mask_blend_ws_bytes", T, H, W, rp), a.device)
+    out = torch.empty_like(a)
+    call("hpvg_mask_blend_u8", ptr(a), ptr(b), ptr(m), T, H, W, rp, ptr(out), *ws, stream())
+    return out[0] if image else out
+
+
 # one hpvg_patchproj_hist_u8 launch fills at most this many bytes of histogram: the atomics' footprint stays within the 256 MB
 # last-level cache, and the benchmarked case (512 directions at 3 x 7 x 7: 231 MB) is still one launch.  More directions go in
 # chunks of whole 128-direction tiles (one direction at a time where a single histogram row passes the cap), each chunk packing

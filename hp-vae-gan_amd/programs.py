@@ -5,7 +5,8 @@ a second import under its own name would load it twice.
 
 Shared: the flags every trainer holds (trainer_parser), the run directory, the logbook, frames on disk, the trainer setup and
 stage loop (Program, which train_video_baselines.BaselineProgram adjusts), and the helpers of the sampling and scoring
-programs: gpu_device, load_opt, default_patch, load_u8_frames, write_samples, real_volume.
+programs: gpu_device, load_opt, default_patch, load_u8_frames, write_samples, real_volume, the hole-mask readers (mask_forms,
+pick_mask) and the --guide flags of generate and generate_patchnn (add_guide_flags, check_guide_flags, load_guide_frames).
 
 The trainers follow the reference's programs (train_video.py:265-417, train_image.py:279-440): the same flags, the same
 setup (noise_amp_init / scale_factor_init, adjust_scales2image, manualSeed drawn when absent and logged, then random.seed
@@ -602,6 +603,98 @@ class Program:
 def train_main(kind, argv=None):
     Program(kind, argv).run()
     return 0
+
+
+# Hole masks (generate_patchnn --mask, --guide-mask of generate and generate_patchnn): what the programs share.
+def mask_forms(path, who="generate_patchnn: --mask"):
+    """Every [T,H,W] bool reading of a mask input, as host arrays: a .npy [T,H,W] or [H,W] (bool or uint8) as it is, and an
+    input with a last axis of 3 ([...,3] .npy, an image file, a frame directory) with any nonzero channel as hole.  An array
+    [H,W,3] has both readings; the volume's shape decides between them (pick_mask).  Another dtype or rank ends the program,
+    under the program and flag `who`."""
+    ra = datasets.load_frames(path)
+    if ra.dtype not in (np.bool_, np.uint8):
+        raise SystemExit("{} must be bool or uint8, got {} {}".format(who, ra.dtype, ra.shape))
+    forms = ([ra] if ra.ndim in (2, 3) else []) + ([ra.any(-1)] if ra.ndim in (3, 4) and ra.shape[-1] == 3 else [])
+    if not forms:
+        raise SystemExit("{} must be [T,H,W], [H,W] or either with a last axis of 3, got {}".format(who, ra.shape))
+    return [np.ascontiguousarray((m[None] if m.ndim == 2 else m) != 0) for m in forms]
+
+
+def pick_mask(forms, shape, who="generate_patchnn: --mask", what="the real volume's"):
+    """The reading of mask_forms with the volume's (T, H, W) = shape; none ends the program."""
+    for m in forms:
+        if tuple(m.shape) == tuple(shape):
+            return m
+    raise SystemExit("{} must have {} shape {}, got {}".format(
+        who, what, tuple(shape), " or ".join(str(tuple(m.shape)) for m in forms)))
+
+
+def refuse_trivial_mask(forms, who="generate_patchnn: --mask"):
+    """End the program when every reading in `forms` is empty, or every one is all hole."""
+    if all(not m.any() for m in forms) or all(m.all() for m in forms):
+        raise SystemExit("{} is {}".format(who, "empty" if not forms[0].any() else "all hole"))
+
+
+# Guided sampling (generate --guide, generate_patchnn --guide): the flags, their refusals and the guide's frames.
+GUIDE_FEATHER = (1, 5, 5)          # --guide-feather of a clip; an image has RT = 0
+GUIDE_FEATHER_MAX = 64             # ops.mask_blend's largest radius
+
+
+def add_guide_flags(p):
+    """The four flags both sampling programs take, with defaults that leave a run without them as it was."""
+    p.add_argument('--guide', default=None, metavar='PATH', help='start from this clip / image (.npy, a frame directory or an image '
+                   'file) injected at pyramid level --guide-level, instead of from noise: the levels above re-render it with the '
+                   'input\'s own statistics')
+    p.add_argument('--guide-level', type=int, default=None, metavar='N', help='the pyramid level (0 = coarsest) that takes the guide; '
+                   'required with --guide')
+    p.add_argument('--guide-mask', default=None, metavar='PATH', help='keep the samples only inside this hole mask (the forms of '
+                   'generate_patchnn --mask; nonzero = hole) and the guide elsewhere, feathered by --guide-feather')
+    p.add_argument('--guide-feather', type=int, nargs=3, default=None, metavar=('RT', 'RH', 'RW'), help='dilation and feather radius '
+                   'of --guide-mask per axis, each in [0, {}] (default {} {} {}; images 0 {} {}, RT must be 0)'.format(
+                       GUIDE_FEATHER_MAX, *GUIDE_FEATHER, *GUIDE_FEATHER[1:]))
+    return p
+
+
+def check_guide_flags(who, guide, guide_level, guide_mask, guide_feather, image):
+    """The refusals of the --guide flags that need no device and no other input, under the program name `who`.  Returns
+    (feather, forms): the feather in force ((rt, rh, rw), None without --guide-mask) and the readings of the mask (mask_forms,
+    None without one); (None, None) without --guide.  image: the run is an image run (the feather's default, and RT = 0)."""
+    if guide is None:
+        for flag, v in (('--guide-level', guide_level), ('--guide-mask', guide_mask), ('--guide-feather', guide_feather)):
+            if v is not None:
+                raise SystemExit("{}: {} needs --guide".format(who, flag))
+        return None, None
+    if guide_level is None:
+        raise SystemExit("{}: --guide needs --guide-level (the pyramid level that takes the guide)".format(who))
+    if guide_feather is not None:
+        guide_feather = tuple(int(e) for e in guide_feather)
+        if len(guide_feather) != 3 or min(guide_feather) < 0 or max(guide_feather) > GUIDE_FEATHER_MAX:
+            raise SystemExit("{}: --guide-feather takes RT RH RW, each in [0, {}], got {}".format(
+                who, GUIDE_FEATHER_MAX, list(guide_feather)))
+        if guide_mask is None:
+            raise SystemExit("{}: --guide-feather needs --guide-mask".format(who))
+        if image and guide_feather[0] != 0:
+            raise SystemExit("{}: --guide-feather of an image has RT = 0, got {}".format(who, list(guide_feather)))
+    if guide_mask is None:
+        return None, None
+    feather = guide_feather if guide_feather is not None else ((0,) + GUIDE_FEATHER[1:] if image else GUIDE_FEATHER)
+    forms = mask_forms(guide_mask, who + ": --guide-mask")
+    refuse_trivial_mask(forms, who + ": --guide-mask")
+    return feather, forms
+
+
+def load_guide_frames(who, path):
+    """The guide's frames as a host array uint8 [N,H,W,3] (datasets.load_frames; an array [H,W,3] is one frame); anything else ends
+    the program."""
+    try:
+        ra = datasets.load_frames(path)
+    except (OSError, NotImplementedError, ValueError) as e:
+        raise SystemExit("{}: --guide {}: {}".format(who, path, e))
+    if ra.ndim == 3:
+        ra = ra[None]
+    if ra.dtype != np.uint8 or ra.ndim != 4 or ra.shape[-1] != 3 or min(ra.shape) < 1:
+        raise SystemExit("{}: --guide must be uint8 [N,H,W,3] or [H,W,3], got {} {}".format(who, ra.dtype, ra.shape))
+    return np.ascontiguousarray(ra)
 
 
 # Rings (generate_patchnn --wrap, evaluate --wrap): what the two programs share.

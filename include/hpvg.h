@@ -477,6 +477,27 @@ int hpvg_volume_resize_check(int Ts, int Hs, int Ws, int To, int Ho, int Wo, lon
  * is HPVG_ERR_ARG.  One launch on `stream`, no workspace, no atomics, no host synchronisation. */
 int hpvg_volume_resize_u8(const unsigned char* src, int Ts, int Hs, int Ws, unsigned char* out, int To, int Ho, int Wo,
                           void* stream);
+/* ---- the feathered composite (generate --guide-mask, generate_patchnn --guide-mask): out takes volume a inside a hole, volume b
+ * far from it and an exact integer blend in between.  a, b, out: [T][H][W][3] uint8; mask: [T][H][W] uint8, nonzero = hole;
+ * radius = (rt, rh, rw): host array of 3 ints, each in [0, 64].  All volumes on the device, at any byte offset.
+ *   box(v) = the voxels u of the volume with |u_ax - v_ax| <= r_ax on every axis (clipped at the borders);
+ *   dil(u) = 1 iff some voxel of box(u) is a hole, else 0;
+ *   c(v) = the number of u in box(v) with dil(u) = 1;  n(v) = |box(v)|;
+ *   out = (2 (c a + (n - c) b) + n) / (2 n) per channel, in integer arithmetic: the weighted mean, halves rounded up.
+ * So out = a on every hole voxel (every u of box(v) has v in box(u): c = n); out = b on every voxel farther than 2 r_ax from
+ * every hole voxel along some axis (c = 0); radius (0, 0, 0) is the hard composite (a on the hole, b elsewhere); an empty mask
+ * returns b and a full mask a.  The numerator fits 32 bits: n <= 129^3 and 129^3 * 255 * 2 + 129^3 < 2^31.
+ *   Dilation (a maximum) and the box count (a sum) are separable: the work is 1-D passes through the workspace, a pass of radius
+ * 0 is skipped, and the last pass sums along t and blends.  No atomics, no host synchronisation, every launch on `stream`
+ * (capturable), and the result is a function of the arguments alone - not of launch geometry, stream or timing.
+ *   HPVG_ERR_ARG: a side < 1, a radius outside [0, 64], a null a / b / mask / out / radius, out overlapping a, b or mask.
+ * HPVG_ERR_UNSUPPORTED: a volume of 2^31 voxels or more.  HPVG_ERR_WORKSPACE: ws null, not 16-byte aligned or shorter than
+ * hpvg_mask_blend_ws_bytes() (radius (0, 0, 0) needs no workspace and takes a null one).  Refusals come before any launch. */
+/* host only: bytes of workspace (two byte planes and two uint16 planes of the volume; 0 for radius (0, 0, 0) and for arguments
+ * hpvg_mask_blend_u8 refuses) */
+size_t hpvg_mask_blend_ws_bytes(int T, int H, int W, const int* radius);
+int hpvg_mask_blend_u8(const unsigned char* a, const unsigned char* b, const unsigned char* mask, int T, int H, int W,
+                       const int* radius, unsigned char* out, void* ws, size_t ws_bytes, void* stream);
 /* The copied regions ("chunks") of a nearest-neighbour field (evaluate --chunks).  nn: int32 [Nq] on the device over the query
  * patch grid qgrid = (gT, gH, gW), raster order (t, y, x), holding indices into the key patch grid rgrid = (kT, kH, kW),
  * Nr = kT kH kW; d2: int32 [Nq] or NULL.  qgrid / rgrid / qstride / rstride: host arrays of 3 ints.  Patch i at grid coordinate
